@@ -235,6 +235,27 @@ def committed_traffic(case, envs):
     return None, None
 
 
+# ------------------------------------------------------------------------------------------------ output dump
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, outputs, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64; `terminated` as float32 0 / 1).  Every array has the env
+    axis first; if they add up to more than `max_bytes`, the same fixed, seeded sample of envs (sorted) is kept from each and
+    its indices are written as env_index.npy."""
+    import numpy as np
+    arrs = {k: (v.astype(np.float32) if v.dtype not in (np.float32, np.float64) else v) for k, v in outputs.items()}
+    n = next(iter(arrs.values())).shape[0]
+    per_env = sum(v.nbytes for v in arrs.values()) // n
+    if per_env * n > max_bytes:
+        keep = np.sort(np.random.default_rng(seed).choice(n, max(1, (max_bytes - 8 * n) // (per_env + 8)), replace=False))
+        arrs = {k: v[keep] for k, v in arrs.items()}
+        arrs["env_index"] = keep.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(outdir, f"{k}.npy"), np.ascontiguousarray(v))
+
+
 # ------------------------------------------------------------------------------------------------ launcher
 def _free_port():
     s = socket.socket()
@@ -272,8 +293,12 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl == RCCL on ROCm); 'gloo' only to "
                                                         "exercise the N>1 path on a box with fewer GPUs than ranks")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="repeat the timed --steps block until the blocks add up to this")
-    ap.add_argument("--repeats", type=int, default=0, help="exactly this many timed blocks (0: repeat until --min-seconds)")
+    ap.add_argument("--min-seconds", type=float, default=0.5, help="with --repeats 0: repeat the timed --steps block until the blocks add up to this")
+    ap.add_argument("--repeats", type=int, default=1, help="exactly this many timed blocks of --steps steps each (default 1: the timed region "
+                                                           "is exactly --steps steps; 0: repeat until --min-seconds)")
+    ap.add_argument("--device-warmup", type=float, default=0.5, help="seconds of steps on a throwaway env of the same shape before the "
+                                                                    "measured env's --warmup steps (device clocks at their steady state; "
+                                                                    "the measured env is not touched; 0: off)")
     ap.add_argument("--inner", action="store_true", help="(internal) short un-instrumented loop for the PMC sub-runs")
     ap.add_argument("--no-other-shapes", action="store_true", help="skip the short case33 / case322 measurements appended to the default line")
     ap.add_argument("--env-id-offset", type=int, default=0, help="global id of this run's first env (a 1-rank run that covers the ids "
@@ -284,6 +309,8 @@ def main():
                                                               "all_reduce and the barriers) even at --gpus 1: first contact with RCCL on one GPU")
     ap.add_argument("--dump-returns", default=None, help="rank 0 writes the gathered per-env episode returns of the LAST timed block "
                                                          "to this .npy file (pre-flight checks of the N > 1 path)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the LAST timed step handed its caller (reward, "
+                                                                          "terminated, info, obs of its env shard) to DIR/<name>.npy, float32 / float64")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -329,7 +356,26 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    def measure(case, B, min_seconds, inner=False):
+    def warm_device(net, prof, args, B, id0, acts, seconds):
+        """`seconds` of step()+get_obs() on a throwaway env of the measured shape, so that the timed block starts on a device at its
+        steady clock; the measured env, its actions and its step count are untouched"""
+        if seconds <= 0:
+            return
+        scratch = VoltageControlBatch(net, prof, args, n_envs=B, device=dev, env_id_offset=id0)
+        scratch.reset()
+        n, t0 = 0, time.perf_counter()
+        while time.perf_counter() - t0 < seconds:
+            scratch.step(acts[n % acts.shape[0]])
+            scratch.get_obs()
+            n += 1
+            if n % (scratch.episode_limit - 1) == 0:
+                scratch.reset()
+            if n % 20 == 0:                                    # the host enqueues faster than the device runs: keep them together
+                torch.cuda.synchronize(dev)
+        torch.cuda.synchronize(dev)
+        scratch.close()
+
+    def measure(case, B, min_seconds, inner=False, dump=False):
         """The timed loop on one (case, envs per GPU): returns the block times (max over ranks), the env and its NR timing."""
         net, prof = make_case(case)
         args = dict(episode_limit=240, action_scale=SCALE[case], action_bias=0.0, voltage_barrier_type="bowl", seed=0)
@@ -345,14 +391,18 @@ def main():
         acts = torch.empty(n_act, B, env.n_sgen, dtype=torch.float32, device=dev).uniform_(-scale, scale, generator=gen)
         steps_in_ep, step_no, resets = [0], [0], [0]
         last_returns = [None]
+        last_out = [None]                                    # (reward, terminated, info, obs) of the latest step: views of the env's buffers
 
         def one_step():
             act = acts[step_no[0] % n_act]
             step_no[0] += 1
-            env.step(act)
-            env.get_obs()
+            reward, term, info = env.step(act)
+            obs = env.get_obs()
+            last_out[0] = (reward, term, info, obs)
             steps_in_ep[0] += 1
             if steps_in_ep[0] >= env.episode_limit - 1:       # all envs terminate together (:204)
+                if dump:                                      # reset() overwrites the obs buffer: keep this step's outputs
+                    last_out[0] = tuple(t.clone() for t in last_out[0])
                 env.reset()
                 resets[0] += 1
                 steps_in_ep[0] = 0
@@ -379,6 +429,8 @@ def main():
             return dt
 
         env.reset()
+        if not inner:
+            warm_device(net, prof, args, B, id0, acts, min(a.device_warmup, min_seconds))
         for _ in range(a.warmup):
             one_step()
         if inner:
@@ -393,6 +445,9 @@ def main():
         while (len(blocks) < a.repeats) if a.repeats > 0 else (len(blocks) < 3 or (sum(blocks) < min_seconds and len(blocks) < 2000)):
             blocks.append(timed_block())
         resets_in_region = resets[0]
+        outputs = None
+        if dump:                                             # before the kernel-timing pass below steps the env further
+            outputs = {k: t.detach().cpu().numpy() for k, t in zip(("reward", "terminated", "info", "obs"), last_out[0])}
         stats = env.stats()
         # ---- dominant kernel (NR solve) duration, HIP events on its launch stream, separate short pass
         # (>= 240 step launches whatever --steps is: 20 launches gave +-5 %; the power flow of a reset — another launch shape, no fused
@@ -420,16 +475,18 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
             nr_per_rank = [float(x) for x in t.tolist()]
         return dict(env=env, blocks=blocks, resets=resets_in_region, stats=stats, nr_per_rank=nr_per_rank, nr_launches=nr_launches,
-                    returns=last_returns[0])
+                    returns=last_returns[0], outputs=outputs)
 
     B = a.envs
-    m = measure(a.case, B, a.min_seconds, inner=a.inner)
+    m = measure(a.case, B, a.min_seconds, inner=a.inner, dump=bool(a.dump_outputs) and rank == 0)
     if a.inner:
         return
     env, blocks, resets_in_region, stats = m["env"], m["blocks"], m["resets"], m["stats"]
     nr_per_rank, nr_launches = m["nr_per_rank"], m["nr_launches"]
     if a.dump_returns and rank == 0 and m["returns"] is not None:
         np.save(a.dump_returns, m["returns"].detach().cpu().numpy())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, m["outputs"])
     blocks_sorted = sorted(blocks)
     dt = blocks_sorted[len(blocks) // 2]
     kname = "k_nr_tree"
@@ -543,7 +600,7 @@ def main():
             "metric": "env-steps/sec (whole node), case141 batch=4096, at 1/2/4/8 MI355X",
             "value": value, "unit": "env-steps/s", "n_gpus": n_gpus, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "repeats": len(blocks), "timed_seconds_total": sum(blocks),
+            "repeats": len(blocks), "timed_steps": len(blocks) * a.steps, "device_warmup_seconds": min(a.device_warmup, a.min_seconds), "timed_seconds_total": sum(blocks),
             "ms_per_step_repeats": {"min": blocks_sorted[0] / a.steps * 1e3, "median": dt / a.steps * 1e3,
                                     "max": blocks_sorted[-1] / a.steps * 1e3},
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
