@@ -169,8 +169,13 @@ typedef struct mapdn_env_config {
                                        coincide on every net with sn_mva == 1 (all MAPDN scenarios and bench nets);
                                        tests/test_pandapower_pin.py::test_tolerance_rule_on_sn_mva_not_one decides which one
                                        pandapower uses wherever pandapower is installed                                    */
-  int32_t nr_init;                  /* runpp(init=...): 0 "auto" / "flat" — every solve starts at the slack set-point, what the
-                                       reference does (exact pandapower iterates).  1 ("results": start a step() solve from the
+  int32_t nr_init;                  /* runpp(init=...): 0 "flat" — every solve starts at the slack set-point, what runpp's
+                                       init="auto" does on a net without lines above 70 kV (exact pandapower iterates).
+                                       2 "dc" — what init="auto" does when calculate_voltage_angles is on (a line at a bus above
+                                       70 kV): every solve (step, reset, solve_only) starts from the angles of a DC power flow
+                                       on the env's own injection, magnitudes at the slack set-point (pandapower run_dc_pf;
+                                       mapdn_get_dc_angles).  Tree and sparse solvers; refused (MAPDN_E_INVALID) with
+                                       nr_solver = dense and on a net with fused buses (bus_alias).  1 ("results": start a step() solve from the
                                        env's last accepted voltages, fall back to the flat start after 3 iterations) is RESERVED
                                        and refused (MAPDN_E_INVALID): the study that was to gate it (tools/history/warm_start_study.py,
                                        profiles/r04_warm_start_study_*.json: 3.6 M solves on the oracle, 15 % of them stressed
@@ -180,7 +185,7 @@ typedef struct mapdn_env_config {
                                        Newton iterations than the flat start (mean 4.12 -> 4.23 iterations on the 141-bus feeder,
                                        4.56 -> 6.34 on the 33-bus one, with the fallback), and under a smooth policy only 43 % /
                                        79 % of the envs (141 / 322 buses) save an iteration, while a workgroup's 16 envs finish
-                                       together: P(all 16 save one) ~ 0.  Not built.                                           */
+                                       together: P(all 16 save one) ~ 0.  Not built.  Other values: MAPDN_E_INVALID.         */
   /* ---- composition of the step() launches (same results; A/B switches) */
   int32_t fuse_inject;              /* step(): 0 auto — the PV-bus injection (_clip_reactive_power, Sbus of the buses with sgens)
                                        runs inside the prologue of k_nr_tree when the handle uses the tree solver and has no
@@ -302,8 +307,17 @@ int mapdn_get_schedule(const mapdn_handle* h, int32_t n_waves, int32_t* n_rows, 
  * device): out[20] = solver (0 tree, 1 sparse, 2 dense), waves, lanes (envs per workgroup), lean, schedule rows, h_lds, g_lds,
  * rec_lds, flat_lds, line_lds, mm_pass, dynamic LDS bytes per workgroup, workgroups, workgroups resident per CU (model),
  * rounds of workgroups, modelled launch time in ns (the chooser's score; 0 when the geometry was forced), fuse_inject (1: step()
- * performs the PV-bus injection in the solver's prologue), number of buses in fused groups (bus_alias), electrical nodes, 0. */
+ * performs the PV-bus injection in the solver's prologue), number of buses in fused groups (bus_alias), electrical nodes, nr_init
+ * (0 flat start, 2 DC-angle start). */
 int mapdn_get_nr_geometry(const mapdn_handle* h, int32_t* out20);
+
+/* Host-side export of the DC-angle start (nr_init = 2, runpp init="dc"; plan check, CPU tests): the angles va_rad [n_bus] (rad, slack 0)
+ * that the solvers start from for the net bus demand p_bus_demand_mw [n_bus] (MW, consumer sign: loads minus sgens after scaling),
+ * computed on the host from the handle's plan constants in the solver's own order of operations — the tree sweeps of k_nr_tree, or
+ * the block program of k_nr_sparse on the Bbus assembly.  Solves Bbus[pvpq, pvpq] Va[pvpq] = Pbus[pvpq] with
+ * Bbus = (Cf - Ct)' diag(1 / (x |tap|)) (Cf - Ct), Pbus = -P_demand / sn_mva - (Cf - Ct)' (b (-shift)) - GS / sn_mva (pandapower
+ * run_dc_pf).  HOST pointers; works on host-only handles.  MAPDN_E_INVALID on a net with fused buses. */
+int mapdn_get_dc_angles(const mapdn_handle* h, const double* p_bus_demand_mw, double* va_rad);
 
 /* Host-side export of the flat-start factorisation the NR kernel's first iteration uses (plan check, CPU tests):
  * factors [n][12] per elimination position = S_calc (re, im), D^-1 (4, row-major), A_pk (re, im), G (4, row-major)

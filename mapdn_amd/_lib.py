@@ -35,7 +35,7 @@ EXPORTS = (
     "mapdn_get_nr_geometry", "mapdn_debug_stream", "mapdn_build_info", "mapdn_layernorm64_bc_forward", "mapdn_layernorm64_bc_backward", "mapdn_relu_dot64_forward", "mapdn_relu_dot64_backward",
     "mapdn_critic_head_forward", "mapdn_critic_head_scratch_floats", "mapdn_critic_head_backward", "mapdn_critic_head_backward_dot", "mapdn_critic_head_mse", "mapdn_get_profile_stats",
     "mapdn_explore_actions", "mapdn_rollout_stats", "mapdn_copy_segments",
-    "mapdn_policy_forward_train", "mapdn_policy_backward", "mapdn_policy_backward_scratch_floats",
+    "mapdn_policy_forward_train", "mapdn_policy_backward", "mapdn_policy_backward_scratch_floats", "mapdn_get_dc_angles",
 )
 
 _pd = C.POINTER(C.c_double)
@@ -81,8 +81,9 @@ TUNING_INT = ("nr_solver", "nr_waves", "nr_lanes", "nr_lean", "nr_h_lds", "nr_g_
               "nr_mm_pass", "sp_lanes", "inject_full", "debug_geometry", "tolerance_is_pu", "nr_init", "fuse_inject", "overlap_advance", "xcd_map")
 TUNING_F64 = ("nr_check_dx", "nr_check_quad", "tolerance_mva")
 NR_SOLVERS = dict(auto=0, tree=0, sparse=1, dense=2)
+NR_INITS = dict(flat=0, dc=2)   # mapdn_env_config.nr_init: runpp init="flat" / init="dc" (1, init="results", is reserved)
 GEOMETRY_KEYS = ("solver", "waves", "lanes", "lean", "rows", "h_lds", "g_lds", "rec_lds", "flat_lds", "line_lds", "mm_pass",
-                 "lds_bytes", "workgroups", "resident_per_cu", "rounds", "model_ns", "fuse_inject", "n_fused_buses", "n_nodes", "reserved")
+                 "lds_bytes", "workgroups", "resident_per_cu", "rounds", "model_ns", "fuse_inject", "n_fused_buses", "n_nodes", "nr_init")
 
 
 class CDims(C.Structure):
@@ -170,6 +171,7 @@ def load():
     lib.mapdn_get_obs_index.argtypes = [vp, _pi, _pi]
     lib.mapdn_get_schedule.argtypes = [vp, C.c_int32, _pi, _pi, _pi]
     lib.mapdn_get_flat_factors.argtypes = [vp, _pd, _pi]
+    lib.mapdn_get_dc_angles.argtypes = [vp, _pd, _pd]
     lib.mapdn_get_nr_geometry.argtypes = [vp, _pi]
     lib.mapdn_debug_stream.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp]
     lib.mapdn_get_sparse_program.argtypes = [vp, C.c_int32, _pi, _pi, _pi, _pi]
@@ -263,11 +265,16 @@ def make_cnetspec(net: NetSpec):
 
 def make_cconfig(args: dict, env_id_offset: int = 0, tuning: dict | None = None) -> CEnvConfig:
     """mapdn_env_config from the reference's constructor kwargs; `tuning` fills the appended launch / solver fields
-    (include/mapdn.h: nr_waves, nr_lanes, nr_lean, nr_*_lds, nr_mm_pass, nr_solver = 'sparse' | 'dense', nr_init, tolerance_mva ...)."""
+    (include/mapdn.h: nr_waves, nr_lanes, nr_lean, nr_*_lds, nr_mm_pass, nr_solver = 'sparse' | 'dense', nr_init = 'flat' | 'dc',
+    tolerance_mva ...)."""
     c = CEnvConfig()
     for k, v in (tuning or {}).items():
         if k == "nr_solver" and isinstance(v, str):
             v = NR_SOLVERS[v]
+        if k == "nr_init" and isinstance(v, str):
+            if v not in NR_INITS:
+                raise ValueError(f"nr_init must be one of {sorted(NR_INITS)} (or 0 / 2), got {v!r}")
+            v = NR_INITS[v]
         if k in TUNING_INT:
             setattr(c, k, int(v))
         elif k in TUNING_F64:

@@ -180,7 +180,7 @@ static int settle_tree_geometry(mapdn_handle* h, int Bp, int n_cu) {
       min_rows = need;
     }
     if (min_rows >= 0) { h->err = "NR schedule: could not settle the number of peeled rows"; return MAPDN_E_INVALID; }
-    const int compiled = nr_geometry_compiled(W, L, g.h_lds, g.g_lds, g.rec_lds, g.flat_lds);
+    const int compiled = nr_geometry_compiled(W, L, g.h_lds, g.g_lds, g.rec_lds, g.flat_lds, c.nr_init == 2);
     if (!compiled) return 1;
     g.W = W; g.L = L; g.lean = lean; g.rows = S.R;
     g.wgs = Bp / L;
@@ -253,12 +253,18 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
   if (!cfg->use_line_weight && !cfg->use_q_weight) {   // voltage_control_env.py:616-617
     h->err = "NotImplementedError: Please at least give one weight, either q_weight or line_weight."; return MAPDN_E_INVALID; }
   if (cfg->episode_limit < 2) { h->err = "episode_limit must be >= 2"; return MAPDN_E_INVALID; }
-  if (cfg->nr_init != 0) {   // reserved: see include/mapdn.h (the gating study found the warm start safe but without effect on the launch time)
+  if (cfg->nr_init == 1) {   // reserved: see include/mapdn.h (the gating study found the warm start safe but without effect on the launch time)
     h->err = "nr_init != 0 (warm start, runpp init=\"results\") is not built: tools/warm_start_study.py / profiles/r04_warm_start_study_*.json "
              "show no iteration saved per 16-env workgroup; every solve starts flat like the reference's";
     return MAPDN_E_INVALID; }
+  if (cfg->nr_init != 0 && cfg->nr_init != 2) { h->err = "nr_init must be 0 (flat start) or 2 (runpp init=\"dc\"); 1 (init=\"results\") is reserved"; return MAPDN_E_INVALID; }
   int rc = build_plan(*net, *cfg, h->plan, h->err);
   if (rc) return rc;
+  if (cfg->nr_init == 2 && !h->plan.dc_ok) {
+    h->err = !h->plan.fused_obus.empty()
+                 ? "nr_init = 2 (runpp init=\"dc\") on a net with fused buses (bus_alias) is not supported (the DC-angle start is defined on unfused nets only)"
+                 : "nr_init = 2 (runpp init=\"dc\"): the DC power flow matrix Bbus of this net is singular or not finite (a branch with x = 0?)";
+    return MAPDN_E_INVALID; }
   {
     // Solver choice.  pp.runpp (voltage_control_env.py:557) solves any connected net: radial feeders take the fill-free
     // tree kernel; meshed nets the general sparse kernel (host symbolic factorisation with fill + a block program, all
@@ -273,6 +279,9 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
     const bool want_sparse = !want_dense && (pick == 1 || !P0.radial);
     if (want_dense) {
       if (2 * P0.n > 1024) { h->err = "nr_solver = dense (MAPDN_NR_DENSE): the dense general-topology solver handles at most 513 buses (one thread per Jacobian row)"; return MAPDN_E_TOPOLOGY; }
+      if (cfg->nr_init == 2) {
+        h->err = "nr_init = 2 (runpp init=\"dc\") is not built for nr_solver = dense (k_nr_dense starts flat only): use the tree or the sparse solver";
+        return MAPDN_E_INVALID; }
       h->solver = 2;
     } else if (want_sparse) {
       SparseProg g0;
@@ -312,7 +321,9 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
   d.action_low = cfg->action_low; d.action_high = cfg->action_high;
   d.seed_lo = (uint32_t)(cfg->seed & 0xffffffffull); d.seed_hi = (uint32_t)(cfg->seed >> 32);
   d.env_id_offset = cfg->env_id_offset;
+  d.nr_init = cfg->nr_init;
 #define UP(field, vec) do { rc = dupload(h, &d.field, vec); if (rc) return rc; } while (0)
+  if (d.nr_init == 2) UP(dc_pc, P.dc_pc);
   UP(bus_of_pos, P.bus_of_pos); UP(root_children, P.root_children); UP(root_y, P.root_y);
   UP(pos_of_obus, P.pos_of_obus); UP(cm_kind, P.cm_kind);
   d.n_fused = (int32_t)P.fused_obus.size(); d.n_alias = (int32_t)P.alias_pos.size(); d.n_slack_group = (int32_t)P.slack_group.size();
@@ -543,7 +554,7 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
   {
     // the attribute is per kernel function, not per handle: always raise it to the full 160 KB so that
     // handles with different LDS needs can share an instantiation
-    const int lr = nr_set_lds_limit(G_.W, G_.L, G_.h_lds, G_.g_lds, G_.rec_lds, G_.flat_lds, 160 * 1024);
+    const int lr = nr_set_lds_limit(G_.W, G_.L, G_.h_lds, G_.g_lds, G_.rec_lds, G_.flat_lds, 160 * 1024, d.nr_init == 2);
     if (lr == -2) { h->err = "this (nr_waves, nr_lanes) combination is not compiled in (csrc/nr_inst_list.hpp)"; return MAPDN_E_INVALID; }
     if (lr != 0) { (void)hipGetLastError(); h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return MAPDN_E_HIP; }
   }
@@ -553,6 +564,7 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
   UP(mm_recs, h->sched.mm_recs); d.mm_recs_bytes = (uint32_t)(h->sched.mm_recs.size() * sizeof(StepRec)); d.mm_np = h->sched.mm_np;
   d.nr_mm_pass = G_.mm_pass;   // the predicted-final mismatch evaluation as a barrier-free pass over all nodes instead of a tree sweep
   UP(flat, h->sched.flat); d.flat_bytes = (uint32_t)(h->sched.flat.size() * sizeof(double));
+  if (d.nr_init == 2) { UP(dc_recs, h->sched.dc_recs); d.dc_recs_bytes = (uint32_t)(h->sched.dc_recs.size() * sizeof(DcRec)); }
   {  // NR scratch: factor blocks (one per node) | 2 x Sbus (one entry per node) | Vout
     const size_t nblk = (size_t)P.n + 2;           // Sbus by node position (+ slack, + the trash node of idle steps: stays 0)
     const size_t fb_rows = (h_lds && g_lds) ? 0 : (size_t)(P.n + 2) * NBP;   // pair rows of Bp x 16 bytes: one block per node (+ slack, trash)
@@ -917,9 +929,67 @@ int mapdn_get_nr_geometry(const mapdn_handle* h, int32_t* out) try {
                              knob_tri(h->cfg.fuse_inject, "MAPDN_FUSE_INJECT") != 2;
   const int32_t v[20] = {h->solver, g.W, g.L, g.lean, g.rows, g.h_lds, g.g_lds, g.rec_lds, g.flat_lds, g.line_lds, g.mm_pass,
                          (int32_t)h->lds_bytes, (int32_t)g.wgs, g.resident, g.rounds, (int32_t)std::min(g.model_ns, 2.0e9),
-                         (h->host_only ? fuse_possible : h->fuse_inject) ? 1 : 0, (int32_t)h->plan.fused_obus.size(), h->plan.nb, 0};
+                         (h->host_only ? fuse_possible : h->fuse_inject) ? 1 : 0, (int32_t)h->plan.fused_obus.size(), h->plan.nb, h->cfg.nr_init};
   std::memcpy(out, v, sizeof(v));
   if (h->solver == 1) out[2] = h->sp_lanes;
+  return MAPDN_OK;
+} MAPDN_CATCH(h)
+
+int mapdn_get_dc_angles(const mapdn_handle* h, const double* p_bus_demand_mw, double* va_rad) try {
+  if (!h || !p_bus_demand_mw || !va_rad) return MAPDN_E_INVALID;
+  const Plan& P = h->plan;
+  if (!P.dc_ok) return api_fail(h, MAPDN_E_INVALID, P.fused_obus.empty() ? "the DC power flow matrix Bbus of this net is singular or not finite"
+                                                                          : "the DC-angle start is not defined on a net with fused buses (bus_alias)");
+  const int n = P.n;
+  std::vector<double> pbus(n);                   // Pbus = Re(Sbus) + dc_pc, Re(Sbus) = -P_demand / sn (as the injection forms it)
+  for (int k = 0; k < n; ++k) pbus[k] = -p_bus_demand_mw[P.bus_of_pos[k]] / P.sn_mva + P.dc_pc[k];
+  std::vector<double> th(n + 1, 0.0);            // by position; the slack (n) stays 0
+  if (h->solver == 0) {                          // k_nr_tree's sweeps, node by node (children in the canonical order)
+    Schedule S;
+    build_schedule(P, 1, S);
+    std::vector<double> c(n, 0.0), hh(n, 0.0);
+    for (int k = 0; k < n; ++k) {
+      double y = pbus[k];
+      for (int j = S.mm_ptr[k]; j < S.mm_ptr[k + 1]; ++j) y -= c[S.mm_child[j]];
+      hh[k] = y * P.dc_id[k];
+      c[k] = P.dc_bpk[k] * hh[k];
+    }
+    for (int k = n - 1; k >= 0; --k) th[k] = std::fma(-P.dc_g[k], th[P.par[k]], hh[k]);
+  } else {                                       // k_nr_sparse's block program on the Bbus assembly
+    SparseProg G;
+    const int S = h->sp_lanes ? 64 / h->sp_lanes : 4;
+    sparse_program(P, S, G);
+    std::vector<double> B((size_t)G.n_blocks * 4, 0.0);          // a00 a01 a10 a11
+    for (size_t r = 0; r < G.rows.size(); ++r) {
+      const SpRow& R = G.rows[r];
+      if (!R.live) continue;
+      const int i = (int)R.node;
+      for (int q = 0; q < G.max_nnz; ++q) {
+        const SpNz& z = G.nz[r * G.max_nnz + q];
+        if ((int)z.col == i) B[(size_t)i * 4] = z.bdc;
+        else if (z.slot >= 0) { double* o = &B[(size_t)z.slot * 4]; o[0] = z.bdc; o[1] = o[2] = o[3] = 0.0; }
+      }
+      B[(size_t)i * 4 + 3] = 1.0;
+      B[(size_t)(n + i) * 4] = pbus[i];
+    }
+    for (int p = 0; p < G.n_phases; ++p)
+      for (int s = 0; s < S; ++s) {
+        const SpOp& op = G.ops[(size_t)p * S + s];
+        const unsigned type = op.type & 255u;
+        if (type == 0u) continue;
+        const double* a = &B[(size_t)op.a * 4]; const double* b = &B[(size_t)op.b * 4];
+        double r[4];
+        if (type == 1u) { const double id = 1.0 / (a[0] * a[3] - a[1] * a[2]); r[0] = a[3] * id; r[1] = -a[1] * id; r[2] = -a[2] * id; r[3] = a[0] * id; }
+        else {
+          const double m[4] = {a[0] * b[0] + a[1] * b[2], a[0] * b[1] + a[1] * b[3], a[2] * b[0] + a[3] * b[2], a[2] * b[1] + a[3] * b[3]};
+          const double* c0 = &B[(size_t)op.c * 4];
+          for (int j = 0; j < 4; ++j) r[j] = type == 2u ? m[j] : c0[j] - m[j];
+        }
+        std::memcpy(&B[(size_t)op.c * 4], r, sizeof(r));
+      }
+    for (int i = 0; i < n; ++i) th[i] = B[(size_t)(n + i) * 4];
+  }
+  for (int b = 0; b < P.nbo; ++b) va_rad[b] = th[P.pos_of_obus[b]];
   return MAPDN_OK;
 } MAPDN_CATCH(h)
 

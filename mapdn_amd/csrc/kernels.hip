@@ -618,23 +618,26 @@ void launch_inject(const Dev& d, int mode, const void* actions, int dtype, const
 }
 // k_nr_tree instantiations: tables exported by the parts of nr_inst.hip (nr_inst_list.hpp).  RES is the residency of the step
 // records / flat-start constants as a compile-time fact (1 both, 2 neither, 3 records only); 0 = the generic body.
-static const NrInst* nr_find(int W, int L, bool hl, bool gl, int res) {
-  const NrInst* tabs[NR_INST_PARTS] = {nr_insts_0, nr_insts_1, nr_insts_2, nr_insts_3};
+// dc: the DC-angle-start variant (nr_init = 2; NrInst::DC)
+#define NR_TABLES \
+  const NrInst* tabs[NR_INST_PARTS] = {nr_insts_0, nr_insts_1, nr_insts_2, nr_insts_3}; \
   const int cnt[NR_INST_PARTS] = {nr_n_insts_0, nr_n_insts_1, nr_n_insts_2, nr_n_insts_3};
+static const NrInst* nr_find(int W, int L, bool hl, bool gl, int res, int dc) {
+  NR_TABLES
   for (int p = 0; p < NR_INST_PARTS; ++p)
     for (int i = 0; i < cnt[p]; ++i) {
       const NrInst& I = tabs[p][i];
-      if (I.W == W && I.L == L && (I.HL != 0) == hl && (I.GL != 0) == gl && I.RES == res) return &I;
+      if (I.W == W && I.L == L && (I.HL != 0) == hl && (I.GL != 0) == gl && I.RES == res && (I.DC != 0) == (dc != 0)) return &I;
     }
   return nullptr;
 }
 static int nr_res_of(int rec_lds, int flat_lds) { return (rec_lds && flat_lds) ? 1 : (!rec_lds && !flat_lds) ? 2 : (rec_lds && !flat_lds) ? 3 : 0; }
 // the instantiation a handle with this geometry / residency runs: the specialised one when compiled in, else the generic body
-static const NrInst* nr_pick(int W, int L, int h_lds, int g_lds, int rec_lds, int flat_lds) {
+static const NrInst* nr_pick(int W, int L, int h_lds, int g_lds, int rec_lds, int flat_lds, int dc) {
   const bool hl = h_lds != 0, gl = hl && g_lds != 0;
   const int res = nr_res_of(rec_lds, flat_lds);
-  const NrInst* I = res ? nr_find(W, L, hl, gl, res) : nullptr;
-  return I ? I : nr_find(W, L, hl, gl, 0);
+  const NrInst* I = res ? nr_find(W, L, hl, gl, res, dc) : nullptr;
+  return I ? I : nr_find(W, L, hl, gl, 0, dc);
 }
 #ifdef MAPDN_NR_STAMPS
 int nr_debug_stamps_0(unsigned long long*, int); int nr_debug_stamps_1(unsigned long long*, int);
@@ -653,11 +656,10 @@ void launch_nr(const Dev& d, int mode, double* reward, uint8_t* term, double* in
   if (d.sparse) { launch_nr_sparse(d, mode, reward, term, info, st); return; }
   const size_t lds = nr_lds_bytes(d.nr_waves, d.nr_lanes, d.n, d.nr_cslots, d.nr_xslots, d.nr_nclist, d.nr_h_lds, d.nr_g_lds,
                                   d.nr_line_lds ? d.n_line : 0, d.nr_rec_lds ? d.nr_rows : 0, d.nr_flat_lds ? d.nr_rows : 0);
-  const NrInst* I = nr_pick(d.nr_waves, d.nr_lanes, d.nr_h_lds, d.nr_g_lds, d.nr_rec_lds, d.nr_flat_lds);
+  const NrInst* I = nr_pick(d.nr_waves, d.nr_lanes, d.nr_h_lds, d.nr_g_lds, d.nr_rec_lds, d.nr_flat_lds, d.nr_init == 2);
   if (!I) return;                                   // (mapdn_create refuses such a geometry: nr_set_lds_limit)
 #ifdef MAPDN_NR_STAMPS
-  { const NrInst* tabs[NR_INST_PARTS] = {nr_insts_0, nr_insts_1, nr_insts_2, nr_insts_3};
-    const int cnt[NR_INST_PARTS] = {nr_n_insts_0, nr_n_insts_1, nr_n_insts_2, nr_n_insts_3};
+  { NR_TABLES
     for (int p = 0; p < NR_INST_PARTS; ++p) if (I >= tabs[p] && I < tabs[p] + cnt[p]) g_last_part = p; }
 #endif
   Dev dd = d;
@@ -666,15 +668,15 @@ void launch_nr(const Dev& d, int mode, double* reward, uint8_t* term, double* in
   (void)hipLaunchKernel(I->fn, dim3(d.Bp / d.nr_lanes), dim3(64 * d.nr_waves), args, lds, st);
 }
 // raises the dynamic-LDS limit of the instantiation this geometry runs; -2: the geometry is not compiled in
-int nr_set_lds_limit(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, size_t bytes) {
-  const NrInst* I = nr_pick(waves, lanes, h_lds, g_lds, rec_lds, flat_lds);
+int nr_set_lds_limit(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, size_t bytes, int dc) {
+  const NrInst* I = nr_pick(waves, lanes, h_lds, g_lds, rec_lds, flat_lds, dc);
   if (!I) return -2;
   return hipFuncSetAttribute(I->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 0 : -1;
 }
 // 1 when some instantiation serves (waves, lanes) at all (host-side check, no device call)
 // ... and 2 when that instantiation is a specialised one (residency known at compile time: ~6 % faster than the generic body)
-int nr_geometry_compiled(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds) {
-  const NrInst* I = nr_pick(waves, lanes, h_lds, g_lds, rec_lds, flat_lds);
+int nr_geometry_compiled(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, int dc) {
+  const NrInst* I = nr_pick(waves, lanes, h_lds, g_lds, rec_lds, flat_lds, dc);
   return I ? (I->RES ? 2 : 1) : 0;
 }
 void launch_reset_begin(const Dev& d, const int64_t* start_rows, int first_try, hipStream_t st) {

@@ -99,6 +99,11 @@ struct Dev {
   // a load-only bus with several loads) | (number of sgens << 8) | min(number of loads, 2) || first load | second load | 0 | 0
   const int32_t* sgb_rec;
   const void* fi_actions; int32_t fi_dtype;      // actions [B, ns] of MAPDN_F32 / MAPDN_F64; nullptr: the injection ran as its own launch
+  // ---- DC-angle start (mapdn_env_config.nr_init = 2, runpp init="dc"; appended so that the fields above keep their kernarg offsets):
+  // k_nr_tree<..., DC = true> sweeps dc_recs ([Wt][R], plan.hpp DcRec), k_nr_sparse<L, true> assembles SpNz::bdc; both add dc_pc
+  int32_t nr_init;
+  const DcRec* dc_recs; uint32_t dc_recs_bytes;
+  const double* dc_pc;                           // [n] by position: Pbus - Re(Sbus) (plan.hpp Plan::dc_pc)
 };
 
 void launch_inject(const Dev& d, int mode, const void* actions, int dtype, const double* pl, const double* ql,
@@ -108,8 +113,9 @@ void launch_inject_sgen(const Dev& d, int mode, const void* actions, int dtype, 
 // fused_actions != nullptr (MODE_STEP only): k_nr_tree's prologue performs the PV-bus injection itself (no k_inject_sgen launch)
 void launch_nr(const Dev& d, int mode, double* reward, uint8_t* term, double* info, hipStream_t st,
                const void* fused_actions = nullptr, int fused_dtype = 0);
-int nr_set_lds_limit(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, size_t bytes);   // -2: geometry not instantiated
-int nr_geometry_compiled(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds);
+// dc: the DC-angle-start instantiations (mapdn_env_config.nr_init = 2)
+int nr_set_lds_limit(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, size_t bytes, int dc = 0);   // -2: geometry not instantiated
+int nr_geometry_compiled(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, int dc = 0);
 // dynamic LDS of k_nr_tree (W waves, L envs per workgroup => Wt = W*64/L workers), in pair rows of L x 16 bytes:
 // node voltages (n+2: nodes, slack, trash), h (n+2) and G (2(n+2)) when resident, contribution slots (4 rows each),
 // x slots (1 row each); then verdict bytes, step-size partials (64*W doubles), overflow child list (padded to

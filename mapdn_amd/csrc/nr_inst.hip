@@ -1,5 +1,5 @@
 // nr_inst.hip — one PART of the k_nr_tree instantiations (nr_inst_list.hpp); compiled once per part, in parallel:
-//   hipcc -c -DNR_INST_PART=<p> nr_inst.hip -o nr_inst_<p>.o
+//   hipcc -c -DNR_INST_PART=<p> nr_inst.hip -o nr_inst_<p>.o   (p = 0..3)
 #include "nr_tree.hpp"
 #include "nr_inst_list.hpp"
 
@@ -11,9 +11,10 @@ namespace mapdn {
 
 #define NR_CAT_(a, b) a##b
 #define NR_CAT(a, b) NR_CAT_(a, b)
-#define NR_ENTRY(w, l, hl, gl, res) {w, l, hl, gl, res, (const void*)k_nr_tree<w, l, hl, gl, res>},
+#define NR_ENTRY(w, l, hl, gl, res) {w, l, hl, gl, res, (const void*)k_nr_tree<w, l, hl, gl, res>, 0},
+#define NR_ENTRY_DC(w, l, hl, gl, res) {w, l, hl, gl, res, (const void*)k_nr_tree<w, l, hl, gl, res, true>, 1},
 
-extern const NrInst NR_CAT(nr_insts_, NR_INST_PART)[] = { NR_CAT(NR_INSTS_, NR_INST_PART)(NR_ENTRY) };
+extern const NrInst NR_CAT(nr_insts_, NR_INST_PART)[] = { NR_CAT(NR_INSTS_, NR_INST_PART)(NR_ENTRY) NR_CAT(NR_INSTS_DC_, NR_INST_PART)(NR_ENTRY_DC) };
 extern const int NR_CAT(nr_n_insts_, NR_INST_PART) = (int)(sizeof(NR_CAT(nr_insts_, NR_INST_PART)) / sizeof(NrInst));
 
 #ifdef MAPDN_NR_STAMPS

@@ -28,8 +28,22 @@
   X(2, 4, true, false, 0) X(2, 4, true, true, 0) X(2, 4, false, false, 0) \
   X(1, 4, true, false, 0) X(1, 4, true, true, 0)
 
+// the DC-angle start (k_nr_tree<..., DC = true>, mapdn_env_config.nr_init = 2), spread over the same four parts: the specialised
+// geometries the chooser returns for the three feeder classes (33 / 141 / 322 buses), and the generic body of every layout the chooser
+// can settle on for its candidate pairs (1, 16) (2, 16) (4, 16) (4, 8) — fat with G in LDS, fat, lean.  Other pairs are refused ("not
+// compiled in").
+#define NR_INSTS_DC_0(X) \
+  X(1, 16, true, true, 1) X(4, 16, true, false, 1) X(4, 16, true, false, 0) X(4, 16, true, true, 0) X(4, 16, false, false, 0) \
+  X(1, 16, true, true, 0)
+#define NR_INSTS_DC_1(X) \
+  X(2, 16, false, false, 2) X(2, 16, true, true, 0) X(2, 16, true, false, 0) X(2, 16, false, false, 0) X(1, 16, true, false, 0) \
+  X(1, 16, false, false, 0)
+#define NR_INSTS_DC_2(X) \
+  X(4, 8, true, false, 3) X(4, 16, false, false, 2) X(4, 8, true, false, 0) X(4, 8, true, true, 0) X(4, 8, false, false, 0)
+#define NR_INSTS_DC_3(X)
+
 namespace mapdn {
-struct NrInst { int W, L, HL, GL, RES; const void* fn; };
+struct NrInst { int W, L, HL, GL, RES; const void* fn; int DC; };   // DC: the DC-angle-start variant
 enum { NR_INST_PARTS = 4 };
 extern const NrInst nr_insts_0[]; extern const int nr_n_insts_0;
 extern const NrInst nr_insts_1[]; extern const int nr_n_insts_1;

@@ -139,7 +139,10 @@ struct BwdF { d2 h, g01, g23; };                        // factors of one step w
 // HL / GL: the h / G factors live in LDS (when they fit) instead of global scratch.  RES: 1 = step records and flat-start
 // constants are LDS-resident (compile-time: the "fat" geometry), 2 = neither is (the "lean" one), 3 = the records are, the
 // flat-start constants are not (the 322-bus feeder: W = 4, L = 8), 0 = per handle (d.nr_*_lds)
-template <int W, int L, bool HL, bool GL, int RES = 0>
+// DC: runpp init="dc" (mapdn_env_config.nr_init = 2) — every solve starts from the angles of a DC power flow (two sweeps over the
+// schedule in the prologue) and its first Newton iteration forms the Jacobian from that start like any later one; the flat-start
+// constants are not read.  DC = false compiles to the flat-start kernel of before.
+template <int W, int L, bool HL, bool GL, int RES = 0, bool DC = false>
 __global__ void __launch_bounds__(64 * W)
 k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ terminated, double* __restrict__ info) {
   extern __shared__ d2 lds2[];
@@ -359,6 +362,93 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
   const double bk_sum = d.sum_rewards[e];
   __syncthreads();
   STAMP(2);
+  if constexpr (DC) {
+    // ---- DC-angle start: pandapower run_dc_pf (oracle/pp_restated.py dc_angles) on the elimination tree.  Bbus[pvpq, pvpq] is a
+    // topology constant factorised on the host (fill-free scalar LU, plan.cpp); per env: Pbus = Re(Sbus) + dc_pc, the forward
+    // substitution leaf -> root over the schedule's rows (c_k = B_pk h_k goes to the parent, the children summed in the canonical
+    // order of mm_child: the same bits in every geometry), the back substitution root -> leaf, then V0 = vroot e^{j theta}.
+    // Staging in sV (free until the Newton loop): (P_k, -) -> (c_k, h_k) -> (-, theta_k); the slack entry holds theta = 0.
+    if (!__all(!act)) {                            // (uniform over the workgroup: every wave holds the same envs)
+      {                                            // Pbus of this worker's nodes: loads of a batch issued back to back
+        constexpr int NQ = 4;
+        for (unsigned kb = t; kb < n; kb += (unsigned)NQ * Wt) {
+          d2 sb[NQ]; double pc[NQ];
+#pragma unroll
+          for (int i = 0; i < NQ; ++i) {
+            const unsigned kx = min(kb + (unsigned)i * Wt, n - 1u);
+            sb[i] = bld2(rs, voS + kx * pb, 0u); pc[i] = d.dc_pc[kx];
+          }
+#pragma unroll
+          for (int i = 0; i < NQ; ++i) {
+            const unsigned kx = kb + (unsigned)i * Wt;
+            if (kx < n) sV[(size_t)kx * L] = d2{sb[i].x + pc[i], 0.0};
+          }
+        }
+      }
+      if (W > 1) lds_barrier();
+      const __amdgpu_buffer_rsrc_t rsD = __builtin_amdgcn_make_buffer_rsrc(const_cast<DcRec*>(d.dc_recs), 0, d.dc_recs_bytes, 0x00020000);
+      constexpr unsigned DB = (unsigned)sizeof(DcRec);
+      const unsigned voD = t * (unsigned)R * DB;
+      struct DcR { u32x4 ix; d2 ib, gp; };         // (kp, nch, c01, c2), (1/d, B_pk), (B_kp/d, -)
+      auto dc_load = [&](int row, DcR& o) {
+        const unsigned st = __builtin_amdgcn_readfirstlane((unsigned)row * DB);
+        o.ix = bldu4(rsD, voD, st); o.ib = bld2(rsD, voD + 16u, st); o.gp = bld2(rsD, voD + 32u, st);
+      };
+      DcR q[4];                                    // records three rows ahead (static ring)
+      // forward substitution, leaf -> root
+      dc_load(0, q[0]); dc_load(min(1, R - 1), q[1]); dc_load(min(2, R - 1), q[2]);
+      for (int r0 = 0; r0 < R; r0 += 4) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int r = r0 + u;
+          if (r < R) {                             // (uniform)
+            const DcR c = q[u];
+            dc_load(min(r + 3, R - 1), q[(u + 3) % 4]);
+            const unsigned k = c.ix.x & 0xffffu, nch = c.ix.y;
+            const double own = sV[(size_t)k * L].x;
+            const double a0 = sV[(size_t)(c.ix.z & 0xffffu) * L].x, a1 = sV[(size_t)(c.ix.z >> 16) * L].x, a2 = sV[(size_t)(c.ix.w & 0xffffu) * L].x;
+            double y = own;
+            if (nch > 0u) y -= a0;
+            if (nch > 1u) y -= a1;
+            if (nch > 2u) y -= a2;
+            if (__any(nch > 3u)) {                 // rare: junctions with more than three children
+              const unsigned c_lo = c.ix.w >> 16;
+#pragma unroll 1
+              for (unsigned j = 3; j < nch; ++j) y -= sV[(size_t)d.mm_child[c_lo + j] * L].x;
+            }
+            const double h = y * c.ib.x;
+            sV[(size_t)k * L] = d2{c.ib.y * h, h};  // (idle steps: the trash node)
+            if (W > 1) lds_barrier();
+          }
+        }
+      }
+      // back substitution, root -> leaf: theta_k = h_k - g_k theta_parent (elimination roots read the slack's 0)
+      dc_load(R - 1, q[0]); dc_load(max(R - 2, 0), q[1]); dc_load(max(R - 3, 0), q[2]);
+      for (int r0 = R - 1; r0 >= 0; r0 -= 4) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int r = r0 - u;
+          if (r >= 0) {                            // (uniform)
+            const DcR c = q[u];
+            dc_load(max(r - 3, 0), q[(u + 3) % 4]);
+            const unsigned k = c.ix.x & 0xffffu, p = c.ix.x >> 16;
+            const double hk = sV[(size_t)k * L].y, tp = sV[(size_t)p * L].y;
+            sV[(size_t)k * L] = d2{0.0, fma(-c.gp.x, tp, hk)};
+            if (W > 1) lds_barrier();
+          }
+        }
+      }
+      // V0 = vroot e^{j theta} (runpp: magnitudes flat); the trash node back to the flat value
+      for (unsigned k = t; k < n + 2u; k += Wt) {
+        if (k == n) continue;
+        double sn_, cs_;
+        sincos(sV[(size_t)k * L].y, &sn_, &cs_);
+        sV[(size_t)k * L] = k < n ? d2{vroot * cs_, vroot * sn_} : d2{vroot, 0.0};
+      }
+      if (W > 1) lds_barrier();
+    }
+    STAMP(3);
+  }
   bool done = !act;
   bool conv = false;
   int it = 0;
@@ -962,7 +1052,7 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
   // first run mismatch-only; if some env then fails the test after all, the sweep is redone in full (its
   // factors are needed for another iteration).  All three flags are uniform over the workgroup: every
   // wave holds the same envs and derives them from the same per-env values.
-  bool first = true, light = false;
+  bool first = !DC, light = false;               // (the DC start has no host-made first iteration)
   while (!nothing_to_solve) {
     // ------------------------------------------------------------------ forward sweep
     allok = true; fmx = 0.0;

@@ -94,6 +94,7 @@ int build_plan(const mapdn_netspec& net_o, const mapdn_env_config& cfg, Plan& P,
   E.ext_grid_bus = eid[net_o.ext_grid_bus]; E.bus_alias = nullptr;
   int rc = build_plan_nodes(E, net_o, cfg, P, err);
   if (rc) return rc;
+  P.dc_ok = false;                                // the DC-angle start is not defined on fused buses (as oracle/pp_restated.py refuses it)
   // ---- the reporting layer
   P.nbo = nbo;
   P.pos_of_obus.resize(nbo);
@@ -298,6 +299,54 @@ static int build_plan_nodes(const mapdn_netspec& net, const mapdn_netspec& net_o
     P.gy_ptr.push_back((int32_t)P.gy_col.size());
   }
 
+  // ---- DC-angle start (runpp init="dc"): pandapower pf/run_dc_pf.py + pypower makeBdc, as restated in oracle/pp_restated.py dc_angles:
+  // b = 1 / x / |tap| per in-service branch, Bbus = (Cf - Ct)' diag(b) (Cf - Ct), Pbusinj = (Cf - Ct)' (b (-shift)),
+  // Pbus = Re(Sbus) - Pbusinj - GS / sn, Va[pvpq] = Bbus[pvpq, pvpq]^-1 Pbus[pvpq], Va[slack] = 0.  Only Re(Sbus) changes per solve.
+  {
+    std::vector<double> B((size_t)nb * nb, 0.0), pinj(nb, 0.0);
+    auto add = [&](int f, int t, double x, double ratio, double shift) {
+      const double b = 1.0 / x / ratio;
+      B[(size_t)f * nb + f] += b; B[(size_t)t * nb + t] += b; B[(size_t)f * nb + t] -= b; B[(size_t)t * nb + f] -= b;
+      pinj[f] += b * -shift; pinj[t] -= b * -shift;
+    };
+    for (int l = 0; l < net.n_line; ++l) {
+      if (!net.line_in_service[l]) continue;
+      const int f = net.line_from_bus[l];
+      const double base_r = net.bus_vn_kv[f] * net.bus_vn_kv[f] / net.sn_mva;
+      add(f, net.line_to_bus[l], net.line_x_ohm_per_km[l] * net.line_length_km[l] / base_r / (double)net.line_parallel[l], 1.0, 0.0);
+    }
+    for (int k = 0; k < net.n_branch_pu; ++k) {
+      const cplx tap = std::polar(net.br_ratio[k] == 0.0 ? 1.0 : net.br_ratio[k], net.br_shift_deg[k] * M_PI / 180.0);
+      add(net.br_from_bus[k], net.br_to_bus[k], net.br_x_pu[k], std::abs(tap), std::arg(tap));
+    }
+    auto Bp = [&](int i, int j) { return B[(size_t)P.bus_of_pos[i] * nb + P.bus_of_pos[j]]; };   // by position
+    bool ok = true;
+    P.dc_pc.assign(P.n, 0.0);
+    for (int k = 0; k < P.n; ++k) {
+      const int bus = P.bus_of_pos[k];
+      P.dc_pc[k] = -pinj[bus] - sh_p_bus[bus] / net.sn_mva;
+      ok = ok && std::isfinite(P.dc_pc[k]);
+    }
+    P.gy_dc.assign(P.gy_col.size(), 0.0);
+    for (int k = 0; k < P.n; ++k)
+      for (int q = P.gy_ptr[k]; q < P.gy_ptr[k + 1]; ++q) { P.gy_dc[q] = Bp(k, P.gy_col[q]); ok = ok && std::isfinite(P.gy_dc[q]); }
+    if (P.radial) {                              // the scalar LU on the elimination forest (children before parents: no fill)
+      std::vector<double> dd(P.n);
+      for (int k = 0; k < P.n; ++k) dd[k] = Bp(k, k);
+      P.dc_id.assign(P.n, 0.0); P.dc_bpk.assign(P.n, 0.0); P.dc_g.assign(P.n, 0.0);
+      for (int k = 0; k < P.n; ++k) {
+        ok = ok && std::isfinite(dd[k]) && dd[k] > 0.0;
+        P.dc_id[k] = 1.0 / dd[k];
+        const int p = P.par[k];
+        if (p < P.n) {
+          P.dc_bpk[k] = Bp(p, k); P.dc_g[k] = Bp(k, p) * P.dc_id[k];
+          dd[p] -= P.dc_bpk[k] * P.dc_g[k];
+        }
+      }
+    }
+    P.dc_ok = ok;
+  }
+
   // ---- res_line flows ---------------------------------------------------------------------------
   P.lines.resize(net.n_line);
   for (int l = 0; l < net.n_line; ++l) {
@@ -428,7 +477,7 @@ void sparse_program(const Plan& P, int S, SparseProg& G) {
   G.max_nnz = 1;
   for (int i = 0; i < n; ++i) G.max_nnz = std::max<int32_t>(G.max_nnz, P.gy_ptr[i + 1] - P.gy_ptr[i]);
   G.rows.assign((size_t)S * G.rows_per_sub, SpRow{(uint32_t)(n + 1), 0u, 0u, 0u});
-  G.nz.assign((size_t)S * G.rows_per_sub * G.max_nnz, SpNz{(uint32_t)(n + 1), -1, {0.0, 0.0}, {0u, 0u}});
+  G.nz.assign((size_t)S * G.rows_per_sub * G.max_nnz, SpNz{(uint32_t)(n + 1), -1, {0.0, 0.0}, 0.0});
   for (int i = 0; i < n; ++i) {
     const size_t r = (size_t)(i % S) * G.rows_per_sub + i / S;
     G.rows[r] = SpRow{(uint32_t)i, (uint32_t)(P.gy_ptr[i + 1] - P.gy_ptr[i]), (uint32_t)i, 1u};
@@ -437,6 +486,7 @@ void sparse_program(const Plan& P, int S, SparseProg& G) {
       SpNz& z = G.nz[r * G.max_nnz + (q - P.gy_ptr[i])];
       z.col = (uint32_t)j; z.y[0] = P.gy_val[2 * q]; z.y[1] = P.gy_val[2 * q + 1];
       z.slot = (j < n && j != i) ? Y.slot.at({i, j}) : -1;
+      if (!P.gy_dc.empty()) z.bdc = P.gy_dc[q];
     }
   }
   // ---- operations in elimination order, then list scheduling into phases of <= S independent ops
@@ -697,6 +747,22 @@ void build_schedule(const Plan& P, int W, Schedule& S, int min_cslots, int Sw, i
         if (k >= 0) std::copy_n(&node[(size_t)k * FLAT_N], (size_t)FLAT_N, &S.flat[((size_t)w * R + r) * FLAT_N]);
       }
   }
+  // ---- DC-angle start: one record per (worker, row), children in the canonical order of mm_child (independent of W)
+  S.dc_recs.assign((size_t)W * R, DcRec{});
+  for (int w = 0; w < W; ++w)
+    for (int r = 0; r < R; ++r) {
+      DcRec& D = S.dc_recs[(size_t)w * R + r];
+      const int k = rows[r][w];
+      const uint32_t trash = (uint32_t)n + 1u;
+      if (k < 0) { D.kp = trash | ((uint32_t)n << 16); D.c01 = trash | (trash << 16); D.c2 = trash; continue; }
+      const int c_lo = S.mm_ptr[k], nch = S.mm_ptr[k + 1] - c_lo;
+      auto child = [&](int q) { return q < nch ? (uint32_t)S.mm_child[c_lo + q] : trash; };
+      D.kp = (uint32_t)k | ((uint32_t)P.par[k] << 16);
+      D.nch = (uint32_t)nch;
+      D.c01 = child(0) | (child(1) << 16);
+      D.c2 = child(2) | ((uint32_t)c_lo << 16);
+      if (P.dc_ok && !P.dc_id.empty()) { D.id = P.dc_id[k]; D.bpk = P.dc_bpk[k]; D.g = P.dc_g[k]; }
+    }
 }
 
 }  // namespace mapdn

@@ -48,6 +48,19 @@ struct StepRec {
 };
 static_assert(sizeof(StepRec) == 80, "StepRec must be 80 bytes (5 x dwordx4)");
 
+// One (worker, row) step of the DC-angle start on the elimination tree (runpp init="dc"): the scalar LU of Bbus[pvpq, pvpq] has no
+// fill on a radial feeder and is factorised on the host (Plan::dc_id / dc_bpk / dc_g); per env there remain the forward substitution
+// y_k = P_k - sum of the children's c, h_k = y_k / d_k, c_k = B_pk h_k (leaf -> root) and the back substitution
+// theta_k = h_k - (B_kp / d_k) theta_parent (root -> leaf, theta_slack = 0).  48 bytes (3 x dwordx4), addressed by (worker, row).
+//   kp  : node | parent << 16   (idle step: the trash node n + 1, parent = the slack n)
+//   nch : number of children;  c01 : child 0 | child 1 << 16;  c2 : child 2 | start of the child list (Schedule::mm_child) << 16
+//   (absent children: the trash node; children 3.. of a junction from mm_child, in the canonical order of the sweeps)
+struct DcRec {
+  uint32_t kp, nch, c01, c2;
+  double id, bpk, g, pad;          // 1 / d_k, B_parent,k, B_k,parent / d_k (0 for elimination roots and idle steps)
+};
+static_assert(sizeof(DcRec) == 48, "DcRec must be 48 bytes (3 x dwordx4)");
+
 // schedule-step flags
 enum : uint32_t {
   S_PARENT_ROOT = 1u,    // elimination root (no parent): no off-diagonal Jacobian block
@@ -89,6 +102,8 @@ struct Schedule {
   // junction come from mm_child.
   int32_t mm_np = 0;                       // records per worker
   std::vector<StepRec> mm_recs;            // [W][mm_np]
+  // DC-angle start (k_nr_tree's DC variant): one record per (worker, row) of the same schedule, see DcRec
+  std::vector<DcRec> dc_recs;               // [W][R]
 };
 // per-step layout of Schedule::flat
 enum { FL_SR = 0, FL_SI, FL_I0, FL_I1, FL_I2, FL_I3, FL_APR, FL_API, FL_G0, FL_G1, FL_G2, FL_G3, FLAT_N };
@@ -128,6 +143,13 @@ struct Plan {
   std::vector<int32_t> slack_group;             // indices into fused_obus of the members of the slack's group (kind 2 needs their sum)
   std::vector<int32_t> alias_pos;               // position of the node of every NON-representative bus (reward statistics count it again)
 
+  // ---- DC-angle start (runpp init="dc": pandapower run_dc_pf / pypower makeBdc + dcpf), topology constants by position.  Not built
+  // on a net with fused buses (dc_ok false).  Bbus = (Cf - Ct)' diag(1 / (x |tap|)) (Cf - Ct), Pbus = Re(Sbus) - Pbusinj - GS / sn:
+  bool dc_ok = false;
+  std::vector<double> dc_pc;                    // [n] -Pbusinj - GS / sn: what Pbus adds to Re(Sbus)
+  std::vector<double> dc_id, dc_bpk, dc_g;      // [n] radial: 1 / d_k, B_parent,k, B_k,parent / d_k of the fill-free scalar LU of Bbus
+  std::vector<double> gy_dc;                    // aligned with gy_col: Bbus entries (the general sparse solver assembles them)
+
   std::vector<LineFlow> lines;                  // [n_line]
   // element -> bus CSR by position (0..nb-1, root last)
   std::vector<int32_t> load_ptr, load_idx, sgen_ptr, sgen_idx;
@@ -150,7 +172,8 @@ struct Plan {
 // block array as [b | 0] blocks, so substitution uses the same three operations.  What pandapower leaves to SuperLU
 // at run time (pypower newtonpf.py: dx = -spsolve(J, F)) is thus decided here, off the hot path.
 struct SpOp { uint32_t type, c, a, b; };                                  // type: 0 NOP, 1 INV, 2 MUL, 3 UPD; block slots
-struct SpNz { uint32_t col; int32_t slot; double y[2]; uint32_t pad[2]; };   // Ybus entry of a row: column position (n = slack), block slot (-1: none), Y
+struct SpNz { uint32_t col; int32_t slot; double y[2]; double bdc; };   // Ybus entry of a row: column position (n = slack), block slot (-1: none), Y;
+                                                                    // bdc: the Bbus entry (the DC-angle start assembles it instead of the Jacobian)
 struct SpRow { uint32_t node, nnz, sb, live; };                           // assembly row: position, entries, Sbus entry, 1 if a real node
 static_assert(sizeof(SpOp) == 16 && sizeof(SpNz) == 32 && sizeof(SpRow) == 16, "sparse program records");
 struct SparseProg {

@@ -22,7 +22,9 @@
 
 namespace mapdn {
 
-template <int L>
+// DC: runpp init="dc" (mapdn_env_config.nr_init = 2) — before the first iteration the same program solves Bbus theta = Pbus per env
+// (the DC power flow of pandapower run_dc_pf) and the solve starts from V0 = vroot e^{j theta}; DC = false: the flat start.
+template <int L, bool DC = false>
 __global__ void __launch_bounds__(64)
 k_nr_sparse(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ terminated, double* __restrict__ info) {
   extern __shared__ d2 lds2[];
@@ -49,6 +51,73 @@ k_nr_sparse(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ 
   const bool nothing_to_solve = __all(!act);
   bool done = !act, conv = false;
   int it = 0;
+  // numeric factorisation + forward / backward substitution: the host-compiled program (plan.cpp::sparse_program)
+  auto run_program = [&]() {
+    constexpr int PF = 8;                          // operation records run PF phases ahead (constant table in L2)
+    u32x4 oq[PF];
+#pragma unroll
+    for (int u = 0; u < PF; ++u) oq[u] = __builtin_amdgcn_raw_buffer_load_b128(rsO, voO, __builtin_amdgcn_readfirstlane((unsigned)min(u, NPH - 1) * S * 16u), 0);
+    for (int p0 = 0; p0 < NPH; p0 += PF) {
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        const int p = p0 + u;
+        if (p < NPH) {                           // (uniform)
+        const u32x4 op = oq[u];
+        oq[u] = __builtin_amdgcn_raw_buffer_load_b128(rsO, voO, __builtin_amdgcn_readfirstlane((unsigned)min(p + PF, NPH - 1) * S * 16u), 0);
+        const unsigned type = op.x & 255u;
+        const unsigned hint = __builtin_amdgcn_readfirstlane(op.x);     // bits 8 / 9: the phase holds an INV / an UPD (wave-uniform)
+        const d2* A = blk(op.z); const d2* B = blk(op.w); d2* C = blk(op.y);
+        const d2 a0 = A[0], a1 = A[1], b0 = B[0], b1 = B[1];
+        d2 c0 = d2{0.0, 0.0}, c1 = d2{0.0, 0.0};
+        if (hint & 512u) { c0 = C[0]; c1 = C[1]; }
+        const double p00 = a0.x * b0.x + a0.y * b1.x, p01 = a0.x * b0.y + a0.y * b1.y;
+        const double p10 = a1.x * b0.x + a1.y * b1.x, p11 = a1.x * b0.y + a1.y * b1.y;
+        d2 n0, n1;
+        if (type == 2u) { n0 = d2{p00, p01}; n1 = d2{p10, p11}; }
+        else { n0 = d2{c0.x - p00, c0.y - p01}; n1 = d2{c1.x - p10, c1.y - p11}; }
+        if (hint & 256u) {
+          const double idet = rcp_nr(a0.x * a1.y - a0.y * a1.x);
+          if (type == 1u) { n0 = d2{a1.y * idet, -a0.y * idet}; n1 = d2{-a1.x * idet, a0.x * idet}; }
+        }
+        if (type != 0u && !done) { C[0] = n0; C[1] = n1; }
+        }
+      }
+    }
+  };
+  if constexpr (DC) {
+    // ---- DC-angle start (oracle/pp_restated.py dc_angles): blocks [[B_ij, 0], [0, 0]] off the diagonal, [[B_ii, 0], [0, 1]] on it and
+    // the right-hand side [Pbus_i | 0], Pbus = Re(Sbus) + dc_pc; the program's solution is [theta_i, 0]
+    if (!nothing_to_solve) {
+      for (unsigned q = s; q < (unsigned)d.sp_fill; q += S) {
+        d2* f = blk((unsigned)d.sp_fill_slots[q]);
+        f[0] = d2{0.0, 0.0}; f[1] = d2{0.0, 0.0};
+      }
+      for (int r = 0; r < RPS; ++r) {
+        const unsigned i = (unsigned)r * S + s;
+        if (i >= (unsigned)n) continue;
+        const SpNz* z = d.sp_nz + ((size_t)s * RPS + r) * MNZ;
+        double bii = 0.0;
+        for (int q = 0; q < MNZ; ++q) {
+          const SpNz zq = z[q];
+          if (zq.col == i) bii = zq.bdc;
+          else if (zq.slot >= 0) { d2* o = blk((unsigned)zq.slot); o[0] = d2{zq.bdc, 0.0}; o[1] = d2{0.0, 0.0}; }
+        }
+        d2* dg = blk(i);
+        dg[0] = d2{bii, 0.0}; dg[1] = d2{0.0, 1.0};
+        d2* rh = blk((unsigned)n + i);
+        rh[0] = d2{gsb[(size_t)i * d.Bp + e].x + d.dc_pc[i], 0.0}; rh[1] = d2{0.0, 0.0};
+      }
+      run_program();
+      for (int r = 0; r < RPS; ++r) {
+        const unsigned i = (unsigned)r * S + s;
+        if (i < (unsigned)n && !done) {
+          double sn, cs;
+          sincos(blk((unsigned)n + i)[0].x, &sn, &cs);
+          sV[(size_t)i * L] = d2{vroot * cs, vroot * sn};
+        }
+      }
+    }
+  }
   while (!nothing_to_solve) {
     // ---- mismatch F = V conj(Ybus V) - Sbus and the Jacobian blocks, row by row (sub-lane s owns rows s, s + S, ...):
     //      dS_i/dtheta_j = -j A_ij, dS_i/dln|V_j| = A_ij (j != i); dS_i/dtheta_i = j (S_i - A_ii), dS_i/dln|V_i| = S_i + A_ii
@@ -126,39 +195,7 @@ k_nr_sparse(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ 
       if (conv || it == d.max_it) done = true;
     }
     if (__all(done)) break;
-    // ---- numeric factorisation + forward / backward substitution: the host-compiled program (plan.cpp::sparse_program)
-    {
-      constexpr int PF = 8;                          // operation records run PF phases ahead (constant table in L2)
-      u32x4 oq[PF];
-#pragma unroll
-      for (int u = 0; u < PF; ++u) oq[u] = __builtin_amdgcn_raw_buffer_load_b128(rsO, voO, __builtin_amdgcn_readfirstlane((unsigned)min(u, NPH - 1) * S * 16u), 0);
-      for (int p0 = 0; p0 < NPH; p0 += PF) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-          const int p = p0 + u;
-          if (p < NPH) {                           // (uniform)
-          const u32x4 op = oq[u];
-          oq[u] = __builtin_amdgcn_raw_buffer_load_b128(rsO, voO, __builtin_amdgcn_readfirstlane((unsigned)min(p + PF, NPH - 1) * S * 16u), 0);
-          const unsigned type = op.x & 255u;
-          const unsigned hint = __builtin_amdgcn_readfirstlane(op.x);     // bits 8 / 9: the phase holds an INV / an UPD (wave-uniform)
-          const d2* A = blk(op.z); const d2* B = blk(op.w); d2* C = blk(op.y);
-          const d2 a0 = A[0], a1 = A[1], b0 = B[0], b1 = B[1];
-          d2 c0 = d2{0.0, 0.0}, c1 = d2{0.0, 0.0};
-          if (hint & 512u) { c0 = C[0]; c1 = C[1]; }
-          const double p00 = a0.x * b0.x + a0.y * b1.x, p01 = a0.x * b0.y + a0.y * b1.y;
-          const double p10 = a1.x * b0.x + a1.y * b1.x, p11 = a1.x * b0.y + a1.y * b1.y;
-          d2 n0, n1;
-          if (type == 2u) { n0 = d2{p00, p01}; n1 = d2{p10, p11}; }
-          else { n0 = d2{c0.x - p00, c0.y - p01}; n1 = d2{c1.x - p10, c1.y - p11}; }
-          if (hint & 256u) {
-            const double idet = rcp_nr(a0.x * a1.y - a0.y * a1.x);
-            if (type == 1u) { n0 = d2{a1.y * idet, -a0.y * idet}; n1 = d2{-a1.x * idet, a0.x * idet}; }
-          }
-          if (type != 0u && !done) { C[0] = n0; C[1] = n1; }
-          }
-        }
-      }
-    }
+    run_program();
     // ---- newtonpf update: Va -= z0, Vm -= |V| z1, V = Vm e^{jVa}   =>   V <- V (1 - z1) e^{-j z0}
     for (int r = 0; r < RPS; ++r) {
       const unsigned i = (unsigned)r * S + s;
@@ -184,7 +221,8 @@ size_t nr_sparse_lds_bytes(int n, int n_blocks, int L) {
 
 #define SP_FOR_EACH(X) X(16) X(8) X(4) X(2)
 int nr_sparse_prepare(int L) {
-#define X(l) if (L == l) return hipFuncSetAttribute((const void*)k_nr_sparse<l>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess ? 0 : -1;
+#define X(l) if (L == l) return (hipFuncSetAttribute((const void*)k_nr_sparse<l>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess && \
+                                hipFuncSetAttribute((const void*)k_nr_sparse<l, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess) ? 0 : -1;
   SP_FOR_EACH(X)
 #undef X
   return -2;
@@ -192,7 +230,10 @@ int nr_sparse_prepare(int L) {
 
 void launch_nr_sparse(const Dev& d, int mode, double* reward, uint8_t* term, double* info, hipStream_t st) {
   const size_t lds = nr_sparse_lds_bytes(d.n, d.sp_blocks, d.sp_lanes);
-#define X(l) if (d.sp_lanes == l) { hipLaunchKernelGGL(k_nr_sparse<l>, dim3(d.Bp / l), dim3(64), lds, st, d, mode, reward, term, info); return; }
+#define X(l) if (d.sp_lanes == l) { \
+    if (d.nr_init == 2) hipLaunchKernelGGL((k_nr_sparse<l, true>), dim3(d.Bp / l), dim3(64), lds, st, d, mode, reward, term, info); \
+    else hipLaunchKernelGGL((k_nr_sparse<l, false>), dim3(d.Bp / l), dim3(64), lds, st, d, mode, reward, term, info); \
+    return; }
   SP_FOR_EACH(X)
 #undef X
 }

@@ -150,11 +150,14 @@ def from_pandapower(net, hv_init: str = "refuse") -> NetSpec:
     shunts (step, in_service), one ext_grid, closed bus-bus switches (bus fusion -> NetSpec.bus_alias).  Refused loudly, never guessed: voltage-dependent loads
     (const_z_percent / const_i_percent: the constant-Z share would be a time-varying shunt), generators, three-winding transformers, impedances, wards, dc lines, storage,
     closed bus-bus switches with z_ohm > 0 (pandapower models them as impedance branches, not as fused buses), fused buses of different vn_kv, and
-    — unless hv_init="flat" — nets with a line at a bus above 70 kV: runpp's defaults then turn calculate_voltage_angles on AND start the
-    Newton iteration from a DC power flow's angles (init="auto" -> "dc"), while every solver here starts flat; the converged answer is the
-    same, the iteration count (and with it the 10-iteration verdict of voltage_control_env.py:188-196) need not be."""
-    if hv_init not in ("refuse", "flat"):
-        raise ValueError("hv_init must be 'refuse' or 'flat'")
+    — by default (hv_init="refuse") — nets with a line at a bus above 70 kV: runpp's defaults then turn calculate_voltage_angles on AND start
+    the Newton iteration from a DC power flow's angles (init="auto" -> "dc").
+    hv_init="auto" does what runpp's defaults do: the DC-angle start (NetSpec.va_init = "dc", run by the solvers as mapdn_env_config.nr_init
+    = 2) exactly when a line touches a bus above 70 kV, the flat start otherwise.  hv_init="flat" converts such a net with the flat start
+    anyway: the converged answer is the same where both converge, the iteration count (and with it the 10-iteration verdict of
+    voltage_control_env.py:188-196) need not be, and with a vector-group shift such as 150 degrees the flat start does not converge."""
+    if hv_init not in ("refuse", "flat", "auto"):
+        raise ValueError("hv_init must be 'refuse', 'flat' or 'auto'")
     def table(name):
         t = net[name] if name in net else None
         return t if t is not None and len(t) else None
@@ -271,8 +274,10 @@ def from_pandapower(net, hv_init: str = "refuse") -> NetSpec:
         raise NotImplementedError("a line touches a bus above 70 kV: pp.runpp's defaults (voltage_control_env.py:557) switch calculate_voltage_angles on "
                                   "and initialise the voltage angles from a DC power flow (init='auto' -> 'dc'); the solvers here start flat, so the "
                                   "Newton iteration count — and the 10-iteration non-convergence verdict — could differ from pandapower's.  Pass "
-                                  "hv_init='flat' to convert anyway (transformer phase shifts applied; same converged voltages where the flat start "
+                                  "hv_init='auto' to start from the DC power flow as runpp does (NetSpec.va_init = 'dc'), or hv_init='flat' to convert "
+                                  "with the flat start anyway (transformer phase shifts applied; same converged voltages where the flat start "
                                   "converges — with a vector-group shift such as 150 degrees it does not, see tests/test_data_ingestion.py)")
+    kw["va_init"] = "dc" if (calc_va and hv_init == "auto") else "flat"
     if trafo is not None:
         t = trafo.sort_index().copy()
         t["in_service"] = trafo_on
@@ -455,9 +460,9 @@ def read_pandapower_pickle(path: str) -> InertNet:
 
 def load_scenario(data_path: str, pv_scale: float = 1.0, demand_scale: float = 1.0, hv_init: str = None):
     """(NetSpec, Profiles) of a scenario directory: netspec.npz or the reference's model.p (read as data by the restricted
-    unpickler above — pandapower is not needed) + the three CSVs.  hv_init ("refuse" | "flat", see from_pandapower; default: the
-    MAPDN_HV_INIT environment variable, else "refuse") decides what happens to a model.p with a line at a bus above 70 kV — runpp
-    would start such a net from a DC power flow's angles, which the HIP solver does not do."""
+    unpickler above — pandapower is not needed) + the three CSVs.  hv_init ("refuse" | "flat" | "auto", see from_pandapower; default:
+    the MAPDN_HV_INIT environment variable, else "refuse") decides what happens to a model.p with a line at a bus above 70 kV — runpp
+    starts such a net from a DC power flow's angles, which "auto" records for the solvers (NetSpec.va_init = "dc")."""
     npz = os.path.join(data_path, "netspec.npz")
     if hv_init is None:
         hv_init = os.environ.get("MAPDN_HV_INIT", "refuse")

@@ -93,6 +93,9 @@ class VoltageControlBatch:
         self.action_space = ActionSpace(low=-a["action_scale"] + a["action_bias"], high=a["action_scale"] + a["action_bias"])
         self._lib = _lib.load()
         cnet, self._keep = _lib.make_cnetspec(net)
+        tuning = dict(tuning or {})
+        if net.va_init == "dc":                                # runpp init="dc" (a line above 70 kV, from_pandapower(hv_init="auto"))
+            tuning.setdefault("nr_init", "dc")
         ccfg = _lib.make_cconfig(a, env_id_offset, tuning)     # tuning: per-handle launch / solver fields of mapdn_env_config
         h = _lib.C.c_void_p()
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()

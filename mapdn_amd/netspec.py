@@ -72,6 +72,10 @@ class NetSpec:
     # that is not fused.  Fused buses are one electrical node — same vm_pu / va in res_bus — but stay rows of every table the env
     # reads: their own p_mw / q_mvar, their own place in the zone frames, the reward's averages.  empty = no fusion
     bus_alias: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    # where every power flow starts (runpp's init="auto" as pd2ppc resolves it): "flat" — all buses at the ext_grid set-point — or "dc" —
+    # the angles of a DC power flow, magnitudes flat, what runpp does when a line touches a bus above 70 kV (calculate_voltage_angles on;
+    # data.from_pandapower(hv_init="auto") records it).  The env runs "dc" as mapdn_env_config.nr_init = 2.
+    va_init: str = "flat"
 
     def __post_init__(self):
         f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
@@ -94,6 +98,9 @@ class NetSpec:
         if not np.array_equal(self.bus_alias[self.bus_alias], self.bus_alias):
             raise ValueError("bus_alias must map every bus to a representative that represents itself")
         self.line_in_service = np.ascontiguousarray(self.line_in_service, dtype=np.uint8)
+        self.va_init = str(self.va_init)
+        if self.va_init not in ("flat", "dc"):
+            raise ValueError(f"va_init must be 'flat' or 'dc', got {self.va_init!r}")
 
     # ---- sizes -------------------------------------------------------------------------------
     @property
