@@ -103,6 +103,18 @@ typedef struct mapdn_netspec {
                                        OWN p_mw / q_mvar (the ext_grid's injection on the ext_grid's own bus), zone frames,
                                        get_state, the reward's averages over all buses.  A branch between two buses of one group
                                        is refused.  NULL = no fusion                                                          */
+  const double* load_const_z;       /* [n_load] voltage-dependent loads (runpp voltage_depend_loads=True): net.load.const_z_percent / 100 */
+  const double* load_const_i;       /* [n_load] ... const_i_percent / 100.  NULL (either) = 0.  Each in [0, 1], cz + ci <= 1.  A load then
+                                       draws S (cp + ci |V| + cz |V|^2), cp = 1 - ci - cz, in pandapower 2.x's scheme: the Newton
+                                       mismatch after every voltage update uses Sbus_k (cp + ci |V_k| + cz |V_k|^2) with the bus's WHOLE
+                                       net demand Sbus_k (loads minus sgens: the sgens of a ZIP bus are scaled too, makeSbus(vm=...)),
+                                       while the first mismatch (iteration 0) uses the constant-power Sbus and the Jacobian has no load
+                                       derivative (a chord-like Newton: iteration counts as runpp's).  res_bus p_mw / q_mvar of a ZIP bus
+                                       = its loads x the polynomial at the converged |V| minus its sgens (unscaled), plus shunts.  The
+                                       host reduces the columns to per-bus constants once per handle.  MAPDN_E_INVALID (with a message):
+                                       loads at one bus with different fractions (runpp solves with their mean, reports each with its
+                                       own), a ZIP load on the ext_grid bus, ZIP loads with bus_alias (fused buses), with nr_solver =
+                                       dense or with overlap_advance.  All-zero columns are the constant-power path.               */
 } mapdn_netspec;
 
 /* Constructor kwargs of VoltageControl (args/env_args/var_voltage_control.yaml:3-20). */

@@ -56,6 +56,7 @@ class CNetSpec(C.Structure):
         ("n_sgen", C.c_int32), ("sgen_bus", _pi), ("sgen_zone", _pi),
         ("ext_grid_bus", C.c_int32), ("ext_grid_vm_pu", C.c_double), ("sn_mva", C.c_double), ("f_hz", C.c_double),
         ("br_g_pu", _pd), ("load_scaling", _pd), ("sgen_scaling", _pd), ("bus_alias", _pi),
+        ("load_const_z", _pd), ("load_const_i", _pd),
     ]
 
 
@@ -260,6 +261,9 @@ def make_cnetspec(net: NetSpec):
     s.load_scaling = _p(net.load_scaling, _pd)
     s.sgen_scaling = _p(net.sgen_scaling, _pd)
     s.bus_alias = _p(net.bus_alias, _pi) if net.has_fused_buses else C.cast(None, _pi)
+    zl = net.has_zip_loads                          # NULL columns: constant-power loads, the path of before
+    s.load_const_z = _p(net.load_const_z, _pd) if zl else C.cast(None, _pd)
+    s.load_const_i = _p(net.load_const_i, _pd) if zl else C.cast(None, _pd)
     return s, keep
 
 

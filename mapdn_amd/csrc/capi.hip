@@ -180,7 +180,7 @@ static int settle_tree_geometry(mapdn_handle* h, int Bp, int n_cu) {
       min_rows = need;
     }
     if (min_rows >= 0) { h->err = "NR schedule: could not settle the number of peeled rows"; return MAPDN_E_INVALID; }
-    const int compiled = nr_geometry_compiled(W, L, g.h_lds, g.g_lds, g.rec_lds, g.flat_lds, c.nr_init == 2);
+    const int compiled = nr_geometry_compiled(W, L, g.h_lds, g.g_lds, g.rec_lds, g.flat_lds, (c.nr_init == 2 ? NR_VAR_DC : 0) | (P.zip ? NR_VAR_ZIP : 0));
     if (!compiled) return 1;
     g.W = W; g.L = L; g.lean = lean; g.rows = S.R;
     g.wgs = Bp / L;
@@ -282,6 +282,10 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
       if (cfg->nr_init == 2) {
         h->err = "nr_init = 2 (runpp init=\"dc\") is not built for nr_solver = dense (k_nr_dense starts flat only): use the tree or the sparse solver";
         return MAPDN_E_INVALID; }
+      if (P0.zip) {
+        h->err = "voltage-dependent loads (load_const_z / load_const_i) are not built for nr_solver = dense (k_nr_dense solves constant-power "
+                 "loads only): use the tree or the sparse solver";
+        return MAPDN_E_INVALID; }
       h->solver = 2;
     } else if (want_sparse) {
       SparseProg g0;
@@ -295,6 +299,9 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
       h->solver = 1; h->sp_lanes = Lc;
     }
   }
+  if (h->plan.zip && knob_int(cfg->overlap_advance, "MAPDN_OVERLAP_ADVANCE") != 0) {
+    // the commit of a ZIP bus reads the loads of the solve (cur_pl / cur_ql), which the side stream's profile rows overwrite
+    h->err = "overlap_advance is not available with voltage-dependent loads (load_const_z / load_const_i)"; return MAPDN_E_INVALID; }
   h->cfg = *cfg;
   h->device = device;
   std::memset(&h->d, 0, sizeof(h->d));
@@ -324,6 +331,8 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
   d.nr_init = cfg->nr_init;
 #define UP(field, vec) do { rc = dupload(h, &d.field, vec); if (rc) return rc; } while (0)
   if (d.nr_init == 2) UP(dc_pc, P.dc_pc);
+  d.zip = P.zip ? 1 : 0;
+  if (d.zip) { UP(zip_c, P.zip_c); d.zip_c_bytes = (uint32_t)(P.zip_c.size() * sizeof(double)); }
   UP(bus_of_pos, P.bus_of_pos); UP(root_children, P.root_children); UP(root_y, P.root_y);
   UP(pos_of_obus, P.pos_of_obus); UP(cm_kind, P.cm_kind);
   d.n_fused = (int32_t)P.fused_obus.size(); d.n_alias = (int32_t)P.alias_pos.size(); d.n_slack_group = (int32_t)P.slack_group.size();
@@ -554,7 +563,8 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
   {
     // the attribute is per kernel function, not per handle: always raise it to the full 160 KB so that
     // handles with different LDS needs can share an instantiation
-    const int lr = nr_set_lds_limit(G_.W, G_.L, G_.h_lds, G_.g_lds, G_.rec_lds, G_.flat_lds, 160 * 1024, d.nr_init == 2);
+    const int lr = nr_set_lds_limit(G_.W, G_.L, G_.h_lds, G_.g_lds, G_.rec_lds, G_.flat_lds, 160 * 1024,
+                                    (d.nr_init == 2 ? NR_VAR_DC : 0) | (d.zip ? NR_VAR_ZIP : 0));
     if (lr == -2) { h->err = "this (nr_waves, nr_lanes) combination is not compiled in (csrc/nr_inst_list.hpp)"; return MAPDN_E_INVALID; }
     if (lr != 0) { (void)hipGetLastError(); h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return MAPDN_E_HIP; }
   }
@@ -730,6 +740,12 @@ static int step_launches(mapdn_handle* h, const void* actions, int32_t actions_d
     if ((e_ = hipStreamWaitEvent(st, h->ev_join, 0)) != hipSuccess) return bail("hipStreamWaitEvent(join)", e_);
     launch_commit_fused(d, st);     // (with fused buses the side stream's profile rows race with this: overlap is an experiment switch)
     launch_advance(d, 0, 0, 1, d.sb_off_alt, st);
+  } else if (d.zip) {
+    // voltage-dependent loads: the commit of a ZIP bus reads the loads the solve used (cur_pl / cur_ql), so it runs before the profile
+    // rows overwrite them (two launches; no fused buses and no overlap with ZIP loads)
+    nr_launch(h, MODE_STEP, reward, terminated, info, st, fused ? actions : nullptr, actions_dtype);
+    launch_advance(d, 0, 0, 1, d.sb_off_alt, st);
+    launch_advance(d, add_noise, 1, 0, d.sb_off_alt, st);
   } else {
     nr_launch(h, MODE_STEP, reward, terminated, info, st, fused ? actions : nullptr, actions_dtype);
     launch_commit_fused(d, st);     // (only with fused buses: their own p_mw / q_mvar, before the element tables advance)

@@ -315,6 +315,18 @@ __device__ __forceinline__ void commit_bus(const Dev& d, int b_, int e, size_t S
     v = sqrt(ek * ek + fk * fk);
     va = atan2(fk, ek);
     P = -sb.x * d.sn; Q = -sb.y * d.sn;
+    if (d.zip) {                                 // voltage-dependent loads (results_bus): the bus's loads x (cp + ci |V| + cz |V|^2), its
+      const double ci = d.zip_c[2 * k], cz = d.zip_c[2 * k + 1];   // sgens as they are: demand + loads (vd - 1), the loads as the
+      if (ci != 0.0 || cz != 0.0) {                                // injection summed them (step(): this launch precedes the profile rows)
+        double Pl = 0.0, Ql = 0.0;
+        for (int i = d.load_ptr[k]; i < d.load_ptr[k + 1]; ++i) {
+          const int li = d.load_idx[i];
+          Pl += d.cur_pl[(size_t)li * S + e] * d.load_scale[li]; Ql += d.cur_ql[(size_t)li * S + e] * d.load_scale[li];
+        }
+        const double vd1 = fma(cz, v * v, fma(ci, v, 1.0 - (ci + cz))) - 1.0;
+        P = fma(Pl, vd1, P); Q = fma(Ql, vd1, Q);
+      }
+    }
   } else {
     v = d.vroot; va = 0.0;
     double ir = d.yrr0 * d.vroot, ii = d.yrr1 * d.vroot;     // I = Y_rr V_r + sum_neighbours Y_rk V_k
@@ -618,26 +630,26 @@ void launch_inject(const Dev& d, int mode, const void* actions, int dtype, const
 }
 // k_nr_tree instantiations: tables exported by the parts of nr_inst.hip (nr_inst_list.hpp).  RES is the residency of the step
 // records / flat-start constants as a compile-time fact (1 both, 2 neither, 3 records only); 0 = the generic body.
-// dc: the DC-angle-start variant (nr_init = 2; NrInst::DC)
+// var: the variant (NrInst::VAR: NR_VAR_DC the DC-angle start, nr_init = 2; NR_VAR_ZIP voltage-dependent loads)
 #define NR_TABLES \
   const NrInst* tabs[NR_INST_PARTS] = {nr_insts_0, nr_insts_1, nr_insts_2, nr_insts_3}; \
   const int cnt[NR_INST_PARTS] = {nr_n_insts_0, nr_n_insts_1, nr_n_insts_2, nr_n_insts_3};
-static const NrInst* nr_find(int W, int L, bool hl, bool gl, int res, int dc) {
+static const NrInst* nr_find(int W, int L, bool hl, bool gl, int res, int var) {
   NR_TABLES
   for (int p = 0; p < NR_INST_PARTS; ++p)
     for (int i = 0; i < cnt[p]; ++i) {
       const NrInst& I = tabs[p][i];
-      if (I.W == W && I.L == L && (I.HL != 0) == hl && (I.GL != 0) == gl && I.RES == res && (I.DC != 0) == (dc != 0)) return &I;
+      if (I.W == W && I.L == L && (I.HL != 0) == hl && (I.GL != 0) == gl && I.RES == res && I.VAR == var) return &I;
     }
   return nullptr;
 }
 static int nr_res_of(int rec_lds, int flat_lds) { return (rec_lds && flat_lds) ? 1 : (!rec_lds && !flat_lds) ? 2 : (rec_lds && !flat_lds) ? 3 : 0; }
 // the instantiation a handle with this geometry / residency runs: the specialised one when compiled in, else the generic body
-static const NrInst* nr_pick(int W, int L, int h_lds, int g_lds, int rec_lds, int flat_lds, int dc) {
+static const NrInst* nr_pick(int W, int L, int h_lds, int g_lds, int rec_lds, int flat_lds, int var) {
   const bool hl = h_lds != 0, gl = hl && g_lds != 0;
   const int res = nr_res_of(rec_lds, flat_lds);
-  const NrInst* I = res ? nr_find(W, L, hl, gl, res, dc) : nullptr;
-  return I ? I : nr_find(W, L, hl, gl, 0, dc);
+  const NrInst* I = res ? nr_find(W, L, hl, gl, res, var) : nullptr;
+  return I ? I : nr_find(W, L, hl, gl, 0, var);
 }
 #ifdef MAPDN_NR_STAMPS
 int nr_debug_stamps_0(unsigned long long*, int); int nr_debug_stamps_1(unsigned long long*, int);
@@ -656,7 +668,8 @@ void launch_nr(const Dev& d, int mode, double* reward, uint8_t* term, double* in
   if (d.sparse) { launch_nr_sparse(d, mode, reward, term, info, st); return; }
   const size_t lds = nr_lds_bytes(d.nr_waves, d.nr_lanes, d.n, d.nr_cslots, d.nr_xslots, d.nr_nclist, d.nr_h_lds, d.nr_g_lds,
                                   d.nr_line_lds ? d.n_line : 0, d.nr_rec_lds ? d.nr_rows : 0, d.nr_flat_lds ? d.nr_rows : 0);
-  const NrInst* I = nr_pick(d.nr_waves, d.nr_lanes, d.nr_h_lds, d.nr_g_lds, d.nr_rec_lds, d.nr_flat_lds, d.nr_init == 2);
+  const NrInst* I = nr_pick(d.nr_waves, d.nr_lanes, d.nr_h_lds, d.nr_g_lds, d.nr_rec_lds, d.nr_flat_lds,
+                            (d.nr_init == 2 ? NR_VAR_DC : 0) | (d.zip ? NR_VAR_ZIP : 0));
   if (!I) return;                                   // (mapdn_create refuses such a geometry: nr_set_lds_limit)
 #ifdef MAPDN_NR_STAMPS
   { NR_TABLES
@@ -668,15 +681,15 @@ void launch_nr(const Dev& d, int mode, double* reward, uint8_t* term, double* in
   (void)hipLaunchKernel(I->fn, dim3(d.Bp / d.nr_lanes), dim3(64 * d.nr_waves), args, lds, st);
 }
 // raises the dynamic-LDS limit of the instantiation this geometry runs; -2: the geometry is not compiled in
-int nr_set_lds_limit(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, size_t bytes, int dc) {
-  const NrInst* I = nr_pick(waves, lanes, h_lds, g_lds, rec_lds, flat_lds, dc);
+int nr_set_lds_limit(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, size_t bytes, int var) {
+  const NrInst* I = nr_pick(waves, lanes, h_lds, g_lds, rec_lds, flat_lds, var);
   if (!I) return -2;
   return hipFuncSetAttribute(I->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 0 : -1;
 }
 // 1 when some instantiation serves (waves, lanes) at all (host-side check, no device call)
 // ... and 2 when that instantiation is a specialised one (residency known at compile time: ~6 % faster than the generic body)
-int nr_geometry_compiled(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, int dc) {
-  const NrInst* I = nr_pick(waves, lanes, h_lds, g_lds, rec_lds, flat_lds, dc);
+int nr_geometry_compiled(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, int var) {
+  const NrInst* I = nr_pick(waves, lanes, h_lds, g_lds, rec_lds, flat_lds, var);
   return I ? (I->RES ? 2 : 1) : 0;
 }
 void launch_reset_begin(const Dev& d, const int64_t* start_rows, int first_try, hipStream_t st) {

@@ -104,6 +104,10 @@ struct Dev {
   int32_t nr_init;
   const DcRec* dc_recs; uint32_t dc_recs_bytes;
   const double* dc_pc;                           // [n] by position: Pbus - Re(Sbus) (plan.hpp Plan::dc_pc)
+  // ---- voltage-dependent (ZIP) loads (mapdn_netspec.load_const_z / _i; appended like the DC fields): k_nr_tree<..., ZIP = true> and
+  // k_nr_sparse scale Sbus_k by cp + ci |V_k| + cz |V_k|^2 after iteration 0; commit_bus reports the loads at the converged |V|
+  int32_t zip;
+  const double* zip_c; uint32_t zip_c_bytes;     // [n + 2][2] by position: (ci, cz) (plan.hpp Plan::zip_c)
 };
 
 void launch_inject(const Dev& d, int mode, const void* actions, int dtype, const double* pl, const double* ql,
@@ -113,9 +117,10 @@ void launch_inject_sgen(const Dev& d, int mode, const void* actions, int dtype, 
 // fused_actions != nullptr (MODE_STEP only): k_nr_tree's prologue performs the PV-bus injection itself (no k_inject_sgen launch)
 void launch_nr(const Dev& d, int mode, double* reward, uint8_t* term, double* info, hipStream_t st,
                const void* fused_actions = nullptr, int fused_dtype = 0);
-// dc: the DC-angle-start instantiations (mapdn_env_config.nr_init = 2)
-int nr_set_lds_limit(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, size_t bytes, int dc = 0);   // -2: geometry not instantiated
-int nr_geometry_compiled(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, int dc = 0);
+// var: the variant — NR_VAR_DC the DC-angle-start instantiations (mapdn_env_config.nr_init = 2), NR_VAR_ZIP the voltage-dependent-load ones
+enum { NR_VAR_DC = 1, NR_VAR_ZIP = 2 };
+int nr_set_lds_limit(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, size_t bytes, int var = 0);   // -2: geometry not instantiated
+int nr_geometry_compiled(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, int var = 0);
 // dynamic LDS of k_nr_tree (W waves, L envs per workgroup => Wt = W*64/L workers), in pair rows of L x 16 bytes:
 // node voltages (n+2: nodes, slack, trash), h (n+2) and G (2(n+2)) when resident, contribution slots (4 rows each),
 // x slots (1 row each); then verdict bytes, step-size partials (64*W doubles), overflow child list (padded to

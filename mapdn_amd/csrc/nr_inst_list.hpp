@@ -42,8 +42,19 @@
   X(4, 8, true, false, 3) X(4, 16, false, false, 2) X(4, 8, true, false, 0) X(4, 8, true, true, 0) X(4, 8, false, false, 0)
 #define NR_INSTS_DC_3(X)
 
+// voltage-dependent (ZIP) loads (k_nr_tree<..., ZIP = true>, mapdn_netspec.load_const_z / _i), with the flat and with the DC start:
+// the specialised geometries the chooser returns for the three feeder classes and the lean generic body of each of its candidate
+// pairs (the layout that fits whenever any does), so that the chooser always finds one; other geometries are refused ("not compiled in")
+#define NR_INSTS_ZIP_0(X) \
+  X(1, 16, true, true, 1) X(4, 16, true, false, 1) X(4, 16, false, false, 0)
+#define NR_INSTS_ZIP_1(X) \
+  X(2, 16, false, false, 2) X(4, 16, true, false, 3) X(1, 16, false, false, 0) X(2, 16, false, false, 0)
+#define NR_INSTS_ZIP_2(X) \
+  X(4, 8, true, false, 3) X(4, 8, true, false, 2) X(4, 16, false, false, 2) X(4, 8, false, false, 0)
+#define NR_INSTS_ZIP_3(X)
+
 namespace mapdn {
-struct NrInst { int W, L, HL, GL, RES; const void* fn; int DC; };   // DC: the DC-angle-start variant
+struct NrInst { int W, L, HL, GL, RES; const void* fn; int VAR; };   // VAR: 0 | NR_VAR_DC (DC-angle start) | NR_VAR_ZIP (ZIP loads), or both
 enum { NR_INST_PARTS = 4 };
 extern const NrInst nr_insts_0[]; extern const int nr_n_insts_0;
 extern const NrInst nr_insts_1[]; extern const int nr_n_insts_1;

@@ -142,7 +142,11 @@ struct BwdF { d2 h, g01, g23; };                        // factors of one step w
 // DC: runpp init="dc" (mapdn_env_config.nr_init = 2) — every solve starts from the angles of a DC power flow (two sweeps over the
 // schedule in the prologue) and its first Newton iteration forms the Jacobian from that start like any later one; the flat-start
 // constants are not read.  DC = false compiles to the flat-start kernel of before.
-template <int W, int L, bool HL, bool GL, int RES = 0, bool DC = false>
+// ZIP: voltage-dependent loads (mapdn_netspec.load_const_z / _i; pandapower 2.x newtonpf with voltage_depend_loads) — every mismatch
+// after iteration 0 is formed against Sbus_k (cp + ci |V_k| + cz |V_k|^2) with the node's (ci, cz) from d.zip_c (global, L2-resident,
+// read beside the Sbus entry); iteration 0 (the flat-start sweep or the DC start's first full sweep) and the Jacobian stay as they are
+// (no load derivative: runpp's chord-like scheme).  The stored Sbus stays constant-power.  ZIP = false compiles to the kernel of before.
+template <int W, int L, bool HL, bool GL, int RES = 0, bool DC = false, bool ZIP = false>
 __global__ void __launch_bounds__(64 * W)
 k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ terminated, double* __restrict__ info) {
   extern __shared__ d2 lds2[];
@@ -530,6 +534,17 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
   // the env's injection at a node: addressed by node, so that the Sbus array is n pair rows, not workers x rows (its re-reads in
   // every sweep then stay in L2 together with the G factor scratch); requested one row ahead, when the next row's node is known
   auto load_sb = [&](uint32_t kp) -> d2 { return bld2(rs, voS + (kp & 0xffffu) * pb, 0u); };
+  // ZIP: the node's (ci, cz) (n + 2 entries: the slack and trash rows are 0), requested with its Sbus entry
+  auto load_zc = [&](uint32_t kp) -> d2 {
+    const __amdgpu_buffer_rsrc_t rsZ = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(d.zip_c), 0, d.zip_c_bytes, 0x00020000);
+    return bld2(rsZ, (kp & 0xffffu) * 16u, 0u);
+  };
+  // ZIP: the injection the mismatch of iteration it is formed against — makeSbus(vm = |V|) after the first voltage update, the
+  // constant-power Sbus before it (the same expression in every sweep form, so that their verdicts agree bit for bit)
+  auto zip_sb = [&](d2 sb, d2 zc, double v2) -> d2 {
+    const double vd = fma(zc.y, v2, fma(zc.x, sqrt(v2), 1.0 - (zc.x + zc.y)));
+    return it > 0 ? d2{sb.x * vd, sb.y * vd} : sb;
+  };
   auto uni = [&](unsigned x) { return __builtin_amdgcn_readfirstlane(x); };
 
   // ---------------------------------------------------------------------------------------------------------------
@@ -560,8 +575,10 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
   auto fwd_sweep = [&](auto kind) {
     constexpr int K = decltype(kind)::value;
     Rec Tq[3]; d2 vkq[3], vpq[3];
+    d2 zq[3];                                      // ZIP: (ci, cz) of the ring's nodes
     load_rec(0, Tq[0]); load_rec(min(1, R - 1), Tq[1]);
-    { const unsigned kp = Tq[0].ix.w; vkq[0] = sV[(size_t)(kp & 0xffffu) * L]; vpq[0] = sV[(size_t)(kp >> 16) * L]; Tq[0].sb = load_sb(kp); }
+    { const unsigned kp = Tq[0].ix.w; vkq[0] = sV[(size_t)(kp & 0xffffu) * L]; vpq[0] = sV[(size_t)(kp >> 16) * L]; Tq[0].sb = load_sb(kp);
+      if constexpr (ZIP) zq[0] = load_zc(kp); }
     double pFp = 0.0, pFq = 0.0; bool pLive = false;       // deferred mismatch bookkeeping of the previous row
     // one row; u = ring position (compile-time), RS = the row number when it is a compile-time constant (peeled rows), else -1
     auto fwd_row = [&](auto uc, auto rsc, int r) {
@@ -589,6 +606,7 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
           const unsigned kpn = Tq[(u + 1) % 3].ix.w;
           vkq[(u + 1) % 3] = sV[(size_t)(kpn & 0xffffu) * L]; vpq[(u + 1) % 3] = sV[(size_t)(kpn >> 16) * L];
           Tq[(u + 1) % 3].sb = load_sb(kpn);
+          if constexpr (ZIP) zq[(u + 1) % 3] = load_zc(kpn);
           load_rec(min(r + 2, R - 1), Tq[(u + 2) % 3]);
         }
         SCHED_FENCE();
@@ -646,7 +664,9 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
         }
         // S_k = V_k conj(sum_j Y_kj V_j), mismatch F_k = S_k - Sbus_k
         const double sr = base_r + aS0, si = base_i + aS1;
-        const double Fp = sr - T.sb.x, Fq = si - T.sb.y;
+        d2 sbk = T.sb;
+        if constexpr (ZIP) sbk = zip_sb(T.sb, zq[u % 3], v2);
+        const double Fp = sr - sbk.x, Fq = si - sbk.y;
         pFp = Fp; pFq = Fq; pLive = (fl & S_LIVE) != 0;
         if constexpr (K == 0) {
           const double D0 = -(si - akk_i) - aD0, D1 = (sr + akk_r) - aD1;
@@ -923,9 +943,13 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
       u32x4 ixA = bldu4(rsP, voP, 0u), ixB = bldu4(rsP, voP, cl(1));
       d2 ykkN = bld2(rsP, voP + 16u, 0u), ykpN = bld2(rsP, voP + 32u, 0u), cksN = bld2(rsP, voP + 64u, 0u);
       d2 sbN = bld2(rs, voSb + (ixA.w & 0xffffu) * pb, 0u);
+      d2 zcN;
+      if constexpr (ZIP) zcN = load_zc(ixA.w);
       for (int j = 0; j < NPs; ++j) {
         const u32x4 ix = ixA;
         const d2 ykk = ykkN, ykp = ykpN, cks = cksN, sb = sbN;
+        d2 zc;
+        if constexpr (ZIP) zc = zcN;
         const unsigned k = ix.w & 0xffffu, pp = ix.w >> 16;
         const int nch = (int)((ix.x >> 8) & 255u);
         const d2 vk = sV[(size_t)k * L], vp = sV[(size_t)pp * L];
@@ -934,6 +958,7 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
           const unsigned s1 = cl(j + 1);
           ykkN = bld2(rsP, voP + 16u, s1); ykpN = bld2(rsP, voP + 32u, s1); cksN = bld2(rsP, voP + 64u, s1);
           sbN = bld2(rs, voSb + (ixB.w & 0xffffu) * pb, 0u);
+          if constexpr (ZIP) zcN = load_zc(ixB.w);
           ixA = ixB; ixB = bldu4(rsP, voP, cl(j + 2));
         }
         const double gkk = ykk.x, bkk = ykk.y, gkp = ykp.x, bkp = ykp.y;
@@ -953,7 +978,9 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
           for (int q = 3; q < nch; ++q) { const d2 a = sH[(size_t)d.mm_child[c_lo + q] * L]; aS0 += a.x; aS1 += a.y; }
         }
         const double sr = base_r + aS0, si = base_i + aS1;
-        note_mismatch(sr - sb.x, si - sb.y, (ix.x & 1u) != 0);
+        d2 sbk = sb;
+        if constexpr (ZIP) sbk = zip_sb(sb, zc, v2);
+        note_mismatch(sr - sbk.x, si - sbk.y, (ix.x & 1u) != 0);
         STAMP(120);
       }
     }

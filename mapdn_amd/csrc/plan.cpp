@@ -58,6 +58,36 @@ int build_plan(const mapdn_netspec& net_o, const mapdn_env_config& cfg, Plan& P,
     fused = fused || alias[b] != b;
   }
   for (int b = 0; b < nbo; ++b) if (alias[alias[b]] != alias[b]) { err = "netspec: bus_alias must map every bus to a representative that represents itself"; return MAPDN_E_INVALID; }
+  {  // voltage-dependent (ZIP) loads: validated here, on the caller's buses; reduced to per-node constants in build_plan_nodes
+    const double* cz = net_o.load_const_z;
+    const double* ci = net_o.load_const_i;
+    bool any = false;
+    for (int i = 0; i < net_o.n_load; ++i) {
+      const double z = cz ? cz[i] : 0.0, c = ci ? ci[i] : 0.0;
+      if (!(z >= 0.0 && z <= 1.0 && c >= 0.0 && c <= 1.0)) {
+        err = "netspec: load_const_z / load_const_i of load " + std::to_string(i) + " must be fractions in [0, 1] (const_*_percent / 100)"; return MAPDN_E_INVALID; }
+      if (z + c > 1.0) { err = "netspec: const_z_percent + const_i_percent need to be less or equal to 100% (load " + std::to_string(i) + ")"; return MAPDN_E_INVALID; }
+      any = any || z != 0.0 || c != 0.0;
+    }
+    if (any) {
+      if (fused) { err = "voltage-dependent loads (load_const_z / load_const_i) on a net with fused buses (bus_alias) are not supported"; return MAPDN_E_INVALID; }
+      std::vector<int> first(nbo, -1);
+      for (int i = 0; i < net_o.n_load; ++i) {
+        const int b = net_o.load_bus[i];
+        if (b < 0 || b >= nbo) continue;                                             // (refused with its own message below)
+        const double z = cz ? cz[i] : 0.0, c = ci ? ci[i] : 0.0;
+        if ((z != 0.0 || c != 0.0) && b == net_o.ext_grid_bus) {
+          err = "voltage-dependent load " + std::to_string(i) + " on the ext_grid bus is not supported (the slack bus reports the network injection)";
+          return MAPDN_E_INVALID; }
+        if (first[b] < 0) { first[b] = i; continue; }
+        const int j = first[b];
+        if (z != (cz ? cz[j] : 0.0) || c != (ci ? ci[j] : 0.0)) {
+          err = "loads " + std::to_string(j) + " and " + std::to_string(i) + " at bus " + std::to_string(b) + " carry different load_const_z / load_const_i: "
+                "runpp solves with their row-count mean but reports each load with its own polynomial (not supported)";
+          return MAPDN_E_INVALID; }
+      }
+    }
+  }
   if (!fused) {
     int rc = build_plan_nodes(net_o, net_o, cfg, P, err);
     if (rc) return rc;
@@ -372,6 +402,14 @@ static int build_plan_nodes(const mapdn_netspec& net, const mapdn_netspec& net_o
   P.load_scale.assign(net.n_load, 1.0); P.sgen_scale.assign(net.n_sgen, 1.0);
   if (net.load_scaling) P.load_scale.assign(net.load_scaling, net.load_scaling + net.n_load);
   if (net.sgen_scaling) P.sgen_scale.assign(net.sgen_scaling, net.sgen_scaling + net.n_sgen);
+  P.zip = false; P.zip_c.assign((size_t)2 * (P.n + 2), 0.0);
+  for (int i = 0; i < net.n_load; ++i) {         // (build_plan checked: same fractions for every load of a bus, none at the slack)
+    const double z = net.load_const_z ? net.load_const_z[i] : 0.0, c = net.load_const_i ? net.load_const_i[i] : 0.0;
+    if (z == 0.0 && c == 0.0) continue;
+    const int k = P.pos_of_bus[net.load_bus[i]];
+    P.zip_c[2 * k] = c; P.zip_c[2 * k + 1] = z;
+    P.zip = true;
+  }
 
   // ---- get_obs (distributed mode) — voltage_control_env.py:245-274 --------------------------------
   const int ss = cfg.state_space;

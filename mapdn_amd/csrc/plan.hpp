@@ -156,6 +156,10 @@ struct Plan {
   std::vector<double> shunt_p, shunt_q;         // [nb] by position, MW/MVAr at 1 p.u.
   std::vector<int32_t> sgen_bus;                // [ns] bus ids
   std::vector<double> load_scale, sgen_scale;   // [nl], [ns] scaling * in_service (pd2ppc sums p, q * scaling)
+  // voltage-dependent (ZIP) loads (mapdn_netspec.load_const_z / _i): zip false = constant power everywhere (NULL or all-zero columns).
+  // zip_c [n + 2][2] by position = (ci, cz) of the bus's loads (all loads of a bus carry the same fractions; slack and trash rows 0)
+  bool zip = false;
+  std::vector<double> zip_c;
 
   // get_obs / get_state tables
   int32_t n_agents = 0, obs_size = 0, state_size = 0, max_zone = 0;

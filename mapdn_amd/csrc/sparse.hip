@@ -13,6 +13,8 @@
 //
 // Same Newton iteration as the other two solvers (flat start, scaled polar unknowns [dtheta, d|V|/|V|], full Jacobian every
 // iteration, ||F||inf < tol, <= max_it iterations, V <- V (1 - z1) e^{-j z0}) and the same fused epilogue (nr_common.hpp).
+// Voltage-dependent loads (d.zip, a run-time branch here): the mismatch after iteration 0 is formed against Sbus_k (cp + ci |V_k| +
+// cz |V_k|^2), the Jacobian stays the constant-power one (pandapower 2.x newtonpf, as k_nr_tree).
 // Radial feeders keep the specialised tree kernel; MAPDN_NR_SPARSE=1 runs this one on them too (cross-check).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -164,7 +166,14 @@ k_nr_sparse(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ 
           if (col == i) { aii_r = ar; aii_i = ai; }
           if (slot >= 0) { d2* o = blk((unsigned)slot); o[0] = d2{ai, ar}; o[1] = d2{-ar, ai}; }
           if (++q == MNZ) {                      // (uniform) end of the row: diagonal block, right-hand side, verdict; next row
-            const double Fp = sr - sb.x, Fq = si - sb.y;
+            double sbr = sb.x, sbi = sb.y;
+            if (d.zip && it > 0) {               // voltage-dependent loads: makeSbus(vm = |V|) after the first voltage update (as k_nr_tree)
+              const double2 zc = ((const double2*)d.zip_c)[live ? i : (unsigned)n + 1u];
+              const double v2 = vi.x * vi.x + vi.y * vi.y;
+              const double vd = fma(zc.y, v2, fma(zc.x, sqrt(v2), 1.0 - (zc.x + zc.y)));
+              sbr *= vd; sbi *= vd;
+            }
+            const double Fp = sr - sbr, Fq = si - sbi;
             if (live) {
               d2* dg = blk(i);
               dg[0] = d2{-(si - aii_i), sr + aii_r}; dg[1] = d2{sr - aii_r, si + aii_i};

@@ -142,22 +142,28 @@ def trafo_to_pi(trafo, bus_vn_kv: np.ndarray, net_sn_mva: float, calculate_volta
                 br_g_pu=-y.imag, br_ratio=ratio, br_shift_deg=shift)
 
 
-def from_pandapower(net, hv_init: str = "refuse") -> NetSpec:
+def from_pandapower(net, hv_init: str = "refuse", zip_loads: str = "refuse") -> NetSpec:
     """pandapowerNet (`pp.from_pickle(model.p)`, voltage_control_env.py:400-405) -> NetSpec: what pd2ppc would build for
     runpp's defaults.  Converted: buses (0..n-1, all in service), lines (an open line / trafo switch takes the branch out
     when that is exact — no shunt terms, or open at both ends — and is refused otherwise), two-winding transformers (trafo_to_pi), loads / sgens with `scaling` and `in_service`,
     non-consecutive bus indices (mapped to the positions of the sorted index, pd2ppc's bus lookup),
     shunts (step, in_service), one ext_grid, closed bus-bus switches (bus fusion -> NetSpec.bus_alias).  Refused loudly, never guessed: voltage-dependent loads
-    (const_z_percent / const_i_percent: the constant-Z share would be a time-varying shunt), generators, three-winding transformers, impedances, wards, dc lines, storage,
+    (const_z_percent / const_i_percent != 0) unless zip_loads="runpp", generators, three-winding transformers, impedances, wards, dc lines, storage,
     closed bus-bus switches with z_ohm > 0 (pandapower models them as impedance branches, not as fused buses), fused buses of different vn_kv, and
     — by default (hv_init="refuse") — nets with a line at a bus above 70 kV: runpp's defaults then turn calculate_voltage_angles on AND start
     the Newton iteration from a DC power flow's angles (init="auto" -> "dc").
     hv_init="auto" does what runpp's defaults do: the DC-angle start (NetSpec.va_init = "dc", run by the solvers as mapdn_env_config.nr_init
     = 2) exactly when a line touches a bus above 70 kV, the flat start otherwise.  hv_init="flat" converts such a net with the flat start
     anyway: the converged answer is the same where both converge, the iteration count (and with it the 10-iteration verdict of
-    voltage_control_env.py:188-196) need not be, and with a vector-group shift such as 150 degrees the flat start does not converge."""
+    voltage_control_env.py:188-196) need not be, and with a vector-group shift such as 150 degrees the flat start does not converge.
+    zip_loads="runpp" converts voltage-dependent loads as runpp's voltage_depend_loads=True solves them (NetSpec.load_const_z /
+    load_const_i = percent / 100).  Still refused with it: loads of different fractions on one bus (runpp solves
+    with their row-count mean but reports each load with its own), a voltage-dependent load on the ext_grid bus, and voltage-dependent
+    loads on a net with fused buses."""
     if hv_init not in ("refuse", "flat", "auto"):
         raise ValueError("hv_init must be 'refuse', 'flat' or 'auto'")
+    if zip_loads not in ("refuse", "runpp"):
+        raise ValueError("zip_loads must be 'refuse' or 'runpp'")
     def table(name):
         t = net[name] if name in net else None
         return t if t is not None and len(t) else None
@@ -247,9 +253,13 @@ def from_pandapower(net, hv_init: str = "refuse") -> NetSpec:
                                               "pandapower keeps it energised from the closed end; not converted")
                 trafo_on[i] = False
     load, sgen = net.load, net.sgen
+    zip_cols = {}
     for col in ("const_z_percent", "const_i_percent"):
         if col in load and np.any(_col(load, col, 0.0) != 0.0):
-            raise NotImplementedError(f"net.load.{col} != 0: voltage-dependent loads (runpp voltage_depend_loads=True) are not converted")
+            if zip_loads != "runpp":
+                raise NotImplementedError(f"net.load.{col} != 0: voltage-dependent loads (runpp voltage_depend_loads=True) are not converted "
+                                          "by default; pass zip_loads='runpp' (or MAPDN_ZIP_LOADS=runpp) to solve them as runpp does")
+            zip_cols[col] = _col(load, col, 0.0) / 100.0
     on = lambda t: (t["in_service"].to_numpy(bool) if "in_service" in t else np.ones(len(t), bool)).astype(np.float64)
     kw = dict(
         name=str(net["name"] if "name" in net and net["name"] else "net"), bus_vn_kv=vn,
@@ -266,6 +276,23 @@ def from_pandapower(net, hv_init: str = "refuse") -> NetSpec:
         sn_mva=float(net.sn_mva), f_hz=float(net.f_hz))
     if fused_alias is not None:
         kw["bus_alias"] = fused_alias
+    if zip_cols:
+        cz = zip_cols.get("const_z_percent", np.zeros(len(load)))
+        ci = zip_cols.get("const_i_percent", np.zeros(len(load)))
+        lb = kw["load_bus"]
+        zip_bus = (cz != 0.0) | (ci != 0.0)
+        if fused_alias is not None:
+            raise NotImplementedError("voltage-dependent loads on a net with fused buses (closed bus-bus switches) are not converted")
+        if np.any(zip_bus & (lb == kw["ext_grid_bus"])):
+            raise NotImplementedError("a voltage-dependent load on the ext_grid bus is not converted (runpp reports the slack bus from the "
+                                      "network injection; its own load's polynomial is not modelled)")
+        for b in np.unique(lb):
+            at = lb == b
+            if np.ptp(cz[at]) != 0.0 or np.ptp(ci[at]) != 0.0:
+                raise NotImplementedError(f"the loads at bus {int(load['bus'].to_numpy()[at][0])} carry different const_z_percent / "
+                                          "const_i_percent: runpp solves with their row-count mean and reports each load with its own "
+                                          "polynomial, which is not converted")
+        kw.update(load_const_z=cz, load_const_i=ci)
     # runpp calculate_voltage_angles="auto": True only if a line touches a bus above 70 kV — and then init="auto" means init_va_degree="dc"
     hv_buses = set(np.nonzero(vn > 70.0)[0].tolist())
     touched = set(rb(line["from_bus"].to_numpy()).tolist()) | set(rb(line["to_bus"].to_numpy()).tolist())
@@ -458,18 +485,24 @@ def read_pandapower_pickle(path: str) -> InertNet:
     return net
 
 
-def load_scenario(data_path: str, pv_scale: float = 1.0, demand_scale: float = 1.0, hv_init: str = None):
+def load_scenario(data_path: str, pv_scale: float = 1.0, demand_scale: float = 1.0, hv_init: str = None, zip_loads: str = None):
     """(NetSpec, Profiles) of a scenario directory: netspec.npz or the reference's model.p (read as data by the restricted
     unpickler above — pandapower is not needed) + the three CSVs.  hv_init ("refuse" | "flat" | "auto", see from_pandapower; default:
     the MAPDN_HV_INIT environment variable, else "refuse") decides what happens to a model.p with a line at a bus above 70 kV — runpp
-    starts such a net from a DC power flow's angles, which "auto" records for the solvers (NetSpec.va_init = "dc")."""
+    starts such a net from a DC power flow's angles, which "auto" records for the solvers (NetSpec.va_init = "dc").  zip_loads
+    ("refuse" | "runpp", see from_pandapower; default: the MAPDN_ZIP_LOADS environment variable, else "refuse") decides what happens
+    to a model.p with voltage-dependent loads (const_z_percent / const_i_percent)."""
     npz = os.path.join(data_path, "netspec.npz")
     if hv_init is None:
         hv_init = os.environ.get("MAPDN_HV_INIT", "refuse")
+    if zip_loads is None:
+        zip_loads = os.environ.get("MAPDN_ZIP_LOADS", "refuse")
     if os.path.exists(npz):
         net = load_netspec(npz)
     elif os.path.exists(os.path.join(data_path, "model.p")):
-        net = from_pandapower(read_pandapower_pickle(os.path.join(data_path, "model.p")), hv_init=hv_init)
+        # (zip_loads is passed only when it is not the default: a from_pandapower stand-in written before it existed keeps working)
+        more = {} if zip_loads == "refuse" else dict(zip_loads=zip_loads)
+        net = from_pandapower(read_pandapower_pickle(os.path.join(data_path, "model.p")), hv_init=hv_init, **more)
     else:
         raise FileNotFoundError(f"no netspec.npz / model.p in {data_path}")
     return net, load_profiles_csv(data_path, pv_scale, demand_scale)

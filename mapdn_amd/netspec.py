@@ -76,13 +76,19 @@ class NetSpec:
     # the angles of a DC power flow, magnitudes flat, what runpp does when a line touches a bus above 70 kV (calculate_voltage_angles on;
     # data.from_pandapower(hv_init="auto") records it).  The env runs "dc" as mapdn_env_config.nr_init = 2.
     va_init: str = "flat"
+    # voltage-dependent loads (runpp voltage_depend_loads=True): net.load.const_z_percent / const_i_percent as fractions (percent / 100).
+    # A load draws S (cp + ci |V| + cz |V|^2), cp = 1 - ci - cz, during the Newton iteration and in res_bus.  empty = all zero (constant
+    # power, what every net without these columns is); data.from_pandapower(zip_loads="runpp") fills them.  DESIGN.md section 9.
+    load_const_z: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    load_const_i: np.ndarray = field(default_factory=lambda: np.zeros(0))
 
     def __post_init__(self):
         f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
         i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
         for k in ("bus_vn_kv", "line_r_ohm_per_km", "line_x_ohm_per_km", "line_c_nf_per_km",
                   "line_g_us_per_km", "line_length_km", "br_r_pu", "br_x_pu", "br_b_pu",
-                  "br_ratio", "br_shift_deg", "shunt_p_mw", "shunt_q_mvar", "br_g_pu", "load_scaling", "sgen_scaling"):
+                  "br_ratio", "br_shift_deg", "shunt_p_mw", "shunt_q_mvar", "br_g_pu", "load_scaling", "sgen_scaling",
+                  "load_const_z", "load_const_i"):
             setattr(self, k, f64(getattr(self, k)))
         if self.br_g_pu.shape[0] == 0 and np.shape(self.br_r_pu)[0]:
             self.br_g_pu = np.zeros(np.shape(self.br_r_pu)[0])
@@ -90,6 +96,17 @@ class NetSpec:
             self.load_scaling = np.ones(np.shape(self.load_bus)[0])
         if self.sgen_scaling.shape[0] == 0:
             self.sgen_scaling = np.ones(np.shape(self.sgen_bus)[0])
+        nl = np.shape(self.load_bus)[0]
+        for k in ("load_const_z", "load_const_i"):
+            v = getattr(self, k)
+            if v.shape[0] == 0:
+                setattr(self, k, np.zeros(nl))
+            elif v.shape != (nl,):
+                raise ValueError(f"{k} must have one entry per load ({nl}), got shape {v.shape}")
+            elif not (np.all(np.isfinite(v)) and np.all(v >= 0.0) and np.all(v <= 1.0)):
+                raise ValueError(f"{k} must be a fraction in [0, 1] (const_*_percent / 100) for every load")
+        if np.any(self.load_const_z + self.load_const_i > 1.0):
+            raise ValueError("const_z_percent + const_i_percent need to be less or equal to 100%!")
         if np.shape(self.bus_alias)[0] == 0:
             self.bus_alias = np.arange(np.shape(self.bus_vn_kv)[0])
         for k in ("bus_zone", "line_from_bus", "line_to_bus", "line_parallel", "load_bus",
@@ -122,6 +139,11 @@ class NetSpec:
     @property
     def n_sgen(self) -> int:
         return int(self.sgen_bus.shape[0])
+
+    @property
+    def has_zip_loads(self) -> bool:
+        """True when some load is voltage-dependent (load_const_z / load_const_i not all zero)"""
+        return bool(np.any(self.load_const_z != 0.0) or np.any(self.load_const_i != 0.0))
 
     @property
     def has_fused_buses(self) -> bool:
