@@ -113,8 +113,8 @@ typedef struct mapdn_netspec {
                                        = its loads x the polynomial at the converged |V| minus its sgens (unscaled), plus shunts.  The
                                        host reduces the columns to per-bus constants once per handle.  MAPDN_E_INVALID (with a message):
                                        loads at one bus with different fractions (runpp solves with their mean, reports each with its
-                                       own), a ZIP load on the ext_grid bus, ZIP loads with bus_alias (fused buses), with nr_solver =
-                                       dense or with overlap_advance.  All-zero columns are the constant-power path.               */
+                                       own), a ZIP load on the ext_grid bus, ZIP loads with bus_alias (fused buses) or with nr_solver =
+                                       dense.  All-zero columns are the constant-power path.                                       */
 } mapdn_netspec;
 
 /* Constructor kwargs of VoltageControl (args/env_args/var_voltage_control.yaml:3-20). */
@@ -203,13 +203,8 @@ typedef struct mapdn_env_config {
                                        runs inside the prologue of k_nr_tree when the handle uses the tree solver and has no
                                        auto_reset (one launch less per step); 1 same, refused (MAPDN_E_INVALID) when impossible;
                                        2 always its own launch (k_inject_sgen)                        env: MAPDN_FUSE_INJECT=1/0 */
-  int32_t overlap_advance;          /* step(): 1 — the profile rows of the advance (next row of the tables + noise, independent of
-                                       the solve) run on an internal side stream beside the solver launch, fork / join by events;
-                                       0 (default) everything on the caller's stream.              env: MAPDN_OVERLAP_ADVANCE=1/0 */
-  int32_t xcd_map;                  /* 1: the wide kernels (profile advance + commit, obs gather) serve the envs in the order that keeps an
-                                       env on the XCD its solver workgroup runs on (env e of an L-env workgroup i = e / L: XCD i % 8), so
-                                       that what one launch writes the next reads from that XCD's L2; 0 (default) / 2: plain order.
-                                       Same results; measured a wash (solver -1 us, gather +1 us), so it is opt-in.   env: MAPDN_XCD_MAP */
+  int32_t overlap_advance;          /* removed, must be 0 (MAPDN_E_INVALID otherwise); the field keeps the layout               */
+  int32_t xcd_map;                  /* removed, must be 0 (MAPDN_E_INVALID otherwise); the field keeps the layout               */
 } mapdn_env_config;
 
 typedef struct mapdn_dims_t {

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kernels.hpp"
@@ -15,12 +16,51 @@
 
 using namespace mapdn;
 
+static constexpr size_t CU_LDS = 160 * 1024;    // LDS of one CU: what one workgroup of any NR kernel may use
+
+// ---- tuning knobs: a field of mapdn_env_config (0 = automatic), overridden by an environment variable when one is set (tools,
+// A/B runs).  resolve_knobs reads them all once, at the top of mapdn_create, into the handle; nothing else reads the environment.
+struct Knobs {
+  int solver;                                    // nr_solver; MAPDN_NR_SPARSE=1 -> 1, MAPDN_NR_DENSE=1 -> 2
+  int waves, lanes;                              // k_nr_tree geometry pins
+  // tri-state residency / mode switches: 0 auto | 1 on | 2 off (nr_lean: 1 lean | 2 fat)
+  int lean, h_lds, g_lds, rec_lds, flat_lds, line_lds, mm_pass, fuse_inject;
+  int sp_lanes;
+  bool inject_full, debug_geometry;
+  double check_dx, check_quad;
+};
+
+static Knobs resolve_knobs(const mapdn_env_config& c) {
+  auto num = [](int v, const char* env) { const char* s = getenv(env); return s ? atoi(s) : v; };
+  auto tri = [](int v, const char* env) { const char* s = getenv(env); return s ? (atoi(s) ? 1 : 2) : v; };   // env NAME=1 on, NAME=0 off
+  auto f64 = [](double v, const char* env, double dflt) { const char* s = getenv(env); return s ? atof(s) : (v != 0.0 ? v : dflt); };
+  Knobs k;
+  k.solver = num(0, "MAPDN_NR_DENSE") ? 2 : (num(0, "MAPDN_NR_SPARSE") ? 1 : c.nr_solver);
+  k.waves = num(c.nr_waves, "MAPDN_NR_WAVES"); k.lanes = num(c.nr_lanes, "MAPDN_NR_LANES"); k.lean = tri(c.nr_lean, "MAPDN_NR_LEAN");
+  k.h_lds = tri(c.nr_h_lds, "MAPDN_NR_H_LDS"); k.g_lds = tri(c.nr_g_lds, "MAPDN_NR_G_LDS"); k.rec_lds = tri(c.nr_rec_lds, "MAPDN_NR_REC_LDS");
+  k.flat_lds = tri(c.nr_flat_lds, "MAPDN_NR_FLAT_LDS"); k.line_lds = tri(c.nr_line_lds, "MAPDN_NR_LINE_LDS");
+  k.mm_pass = tri(c.nr_mm_pass, "MAPDN_NR_MM_PASS");
+  k.fuse_inject = tri(c.fuse_inject, "MAPDN_FUSE_INJECT");
+  k.sp_lanes = num(c.sp_lanes, "MAPDN_SP_LANES");
+  k.inject_full = num(c.inject_full, "MAPDN_INJECT_FULL") != 0;
+  k.debug_geometry = num(c.debug_geometry, "MAPDN_DEBUG_GEOMETRY") != 0;
+  // 1e-7: with quadratic convergence the mismatch after such a step is ~|Y| dx^2 << tol, so a wrong prediction
+  // (which costs one extra mismatch-only sweep for that workgroup) practically never happens
+  k.check_dx = f64(c.nr_check_dx, "MAPDN_NR_CHECK_DX", 1e-7);
+  // quadratic extrapolation of the mismatch norm, no safety margin: in 4096-env samples of all three cases it
+  // predicts the last sweep of 95-100 % of the workgroups and never a non-final one (tools/predictor_study.py)
+  k.check_quad = f64(c.nr_check_quad, "MAPDN_NR_CHECK_QUAD", 1.0);
+  return k;
+}
+
 struct mapdn_handle {
   Plan plan;
   Schedule sched;
   SparseProg sprog;
+  Knobs knobs;
   int solver = 0;                 // 0 tree (radial), 1 general sparse (k_nr_sparse), 2 general dense (k_nr_dense)
   int sp_lanes = 0;
+  int nr_var = 0;                 // k_nr_tree variant: NR_VAR_DC | NR_VAR_ZIP
   mapdn_env_config cfg;
   Dev d;
   int device = 0;
@@ -28,13 +68,8 @@ struct mapdn_handle {
   std::vector<void*> allocs;
   bool have_profiles = false, was_reset = false, host_only = false;
   bool sbus_stale = true;         // Sbus / bus_ld do not reflect cur_pl / cur_ql (fresh handle, after mapdn_solve_only): the next
-                                  // injection runs the all-bus kernel; MAPDN_INJECT_FULL=1 keeps it that way (A/B, tests)
-  bool inject_full = false;
+                                  // injection runs the all-bus kernel; knobs.inject_full keeps it that way (A/B, tests)
   bool fuse_inject = false;       // step(): the PV-bus injection runs in the prologue of k_nr_tree instead of as k_inject_sgen (tree solver, no auto_reset)
-  bool overlap = false;           // step(): the profile rows of k_advance run on a side stream beside the solver launch (experiment)
-  hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  uint32_t sb_base = 0, sb_bytes = 0;   // the two Sbus buffers of nrbuf: d.sb_off / d.sb_off_alt alternate between them
-  std::vector<int32_t> ld_dest_host;
   size_t lds_bytes = 0;
   // what mapdn_create settled on (mapdn_get_nr_geometry); tree solver only: W .. mm_pass
   struct Geo { int W = 0, L = 0, lean = 0, rows = 0, h_lds = 0, g_lds = 0, rec_lds = 0, flat_lds = 0, line_lds = 0, mm_pass = 0, ncl = 0;
@@ -88,25 +123,15 @@ static int dalloc(mapdn_handle* h, T** p, size_t count) {
   return MAPDN_OK;
 }
 
-template <typename T>
-static int dupload(mapdn_handle* h, const T** p, const std::vector<T>& v) {
+template <typename Q, typename T>                // Q: T or const T
+static int dupload(mapdn_handle* h, Q** p, const std::vector<T>& v) {
+  static_assert(std::is_same<std::remove_const_t<Q>, T>::value, "dupload: element type mismatch");
   T* q = nullptr;
   int rc = dalloc(h, &q, v.size());
   if (rc) return rc;
   if (!v.empty()) HIPCHK(h, hipMemcpy(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   *p = q;
   return MAPDN_OK;
-}
-
-// ---- tuning knobs: a field of mapdn_env_config (0 = automatic), overridden by an environment variable when one is set (tools,
-// A/B runs).  Read once, in mapdn_create; nothing is process-global afterwards.
-static int knob_int(int cfg_value, const char* env) { const char* s = getenv(env); return s ? atoi(s) : cfg_value; }
-// tri-state residency / mode switches: cfg 0 auto | 1 on | 2 off;  env NAME=1 -> on, NAME=0 -> off
-static int knob_tri(int cfg_value, const char* env) { const char* s = getenv(env); return s ? (atoi(s) ? 1 : 2) : cfg_value; }
-static double knob_f64(double cfg_value, const char* env, double dflt) {
-  const char* s = getenv(env);
-  if (s) return atof(s);
-  return cfg_value != 0.0 ? cfg_value : dflt;
 }
 
 // ---- k_nr_tree launch geometry.
@@ -140,15 +165,12 @@ static double nr_model_ns(int W, int L, int n, int R, int h_lds, long wgs, int r
   return rounds * base * load * share;
 }
 
-// Settles the k_nr_tree geometry of a handle: (W, L, lean) — pinned by the config / environment or chosen by the model above —
-// then the schedule for Wt workers and the LDS residents.  Works without a device (host-only handles assume n_cu CUs).
+// Settles the k_nr_tree geometry of a handle: (W, L, lean) — pinned by the knobs or chosen by the model above — then the
+// schedule for Wt workers and the LDS residents.  Works without a device (host-only handles assume n_cu CUs).
 static int settle_tree_geometry(mapdn_handle* h, int Bp, int n_cu) {
   const Plan& P = h->plan;
-  const mapdn_env_config& c = h->cfg;
-  const size_t LDS_MAX = 160 * 1024;
+  const Knobs& k = h->knobs;
   if (P.n + 1 > 0xffff) { h->err = "networks with more than 65534 buses are not supported (16-bit node positions in the NR step records)"; return MAPDN_E_INVALID; }
-  const int f_h = knob_tri(c.nr_h_lds, "MAPDN_NR_H_LDS"), f_g = knob_tri(c.nr_g_lds, "MAPDN_NR_G_LDS"), f_rec = knob_tri(c.nr_rec_lds, "MAPDN_NR_REC_LDS"),
-            f_flat = knob_tri(c.nr_flat_lds, "MAPDN_NR_FLAT_LDS"), f_line = knob_tri(c.nr_line_lds, "MAPDN_NR_LINE_LDS");
   auto tri = [](int forced, bool dflt) { return forced == 1 ? 1 : (forced == 2 ? 0 : (dflt ? 1 : 0)); };
   // Optional LDS residents, in order of benefit: the h factors, the step records, the flat-start constants, the net.line
   // constants of the fused res_line epilogue, then the G factors (with everything resident the solve state never leaves
@@ -168,33 +190,32 @@ static int settle_tree_geometry(mapdn_handle* h, int Bp, int n_cu) {
       const int R_ = S.R;
       auto lds_for = [&](int hl, int gl, int ll, int rl, int fl) {
         return nr_lds_bytes(W, L, P.n, S.n_cslots, S.n_xslots, g.ncl, hl, gl, ll ? P.n_line : 0, rl ? R_ : 0, fl ? R_ : 0); };
-      g.h_lds = tri(f_h, !lean && lds_for(1, 0, 0, 0, 0) <= LDS_MAX);
-      g.rec_lds = tri(f_rec, !lean && lds_for(g.h_lds, 0, 0, 1, 0) <= LDS_MAX);
-      g.flat_lds = tri(f_flat, !lean && lds_for(g.h_lds, 0, 0, g.rec_lds, 1) <= LDS_MAX);
-      g.line_lds = (tri(f_line, !lean && P.n_line > 0 && lds_for(g.h_lds, 0, 1, g.rec_lds, g.flat_lds) <= LDS_MAX) && P.n_line > 0) ? 1 : 0;
-      g.g_lds = (tri(f_g, !lean && g.h_lds && lds_for(1, 1, g.line_lds, g.rec_lds, g.flat_lds) <= LDS_MAX) && g.h_lds) ? 1 : 0;
+      g.h_lds = tri(k.h_lds, !lean && lds_for(1, 0, 0, 0, 0) <= CU_LDS);
+      g.rec_lds = tri(k.rec_lds, !lean && lds_for(g.h_lds, 0, 0, 1, 0) <= CU_LDS);
+      g.flat_lds = tri(k.flat_lds, !lean && lds_for(g.h_lds, 0, 0, g.rec_lds, 1) <= CU_LDS);
+      g.line_lds = (tri(k.line_lds, !lean && P.n_line > 0 && lds_for(g.h_lds, 0, 1, g.rec_lds, g.flat_lds) <= CU_LDS) && P.n_line > 0) ? 1 : 0;
+      g.g_lds = (tri(k.g_lds, !lean && g.h_lds && lds_for(1, 1, g.line_lds, g.rec_lds, g.flat_lds) <= CU_LDS) && g.h_lds) ? 1 : 0;
       g.lds = lds_for(g.h_lds, g.g_lds, g.line_lds, g.rec_lds, g.flat_lds);
-      if (g.lds > LDS_MAX) return 1;
+      if (g.lds > CU_LDS) return 1;
       const int need = g.g_lds ? 0 : (g.h_lds ? NR_G_REG_ROWS : NR_HG_REG_ROWS);
       if (R_ >= need) { min_rows = -1; break; }
       min_rows = need;
     }
     if (min_rows >= 0) { h->err = "NR schedule: could not settle the number of peeled rows"; return MAPDN_E_INVALID; }
-    const int compiled = nr_geometry_compiled(W, L, g.h_lds, g.g_lds, g.rec_lds, g.flat_lds, (c.nr_init == 2 ? NR_VAR_DC : 0) | (P.zip ? NR_VAR_ZIP : 0));
+    const int compiled = nr_geometry_compiled(W, L, g.h_lds, g.g_lds, g.rec_lds, g.flat_lds, h->nr_var);
     if (!compiled) return 1;
     g.W = W; g.L = L; g.lean = lean; g.rows = S.R;
     g.wgs = Bp / L;
     // workgroups resident per CU: LDS, and the register file — every k_nr_tree instantiation keeps factors of its peeled rows in
     // AGPRs and uses 284 ... 452 of a SIMD's 512 registers per lane: one wave per SIMD, i.e. 4 / W workgroups per CU
-    g.resident = (int)std::max<size_t>(1, std::min<size_t>(LDS_MAX / std::max<size_t>(g.lds, 1), (size_t)std::max(4 / W, 1)));
+    g.resident = (int)std::max<size_t>(1, std::min<size_t>(CU_LDS / std::max<size_t>(g.lds, 1), (size_t)std::max(4 / W, 1)));
     const long per_round = (long)n_cu * g.resident;
     g.rounds = (int)((g.wgs + per_round - 1) / per_round);
     g.model_ns = nr_model_ns(W, L, P.n, S.R, g.h_lds, g.wgs, g.resident, n_cu) * (compiled == 2 ? 1.0 : 1.05);   // generic body: the
                                                                    // per-row residency branches cost ~6 %
     return 0;
   };
-  int W = knob_int(c.nr_waves, "MAPDN_NR_WAVES"), L = knob_int(c.nr_lanes, "MAPDN_NR_LANES");
-  const int lean_k = knob_tri(c.nr_lean, "MAPDN_NR_LEAN");          // 0 auto, 1 lean, 2 fat
+  const int W = k.waves, L = k.lanes, lean_k = k.lean;          // lean_k: 0 auto, 1 lean, 2 fat
   if ((W != 0 && W != 1 && W != 2 && W != 4 && W != 8) || (L != 0 && L != 4 && L != 8 && L != 16 && L != 32)) {
     h->err = "nr_waves (MAPDN_NR_WAVES) must be 1/2/4/8 and nr_lanes (MAPDN_NR_LANES) 4/8/16/32 (0 = automatic)"; return MAPDN_E_INVALID; }
   mapdn_handle::Geo best; Schedule bestS; bool have = false;
@@ -217,17 +238,16 @@ static int settle_tree_geometry(mapdn_handle* h, int Bp, int n_cu) {
     const int r = settle(W, L, lean_k == 1 ? 1 : 0, S, g);
     if (r < 0) return r;
     if (r == 0) { best = g; bestS = std::move(S); have = true; }
-    else if (g.lds > LDS_MAX) { h->err = "NR schedule needs more LDS than one CU has (160 KB); use fewer envs per workgroup (nr_lanes / MAPDN_NR_LANES) or fewer waves"; return MAPDN_E_INVALID; }
+    else if (g.lds > CU_LDS) { h->err = "NR schedule needs more LDS than one CU has (160 KB); use fewer envs per workgroup (nr_lanes / MAPDN_NR_LANES) or fewer waves"; return MAPDN_E_INVALID; }
   }
   if (!have) {
     h->err = (W || L) ? "this (nr_waves, nr_lanes) combination is not compiled in or does not fit the 160 KB LDS of a CU (csrc/nr_inst_list.hpp)"
                       : "no compiled k_nr_tree geometry fits this network into the 160 KB LDS of a CU";
     return MAPDN_E_INVALID; }
   if (forced) best.model_ns = 0.0;
-  const int mm = knob_tri(c.nr_mm_pass, "MAPDN_NR_MM_PASS");
-  best.mm_pass = (best.h_lds && mm != 2) ? 1 : 0;    // the pass needs the h array in LDS
+  best.mm_pass = (best.h_lds && k.mm_pass != 2) ? 1 : 0;    // the pass needs the h array in LDS
   h->geo = best; h->sched = std::move(bestS); h->lds_bytes = best.lds;
-  if (knob_int(c.debug_geometry, "MAPDN_DEBUG_GEOMETRY"))
+  if (k.debug_geometry)
     fprintf(stderr, "[mapdn] k_nr_tree geometry: W %d L %d lean %d rows %d cslots %d | LDS: h %d rec %d flat %d line %d G %d = %zu B | "
                     "%ld workgroups, %d per CU, %d round(s), model %.1f us\n",
             best.W, best.L, best.lean, best.rows, h->sched.n_cslots, best.h_lds, best.rec_lds, best.flat_lds, best.line_lds, best.g_lds,
@@ -235,101 +255,83 @@ static int settle_tree_geometry(mapdn_handle* h, int Bp, int n_cu) {
   return MAPDN_OK;
 }
 
-extern "C" {
+// ---- mapdn_create, stage by stage: create_impl below calls them in order.
 
-const char* mapdn_last_error(const mapdn_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
-
-#ifndef MAPDN_SRC_HASH
-#define MAPDN_SRC_HASH "unknown"
-#endif
-// "MAPDN_SRC_HASH=<sha256 of the sources and flags this library was built from>" (mapdn_amd/build.py): the loader compares it with the
-// sources on disk, so that a prebuilt library can never silently disagree with them
-const char* mapdn_build_info(void) { return "MAPDN_SRC_HASH=" MAPDN_SRC_HASH; }
-
-static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_env_config* cfg, int32_t B, int32_t device) {
-  if (!net || !cfg) { h->err = "null netspec/config"; return MAPDN_E_INVALID; }
-  if (B < 1) { h->err = "n_envs must be >= 1"; return MAPDN_E_INVALID; }
-  if (cfg->barrier_type < 0 || cfg->barrier_type > MAPDN_BARRIER_BUMP) { h->err = "unknown voltage_barrier_type"; return MAPDN_E_INVALID; }
-  if (!cfg->use_line_weight && !cfg->use_q_weight) {   // voltage_control_env.py:616-617
-    h->err = "NotImplementedError: Please at least give one weight, either q_weight or line_weight."; return MAPDN_E_INVALID; }
-  if (cfg->episode_limit < 2) { h->err = "episode_limit must be >= 2"; return MAPDN_E_INVALID; }
-  if (cfg->nr_init == 1) {   // reserved: see include/mapdn.h (the gating study found the warm start safe but without effect on the launch time)
-    h->err = "nr_init != 0 (warm start, runpp init=\"results\") is not built: tools/warm_start_study.py / profiles/r04_warm_start_study_*.json "
-             "show no iteration saved per 16-env workgroup; every solve starts flat like the reference's";
-    return MAPDN_E_INVALID; }
-  if (cfg->nr_init != 0 && cfg->nr_init != 2) { h->err = "nr_init must be 0 (flat start) or 2 (runpp init=\"dc\"); 1 (init=\"results\") is reserved"; return MAPDN_E_INVALID; }
-  int rc = build_plan(*net, *cfg, h->plan, h->err);
-  if (rc) return rc;
-  if (cfg->nr_init == 2 && !h->plan.dc_ok) {
-    h->err = !h->plan.fused_obus.empty()
-                 ? "nr_init = 2 (runpp init=\"dc\") on a net with fused buses (bus_alias) is not supported (the DC-angle start is defined on unfused nets only)"
-                 : "nr_init = 2 (runpp init=\"dc\"): the DC power flow matrix Bbus of this net is singular or not finite (a branch with x = 0?)";
-    return MAPDN_E_INVALID; }
-  {
-    // Solver choice.  pp.runpp (voltage_control_env.py:557) solves any connected net: radial feeders take the fill-free
-    // tree kernel; meshed nets the general sparse kernel (host symbolic factorisation with fill + a block program, all
-    // blocks of L envs in LDS); MAPDN_NR_DENSE=1 selects the dense LDS-resident LU with f64 MFMA (<= 65 buses),
-    // MAPDN_NR_SPARSE=1 the sparse kernel on a radial net (cross-checks).
-    const Plan& P0 = h->plan;
-    int pick = cfg->nr_solver;
-    if (const char* fs = getenv("MAPDN_NR_SPARSE")) if (atoi(fs)) pick = 1;
-    if (const char* fd = getenv("MAPDN_NR_DENSE")) if (atoi(fd)) pick = 2;
-    if (pick < 0 || pick > 2) { h->err = "nr_solver must be 0 (auto), 1 (sparse) or 2 (dense)"; return MAPDN_E_INVALID; }
-    const bool want_dense = pick == 2;
-    const bool want_sparse = !want_dense && (pick == 1 || !P0.radial);
-    if (want_dense) {
-      if (2 * P0.n > 1024) { h->err = "nr_solver = dense (MAPDN_NR_DENSE): the dense general-topology solver handles at most 513 buses (one thread per Jacobian row)"; return MAPDN_E_TOPOLOGY; }
-      if (cfg->nr_init == 2) {
-        h->err = "nr_init = 2 (runpp init=\"dc\") is not built for nr_solver = dense (k_nr_dense starts flat only): use the tree or the sparse solver";
-        return MAPDN_E_INVALID; }
-      if (P0.zip) {
-        h->err = "voltage-dependent loads (load_const_z / load_const_i) are not built for nr_solver = dense (k_nr_dense solves constant-power "
-                 "loads only): use the tree or the sparse solver";
-        return MAPDN_E_INVALID; }
-      h->solver = 2;
-    } else if (want_sparse) {
-      SparseProg g0;
-      sparse_symbolic(P0, g0);
-      int Lc = 0;
-      for (int l : {16, 8, 4, 2}) if (nr_sparse_lds_bytes(P0.n, g0.n_blocks, l) <= 160 * 1024) { Lc = l; break; }
-      if (!Lc) {
-        h->err = "topology: meshed network with " + std::to_string(P0.nb) + " buses needs " + std::to_string(g0.n_blocks) +
-                 " Jacobian blocks after fill; two envs of it do not fit the 160 KB LDS of a CU";
-        return MAPDN_E_TOPOLOGY; }
-      h->solver = 1; h->sp_lanes = Lc;
-    }
-  }
-  if (h->plan.zip && knob_int(cfg->overlap_advance, "MAPDN_OVERLAP_ADVANCE") != 0) {
-    // the commit of a ZIP bus reads the loads of the solve (cur_pl / cur_ql), which the side stream's profile rows overwrite
-    h->err = "overlap_advance is not available with voltage-dependent loads (load_const_z / load_const_i)"; return MAPDN_E_INVALID; }
-  h->cfg = *cfg;
-  h->device = device;
-  std::memset(&h->d, 0, sizeof(h->d));
-  h->d.B = B;
-  if (device == -1) {                                            // plan only (CPU tests): no device work
-    h->host_only = true;
-    if (h->solver == 0) return settle_tree_geometry(h, (B + 63) / 64 * 64, 256);   // (an MI355X has 256 CUs)
-    return MAPDN_OK;
-  }
-  int ndev = 0;
-  HIPCHK(h, hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) { h->err = "device index out of range"; return MAPDN_E_HIP; }
-  HIPCHK(h, hipSetDevice(device));
+// Solver choice.  pp.runpp (voltage_control_env.py:557) solves any connected net: radial feeders take the fill-free
+// tree kernel; meshed nets the general sparse kernel (host symbolic factorisation with fill + a block program, all
+// blocks of L envs in LDS); MAPDN_NR_DENSE=1 selects the dense LDS-resident LU with f64 MFMA (<= 65 buses),
+// MAPDN_NR_SPARSE=1 the sparse kernel on a radial net (cross-checks).
+static int choose_solver(mapdn_handle* h) {
   const Plan& P = h->plan;
+  const int pick = h->knobs.solver;
+  if (pick < 0 || pick > 2) { h->err = "nr_solver must be 0 (auto), 1 (sparse) or 2 (dense)"; return MAPDN_E_INVALID; }
+  if (pick == 2) {
+    if (2 * P.n > 1024) { h->err = "nr_solver = dense (MAPDN_NR_DENSE): the dense general-topology solver handles at most 513 buses (one thread per Jacobian row)"; return MAPDN_E_TOPOLOGY; }
+    h->solver = 2;
+  } else if (pick == 1 || !P.radial) {
+    SparseProg g0;
+    sparse_symbolic(P, g0);
+    int Lc = 0;
+    for (int l : {16, 8, 4, 2}) if (nr_sparse_lds_bytes(P.n, g0.n_blocks, l) <= CU_LDS) { Lc = l; break; }
+    if (!Lc) {
+      h->err = "topology: meshed network with " + std::to_string(P.nb) + " buses needs " + std::to_string(g0.n_blocks) +
+               " Jacobian blocks after fill; two envs of it do not fit the 160 KB LDS of a CU";
+      return MAPDN_E_TOPOLOGY; }
+    h->solver = 1; h->sp_lanes = Lc;
+  }
+  return MAPDN_OK;
+}
+
+// Every refusal of a config that build_plan and the solver choice accepted, for host-only and device handles alike (mapdn.h: a
+// pinned switch that cannot take effect is MAPDN_E_INVALID, never silently ignored).
+static int validate(mapdn_handle* h, const mapdn_env_config& c) {
+  const Plan& P = h->plan;
+  const Knobs& k = h->knobs;
+  if (c.nr_init == 1)   // reserved: see include/mapdn.h (the gating study found the warm start safe but without effect on the launch time)
+    return api_fail(h, MAPDN_E_INVALID, "nr_init != 0 (warm start, runpp init=\"results\") is not built: tools/warm_start_study.py / "
+                                        "profiles/r04_warm_start_study_*.json show no iteration saved per 16-env workgroup; every solve "
+                                        "starts flat like the reference's");
+  if (c.nr_init != 0 && c.nr_init != 2) return api_fail(h, MAPDN_E_INVALID, "nr_init must be 0 (flat start) or 2 (runpp init=\"dc\"); 1 (init=\"results\") is reserved");
+  if (c.nr_init == 2 && !P.dc_ok)
+    return api_fail(h, MAPDN_E_INVALID, !P.fused_obus.empty()
+                        ? "nr_init = 2 (runpp init=\"dc\") on a net with fused buses (bus_alias) is not supported (the DC-angle start is defined on unfused nets only)"
+                        : "nr_init = 2 (runpp init=\"dc\"): the DC power flow matrix Bbus of this net is singular or not finite (a branch with x = 0?)");
+  if (h->solver == 2 && c.nr_init == 2)
+    return api_fail(h, MAPDN_E_INVALID, "nr_init = 2 (runpp init=\"dc\") is not built for nr_solver = dense (k_nr_dense starts flat only): use the tree or the sparse solver");
+  if (h->solver == 2 && P.zip)
+    return api_fail(h, MAPDN_E_INVALID, "voltage-dependent loads (load_const_z / load_const_i) are not built for nr_solver = dense (k_nr_dense solves "
+                                        "constant-power loads only): use the tree or the sparse solver");
+  if (c.overlap_advance) return api_fail(h, MAPDN_E_INVALID, "overlap_advance was removed (measured slower than the single stream): it must be 0");
+  if (c.xcd_map) return api_fail(h, MAPDN_E_INVALID, "xcd_map was removed (the XCD-aligned env order measured a wash): it must be 0");
+  if (k.fuse_inject == 1 && h->solver != 0)
+    return api_fail(h, MAPDN_E_INVALID, "fuse_inject = 1 exists on the tree solver only (this handle runs the general sparse / dense solver)");
+  if (k.fuse_inject == 1 && (c.auto_reset || k.inject_full))
+    return api_fail(h, MAPDN_E_INVALID, "fuse_inject = 1 needs a handle without auto_reset and without inject_full");
+  if (h->solver == 1 && k.sp_lanes != 0 && k.sp_lanes != 16 && k.sp_lanes != 8 && k.sp_lanes != 4 && k.sp_lanes != 2)
+    return api_fail(h, MAPDN_E_INVALID, "sp_lanes (MAPDN_SP_LANES) must be 16, 8, 4 or 2 (0 = automatic)");
+  return MAPDN_OK;
+}
+
+#define UP(field, vec) do { if (const int rc_ = dupload(h, &d.field, vec)) return rc_; } while (0)
+#define AL(field, rows) do { if (const int rc_ = dalloc(h, &d.field, (size_t)(rows) * d.Bp)) return rc_; } while (0)
+
+// the scalars of Dev and the topology plan
+static int upload_topology(mapdn_handle* h) {
+  const Plan& P = h->plan;
+  const mapdn_env_config& c = h->cfg;
   Dev& d = h->d;
-  d.B = B; d.Bp = (B + 63) / 64 * 64; d.nb = P.nb; d.n = P.n; d.nl = P.nl; d.ns = P.ns; d.n_line = P.n_line;
+  d.nb = P.nb; d.n = P.n; d.nl = P.nl; d.ns = P.ns; d.n_line = P.n_line;
   d.nbo = P.nbo;                                 // original buses (> nb with fused buses): the rows of res_bus / obs / state
   d.ncol = P.ns + 2 * P.nl;
   d.vroot = P.vroot; d.sn = P.sn_mva; d.tol = P.tol; d.max_it = 10;   // runpp max_iteration="auto" -> 10
   d.yrr0 = P.yrr[0]; d.yrr1 = P.yrr[1];
-  d.barrier_type = cfg->barrier_type; d.use_line_weight = cfg->use_line_weight; d.episode_limit = cfg->episode_limit;
-  d.reset_action = cfg->reset_action; d.auto_reset = cfg->auto_reset ? 1 : 0; d.voltage_weight = cfg->voltage_weight; d.q_weight = cfg->q_weight;
-  d.line_weight = cfg->line_weight; d.v_lower = cfg->v_lower; d.v_upper = cfg->v_upper;
-  d.action_low = cfg->action_low; d.action_high = cfg->action_high;
-  d.seed_lo = (uint32_t)(cfg->seed & 0xffffffffull); d.seed_hi = (uint32_t)(cfg->seed >> 32);
-  d.env_id_offset = cfg->env_id_offset;
-  d.nr_init = cfg->nr_init;
-#define UP(field, vec) do { rc = dupload(h, &d.field, vec); if (rc) return rc; } while (0)
+  d.barrier_type = c.barrier_type; d.use_line_weight = c.use_line_weight; d.episode_limit = c.episode_limit;
+  d.reset_action = c.reset_action; d.auto_reset = c.auto_reset ? 1 : 0; d.voltage_weight = c.voltage_weight; d.q_weight = c.q_weight;
+  d.line_weight = c.line_weight; d.v_lower = c.v_lower; d.v_upper = c.v_upper;
+  d.action_low = c.action_low; d.action_high = c.action_high;
+  d.seed_lo = (uint32_t)(c.seed & 0xffffffffull); d.seed_hi = (uint32_t)(c.seed >> 32);
+  d.env_id_offset = c.env_id_offset;
+  d.nr_init = c.nr_init;
   if (d.nr_init == 2) UP(dc_pc, P.dc_pc);
   d.zip = P.zip ? 1 : 0;
   if (d.zip) { UP(zip_c, P.zip_c); d.zip_c_bytes = (uint32_t)(P.zip_c.size() * sizeof(double)); }
@@ -345,262 +347,280 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
   d.n_root_children = (int32_t)P.root_children.size();
   UP(load_ptr, P.load_ptr); UP(load_idx, P.load_idx); UP(sgen_ptr, P.sgen_ptr); UP(sgen_idx, P.sgen_idx);
   UP(shunt_p, P.shunt_p); UP(shunt_q, P.shunt_q); UP(load_scale, P.load_scale); UP(sgen_scale, P.sgen_scale);
-  {
-    std::vector<int32_t> sgb, sgb_of(P.nb, -1), lb, mlo;
-    for (int k = 0; k < P.nb; ++k) {
-      if (P.sgen_ptr[k + 1] > P.sgen_ptr[k]) { sgb_of[k] = (int32_t)sgb.size(); sgb.push_back(k); }
-      else if (P.load_ptr[k + 1] > P.load_ptr[k]) {
-        lb.push_back(k);
-        if (P.load_ptr[k + 1] - P.load_ptr[k] > 1 && k < P.n) mlo.push_back(k);
-      }
+  std::vector<LineFlow> padded(P.lines);         // read 16 bytes at a time by the NR kernel's LDS staging
+  if (padded.size() % 2) padded.push_back(LineFlow{});
+  UP(lines, padded);
+  return MAPDN_OK;
+}
+
+// The tables of the step()/reset() injection: buses with sgens (PV buses), load-only buses, load-only buses with several loads, the
+// 16-byte records of the fused prologue of k_nr_tree, and where k_advance puts a load that is alone on its bus (ld_dest).
+static int setup_pv_buses(mapdn_handle* h) {
+  const Plan& P = h->plan;
+  Dev& d = h->d;
+  std::vector<int32_t> sgb, sgb_of(P.nb, -1), lb, mlo;
+  for (int k = 0; k < P.nb; ++k) {
+    if (P.sgen_ptr[k + 1] > P.sgen_ptr[k]) { sgb_of[k] = (int32_t)sgb.size(); sgb.push_back(k); }
+    else if (P.load_ptr[k + 1] > P.load_ptr[k]) {
+      lb.push_back(k);
+      if (P.load_ptr[k + 1] - P.load_ptr[k] > 1 && k < P.n) mlo.push_back(k);
     }
-    d.n_sgb = (int32_t)sgb.size(); d.n_lb = (int32_t)lb.size(); d.n_mlo = (int32_t)mlo.size();
-    if (lb.empty()) lb.push_back(0);
-    if (mlo.empty()) mlo.push_back(0);
-    {   // per (PV bus | load-only bus with several loads) row of the injection: what the fused prologue of k_nr_tree needs in one 16-byte load
-      std::vector<int32_t> rec;
-      auto put = [&](int k, bool pv) {
-        const int nsg = pv ? P.sgen_ptr[k + 1] - P.sgen_ptr[k] : 0, nld = P.load_ptr[k + 1] - P.load_ptr[k];
-        rec.push_back(k < P.n ? k : -1);            // Sbus is stored by node position (sb_index[k] == k, see alloc_nrbuf below)
-        rec.push_back(k);
-        rec.push_back(pv ? P.sgen_idx[P.sgen_ptr[k]] : -1);
-        rec.push_back((nsg << 8) | std::min(nld, 2));
-        rec.push_back(nld > 0 ? P.load_idx[P.load_ptr[k]] : -1);        // the first two loads of the bus (CSR order)
-        rec.push_back(nld > 1 ? P.load_idx[P.load_ptr[k] + 1] : -1);
-        rec.push_back(0); rec.push_back(0);
-      };
-      for (int i = 0; i < d.n_sgb; ++i) put(sgb[i], true);
-      for (int i = 0; i < d.n_mlo; ++i) put(mlo[i], false);
-      UP(sgb_rec, rec);
-    }
-    UP(sgb_pos, sgb); UP(sgb_of_pos, sgb_of); UP(lb_pos, lb); UP(mlo_pos, mlo);
-    h->ld_dest_host.assign(std::max(P.nl, 1), 2);             // filled once the Sbus order (sb_index) is known, see alloc_nrbuf
-    rc = dalloc(h, &d.bus_ld, (size_t)2 * d.n_sgb * d.Bp); if (rc) return rc;
-    h->inject_full = knob_int(cfg->inject_full, "MAPDN_INJECT_FULL") != 0;
   }
-  {
-    std::vector<LineFlow> padded(P.lines);               // read 16 bytes at a time by the NR kernel's LDS staging
-    if (padded.size() % 2) padded.push_back(LineFlow{});
-    UP(lines, padded);
+  d.n_sgb = (int32_t)sgb.size(); d.n_lb = (int32_t)lb.size(); d.n_mlo = (int32_t)mlo.size();
+  if (lb.empty()) lb.push_back(0);
+  if (mlo.empty()) mlo.push_back(0);
+  {   // per (PV bus | load-only bus with several loads) row of the injection: what the fused prologue of k_nr_tree needs in one 16-byte load
+    std::vector<int32_t> rec;
+    auto put = [&](int k, bool pv) {
+      const int nsg = pv ? P.sgen_ptr[k + 1] - P.sgen_ptr[k] : 0, nld = P.load_ptr[k + 1] - P.load_ptr[k];
+      rec.push_back(k < P.n ? k : -1);            // Sbus is stored by node position
+      rec.push_back(k);
+      rec.push_back(pv ? P.sgen_idx[P.sgen_ptr[k]] : -1);
+      rec.push_back((nsg << 8) | std::min(nld, 2));
+      rec.push_back(nld > 0 ? P.load_idx[P.load_ptr[k]] : -1);        // the first two loads of the bus (CSR order)
+      rec.push_back(nld > 1 ? P.load_idx[P.load_ptr[k] + 1] : -1);
+      rec.push_back(0); rec.push_back(0);
+    };
+    for (int i = 0; i < d.n_sgb; ++i) put(sgb[i], true);
+    for (int i = 0; i < d.n_mlo; ++i) put(mlo[i], false);
+    UP(sgb_rec, rec);
   }
+  UP(sgb_pos, sgb); UP(sgb_of_pos, sgb_of); UP(lb_pos, lb); UP(mlo_pos, mlo);
+  // ld_dest: a load alone on its bus goes straight to the Sbus entry (kind 0) / bus_ld row (kind 1) of that bus; 2: neither
+  std::vector<int32_t> ld_dest(std::max(P.nl, 1), 2);
+  for (int k = 0; k < P.nb; ++k) {
+    if (P.load_ptr[k + 1] - P.load_ptr[k] != 1) continue;
+    const int li = P.load_idx[P.load_ptr[k]];
+    if (sgb_of[k] >= 0) ld_dest[li] = (sgb_of[k] << 2) | 1;
+    else if (k < P.n) ld_dest[li] = (k << 2) | 0;
+  }
+  UP(ld_dest, ld_dest);
+  return dalloc(h, &d.bus_ld, (size_t)2 * d.n_sgb * d.Bp);
+}
+
+// gatherable state block gbuf (rows of Bp doubles): cur_pv cur_q [ns] | vm va res_p res_q [nbo]
+struct GbufRows { int pv, q, vm, va, rp, rq, n; };
+static GbufRows gbuf_rows(const Dev& d) {
+  const int vm = 2 * d.ns;
+  return {0, d.ns, vm, vm + d.nbo, vm + 2 * d.nbo, vm + 3 * d.nbo, vm + 4 * d.nbo};
+}
+
+// env state: element tables, gbuf, per-env bookkeeping, the staging of mapdn_solve_only and mapdn_stats
+static int setup_env_state(mapdn_handle* h) {
+  Dev& d = h->d;
   const size_t Bp = d.Bp;
-#define AL(field, rows) do { rc = dalloc(h, &d.field, (size_t)(rows) * Bp); if (rc) return rc; } while (0)
   AL(q_new, d.ns); AL(cur_pl, d.nl); AL(cur_ql, d.nl); AL(pl, d.n_line);
-  // gatherable state block: cur_pv cur_q [ns] | vm va res_p res_q [nb]
-  const int r_pv = 0, r_q = r_pv + d.ns, r_vm = r_q + d.ns, r_va = r_vm + d.nbo,
-            r_rp = r_va + d.nbo, r_rq = r_rp + d.nbo, g_rows = r_rq + d.nbo;
-  rc = dalloc(h, &d.gbuf, (size_t)g_rows * Bp); if (rc) return rc;
-  d.cur_pv = d.gbuf + (size_t)r_pv * Bp;
-  d.cur_q = d.gbuf + (size_t)r_q * Bp; d.vm = d.gbuf + (size_t)r_vm * Bp; d.va = d.gbuf + (size_t)r_va * Bp;
-  d.res_p = d.gbuf + (size_t)r_rp * Bp; d.res_q = d.gbuf + (size_t)r_rq * Bp;
+  const GbufRows r = gbuf_rows(d);
+  AL(gbuf, r.n);
+  d.cur_pv = d.gbuf + (size_t)r.pv * Bp;
+  d.cur_q = d.gbuf + (size_t)r.q * Bp; d.vm = d.gbuf + (size_t)r.vm * Bp; d.va = d.gbuf + (size_t)r.va * Bp;
+  d.res_p = d.gbuf + (size_t)r.rp * Bp; d.res_q = d.gbuf + (size_t)r.rq * Bp;
   AL(sum_rewards, 1); AL(steps, 1); AL(start_row, 1); AL(draw, 1); AL(done, 1); AL(pending, 1);
   AL(active, 1); AL(commit, 1); AL(bad_start, 1); AL(resetting, 1); AL(adv_row, 1); AL(adv_draw, 1); AL(iters, 1); AL(conv, 1);
-  {
-    std::vector<uint8_t> ones(Bp, 1);
-    HIPCHK(h, hipMemcpy(d.done, ones.data(), Bp, hipMemcpyHostToDevice));   // nothing is steppable before reset
-  }
-  const int32_t* tmp;
-  {  // obs / state columns -> (source row of gbuf, scale, extra rows to add); -1 = zero padding.
-     // P/Q columns with the effective PV add-back (voltage_control_env.py:238-244) = res_bus row + the
-     // sgen.p_mw / q_mvar rows of the sgens on that bus.
-    std::vector<std::vector<int>> sgens_at(P.nbo);
-    for (int j = 0; j < P.ns; ++j) sgens_at[P.sgen_bus[j]].push_back(j);
-    auto tables = [&](const std::vector<int32_t>& kind, const std::vector<int32_t>& idx, std::vector<int32_t>& rows,
-                      std::vector<double>& scale, std::vector<int32_t>& xptr, std::vector<int32_t>& xrow) {
-      rows.resize(kind.size()); scale.assign(kind.size(), 1.0); xptr.assign(kind.size() + 1, 0); xrow.clear();
-      for (size_t c = 0; c < kind.size(); ++c) {
-        switch (kind[c]) {
-          case G_P_ADDBACK: rows[c] = r_rp + idx[c]; for (int j : sgens_at[idx[c]]) xrow.push_back(r_pv + j); break;
-          case G_Q_ADDBACK: rows[c] = r_rq + idx[c]; for (int j : sgens_at[idx[c]]) xrow.push_back(r_q + j); break;
-          case G_SGEN_P: rows[c] = r_pv + idx[c]; break;
-          case G_SGEN_Q: rows[c] = r_q + idx[c]; break;
-          case G_VM: rows[c] = r_vm + idx[c]; break;
-          case G_VA_RAD: rows[c] = r_va + idx[c]; break;
-          case G_P: rows[c] = r_rp + idx[c]; break;
-          case G_Q: rows[c] = r_rq + idx[c]; break;
-          case G_VA_DEG: rows[c] = r_va + idx[c]; scale[c] = 180.0 / M_PI; break;
-          default: rows[c] = -1; break;
-        }
-        xptr[c + 1] = (int32_t)xrow.size();
-        if (xptr[c + 1] > xptr[c]) rows[c] |= 0x40000000;   // GATHER_HAS_EXTRA
+  std::vector<uint8_t> ones(Bp, 1);
+  HIPCHK(h, hipMemcpy(d.done, ones.data(), Bp, hipMemcpyHostToDevice));   // nothing is steppable before reset
+  int rc;
+  if ((rc = dalloc(h, &h->t_pl, (size_t)d.nl * Bp)) || (rc = dalloc(h, &h->t_ql, (size_t)d.nl * Bp)) ||
+      (rc = dalloc(h, &h->t_pv, (size_t)d.ns * Bp)) || (rc = dalloc(h, &h->t_q, (size_t)d.ns * Bp)))
+    return rc;
+  return dalloc(h, &h->stats_dev, 4);
+}
+
+// obs / state columns -> (source row of gbuf, scale, extra rows to add); -1 = zero padding.  P/Q columns with the effective PV
+// add-back (voltage_control_env.py:238-244) = res_bus row + the sgen.p_mw / q_mvar rows of the sgens on that bus.
+static int setup_gather_tables(mapdn_handle* h) {
+  const Plan& P = h->plan;
+  const Dev& d = h->d;
+  const GbufRows g = gbuf_rows(d);
+  std::vector<std::vector<int>> sgens_at(P.nbo);
+  for (int j = 0; j < P.ns; ++j) sgens_at[P.sgen_bus[j]].push_back(j);
+  auto tables = [&](const std::vector<int32_t>& kind, const std::vector<int32_t>& idx, std::vector<int32_t>& rows,
+                    std::vector<double>& scale, std::vector<int32_t>& xptr, std::vector<int32_t>& xrow) {
+    rows.resize(kind.size()); scale.assign(kind.size(), 1.0); xptr.assign(kind.size() + 1, 0); xrow.clear();
+    for (size_t c = 0; c < kind.size(); ++c) {
+      switch (kind[c]) {
+        case G_P_ADDBACK: rows[c] = g.rp + idx[c]; for (int j : sgens_at[idx[c]]) xrow.push_back(g.pv + j); break;
+        case G_Q_ADDBACK: rows[c] = g.rq + idx[c]; for (int j : sgens_at[idx[c]]) xrow.push_back(g.q + j); break;
+        case G_SGEN_P: rows[c] = g.pv + idx[c]; break;
+        case G_SGEN_Q: rows[c] = g.q + idx[c]; break;
+        case G_VM: rows[c] = g.vm + idx[c]; break;
+        case G_VA_RAD: rows[c] = g.va + idx[c]; break;
+        case G_P: rows[c] = g.rp + idx[c]; break;
+        case G_Q: rows[c] = g.rq + idx[c]; break;
+        case G_VA_DEG: rows[c] = g.va + idx[c]; scale[c] = 180.0 / M_PI; break;
+        default: rows[c] = -1; break;
       }
-      if (xrow.empty()) xrow.push_back(0);
-    };
-    std::vector<int32_t> rows, xptr, xrow; std::vector<double> scale; const double* dt;
-    tables(P.obs_kind, P.obs_idx, rows, scale, xptr, xrow);
-    rc = dupload(h, &tmp, rows); if (rc) return rc; h->obs_rows = (int32_t*)tmp;
-    rc = dupload(h, &dt, scale); if (rc) return rc; h->obs_scale = (double*)dt;
-    rc = dupload(h, &tmp, xptr); if (rc) return rc; h->obs_xptr = (int32_t*)tmp;
-    rc = dupload(h, &tmp, xrow); if (rc) return rc; h->obs_xrow = (int32_t*)tmp;
-    tables(P.state_kind, P.state_idx, rows, scale, xptr, xrow);     // get_state has no add-back
-    rc = dupload(h, &tmp, rows); if (rc) return rc; h->state_rows = (int32_t*)tmp;
-    rc = dupload(h, &dt, scale); if (rc) return rc; h->state_scale = (double*)dt;
-  }
-  const int maxn = std::max(std::max(d.nbo, d.n_line), std::max(d.nl, d.ns));
-  std::vector<int32_t> io(maxn);
-  for (int i = 0; i < maxn; ++i) io[i] = i;
-  rc = dupload(h, &tmp, io); if (rc) return rc; h->iota_idx = (int32_t*)tmp;
-  rc = dalloc(h, &h->t_pl, (size_t)d.nl * Bp); if (rc) return rc;
-  rc = dalloc(h, &h->t_ql, (size_t)d.nl * Bp); if (rc) return rc;
-  rc = dalloc(h, &h->t_pv, (size_t)d.ns * Bp); if (rc) return rc;
-  rc = dalloc(h, &h->t_q, (size_t)d.ns * Bp); if (rc) return rc;
-  rc = dalloc(h, &h->stats_dev, 4); if (rc) return rc;
-  // NR scratch `nrbuf`: factor blocks (fb_rows pair rows) | Sbus (nblk pair rows, entry sbi[k] for position k) | Vout;
-  // a single buffer resource addresses it
-  auto alloc_nrbuf = [&](size_t fb_rows, size_t nblk, const std::vector<int32_t>& sbi) -> int {
-    const size_t sb_off = fb_rows * Bp * 16;
-    const size_t vout_off = sb_off + 2 * nblk * Bp * 16;        // two Sbus buffers
-    const size_t bytes = vout_off + (size_t)VOF * (P.n + 1) * Bp * sizeof(double);
-    if (bytes >= (size_t)0xFFFFFFFFu) { h->err = "env batch too large: NR scratch exceeds the 4 GiB one buffer resource addresses; use fewer envs per handle"; return MAPDN_E_INVALID; }
-    rc = dalloc(h, &d.nrbuf, bytes / sizeof(double)); if (rc) return rc;
-    d.nrbuf_bytes = (uint32_t)bytes;
-    d.sb_off = (uint32_t)sb_off; d.sb_off_alt = (uint32_t)(sb_off + nblk * Bp * 16);
-    h->sb_base = d.sb_off; h->sb_bytes = (uint32_t)(nblk * Bp * 16);
-    d.r_vout = (uint32_t)(vout_off / (Bp * sizeof(double)));
-    rc = dupload(h, &d.sb_index, sbi); if (rc) return rc;
-    {   // ld_dest: a load alone on its bus goes straight to the Sbus entry (kind 0) / bus_ld row (kind 1) of that bus
-      std::vector<int32_t> sgb_of(P.nb, -1); int nsg = 0;
-      for (int k = 0; k < P.nb; ++k) if (P.sgen_ptr[k + 1] > P.sgen_ptr[k]) sgb_of[k] = nsg++;
-      for (int k = 0; k < P.nb; ++k) {
-        if (P.load_ptr[k + 1] - P.load_ptr[k] != 1) continue;
-        const int li = P.load_idx[P.load_ptr[k]];
-        if (sgb_of[k] >= 0) h->ld_dest_host[li] = (sgb_of[k] << 2) | 1;
-        else if (k < P.n) h->ld_dest_host[li] = (sbi[k] << 2) | 0;
-      }
-      rc = dupload(h, &d.ld_dest, h->ld_dest_host); if (rc) return rc;
+      xptr[c + 1] = (int32_t)xrow.size();
+      if (xptr[c + 1] > xptr[c]) rows[c] |= 0x40000000;   // GATHER_HAS_EXTRA
     }
-    std::vector<double> row(Bp, d.vroot);   // slack entry of Vout: V = vroot + 0j (angle 0 from the memset)
-    double* rootv = d.nrbuf + ((size_t)d.r_vout + (size_t)VOF * P.n) * Bp;
-    HIPCHK(h, hipMemcpy(rootv + (size_t)VO_E * Bp, row.data(), Bp * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(rootv + (size_t)VO_VM * Bp, row.data(), Bp * sizeof(double), hipMemcpyHostToDevice));
-    std::vector<int32_t> vmrow(P.nbo), varow(P.nbo);
-    for (int b = 0; b < P.nbo; ++b) { const int k = P.pos_of_obus[b]; vmrow[b] = (int)d.r_vout + VOF * k + VO_VM; varow[b] = (int)d.r_vout + VOF * k + VO_VA; }
-    rc = dupload(h, &tmp, vmrow); if (rc) return rc; h->vm_row = (int32_t*)tmp;
-    rc = dupload(h, &tmp, varow); if (rc) return rc; h->va_row = (int32_t*)tmp;
-    return MAPDN_OK;
+    if (xrow.empty()) xrow.push_back(0);
   };
-  // ---- step() composition switches that only exist on the tree solver: checked BEFORE the solver-specific set-up returns
-  // (mapdn.h: a pinned switch that cannot take effect is MAPDN_E_INVALID, never silently ignored)
-  {
-    const int fi = knob_tri(cfg->fuse_inject, "MAPDN_FUSE_INJECT");
-    const bool ov = knob_int(cfg->overlap_advance, "MAPDN_OVERLAP_ADVANCE") != 0, xm = knob_tri(cfg->xcd_map, "MAPDN_XCD_MAP") == 1;
-    if (h->solver != 0 && (fi == 1 || ov || xm)) {
-      h->err = "fuse_inject = 1 / overlap_advance / xcd_map exist on the tree solver only (this handle runs the general sparse / dense solver)";
-      return MAPDN_E_INVALID; }
-    if (ov && fi != 2 && !cfg->auto_reset && !knob_int(cfg->inject_full, "MAPDN_INJECT_FULL")) {
-      h->err = "overlap_advance = 1 has no effect while the PV-bus injection runs in the solver's prologue (the prologue reads what the side "
-               "stream's profile rows write): set fuse_inject = 2 as well";
-      return MAPDN_E_INVALID; }
+  std::vector<int32_t> rows, xptr, xrow; std::vector<double> scale;
+  int rc;
+  tables(P.obs_kind, P.obs_idx, rows, scale, xptr, xrow);
+  if ((rc = dupload(h, &h->obs_rows, rows)) || (rc = dupload(h, &h->obs_scale, scale)) || (rc = dupload(h, &h->obs_xptr, xptr)) ||
+      (rc = dupload(h, &h->obs_xrow, xrow)))
+    return rc;
+  tables(P.state_kind, P.state_idx, rows, scale, xptr, xrow);     // get_state has no add-back
+  if ((rc = dupload(h, &h->state_rows, rows)) || (rc = dupload(h, &h->state_scale, scale))) return rc;
+  std::vector<int32_t> io(std::max(std::max(d.nbo, d.n_line), std::max(d.nl, d.ns)));   // identity rows of the result exports
+  for (size_t i = 0; i < io.size(); ++i) io[i] = (int32_t)i;
+  return dupload(h, &h->iota_idx, io);
+}
+
+// NR scratch `nrbuf` (kernels.hpp): factor blocks (fb_rows pair rows) | 2 x Sbus (nblk pair rows each, entry k for position k) | Vout;
+// a single buffer resource addresses it.  Also the rows of |V| / angle in Vout that mapdn_solve_only exports.
+static int alloc_nrbuf(mapdn_handle* h, size_t fb_rows, size_t nblk) {
+  const Plan& P = h->plan;
+  Dev& d = h->d;
+  const size_t Bp = d.Bp;
+  const size_t sb_off = fb_rows * Bp * 16;
+  const size_t vout_off = sb_off + 2 * nblk * Bp * 16;        // two Sbus buffers
+  const size_t bytes = vout_off + (size_t)VOF * (P.n + 1) * Bp * sizeof(double);
+  if (bytes >= (size_t)0xFFFFFFFFu) { h->err = "env batch too large: NR scratch exceeds the 4 GiB one buffer resource addresses; use fewer envs per handle"; return MAPDN_E_INVALID; }
+  if (const int rc = dalloc(h, &d.nrbuf, bytes / sizeof(double))) return rc;
+  d.nrbuf_bytes = (uint32_t)bytes;
+  d.sb_off = (uint32_t)sb_off; d.sb_off_alt = (uint32_t)(sb_off + nblk * Bp * 16);
+  d.r_vout = (uint32_t)(vout_off / (Bp * sizeof(double)));
+  std::vector<double> row(Bp, d.vroot);   // slack entry of Vout: V = vroot + 0j (angle 0 from the memset)
+  double* rootv = d.nrbuf + ((size_t)d.r_vout + (size_t)VOF * P.n) * Bp;
+  HIPCHK(h, hipMemcpy(rootv + (size_t)VO_E * Bp, row.data(), Bp * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(rootv + (size_t)VO_VM * Bp, row.data(), Bp * sizeof(double), hipMemcpyHostToDevice));
+  std::vector<int32_t> vmrow(P.nbo), varow(P.nbo);
+  for (int b = 0; b < P.nbo; ++b) { const int k = P.pos_of_obus[b]; vmrow[b] = (int)d.r_vout + VOF * k + VO_VM; varow[b] = (int)d.r_vout + VOF * k + VO_VA; }
+  int rc;
+  if ((rc = dupload(h, &h->vm_row, vmrow)) || (rc = dupload(h, &h->va_row, varow))) return rc;
+  return MAPDN_OK;
+}
+
+// k_nr_dense (dense.hip): one env per workgroup, dense Jacobian in LDS, f64 MFMA
+static int setup_dense(mapdn_handle* h) {
+  const Plan& P = h->plan;
+  Dev& d = h->d;
+  d.dense = 1; d.dn_N = (2 * P.n + 15) / 16 * 16; d.dn_lda = d.dn_N + 2;
+  if (d.dn_N > 128) {                            // beyond 65 buses the Jacobian of every env lives in a slab of global memory
+    const size_t per_env = (size_t)d.dn_N * d.dn_lda;
+    if (const int rc = dalloc(h, &d.dn_A, per_env * d.Bp)) return rc;
   }
-  // ---- general-topology paths (see the solver choice above)
-  if (h->solver == 2) {                           // k_nr_dense (dense.hip): one env per workgroup, dense Jacobian in LDS, f64 MFMA
-    d.dense = 1; d.dn_N = (2 * P.n + 15) / 16 * 16; d.dn_lda = d.dn_N + 2;
-    if (d.dn_N > 128) {                            // beyond 65 buses the Jacobian of every env lives in a slab of global memory
-      const size_t per_env = (size_t)d.dn_N * d.dn_lda;
-      rc = dalloc(h, &d.dn_A, per_env * d.Bp); if (rc) return rc;
-    }
-    UP(gy_ptr, P.gy_ptr); UP(gy_col, P.gy_col); UP(gy_val, P.gy_val);
-    std::vector<int32_t> sbi(P.n);
-    for (int k = 0; k < P.n; ++k) sbi[k] = k;
-    rc = alloc_nrbuf(0, (size_t)P.n, sbi); if (rc) return rc;
-    if (nr_dense_prepare(d) != 0) { (void)hipGetLastError(); h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for k_nr_dense"; return MAPDN_E_HIP; }
-    h->lds_bytes = nr_dense_lds_bytes(d);
-    return MAPDN_OK;
-  }
-  if (h->solver == 1) {                           // k_nr_sparse (sparse.hip): host-compiled block elimination program
+  UP(gy_ptr, P.gy_ptr); UP(gy_col, P.gy_col); UP(gy_val, P.gy_val);
+  if (const int rc = alloc_nrbuf(h, 0, (size_t)P.n)) return rc;
+  if (nr_dense_prepare(d) != 0) { (void)hipGetLastError(); h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for k_nr_dense"; return MAPDN_E_HIP; }
+  h->lds_bytes = nr_dense_lds_bytes(d);
+  return MAPDN_OK;
+}
+
+// k_nr_sparse (sparse.hip): host-compiled block elimination program
+static int setup_sparse(mapdn_handle* h) {
+  const Plan& P = h->plan;
+  Dev& d = h->d;
+  if (h->knobs.sp_lanes) h->sp_lanes = h->knobs.sp_lanes;      // pinned envs per workgroup (16 / 8 / 4 / 2)
+  else {
     // Envs per (one-wave) workgroup: fewer envs = more sub-lanes per env = fewer phases, and a smaller LDS tile = more
     // resident waves per CU to hide each other's LDS latency.  Score = envs in flight per CU / length of the per-iteration
     // instruction stream (phases + assembly entries); measured on case33 / case141 / case322 with tie lines closed
     // (profiles/r02_sparse_lanes_sweep.txt): the score ranks the four geometries in the measured order.
-    {
-      double best = -1.0;
-      for (int l : {16, 8, 4, 2}) {
-        SparseProg g;
-        sparse_program(P, 64 / l, g);
-        const size_t lds = nr_sparse_lds_bytes(P.n, g.n_blocks, l);
-        if (lds > 160 * 1024) continue;
-        const double waves = (double)std::min<size_t>(160 * 1024 / lds, 8);
-        const double score = waves * l / ((double)g.n_phases + 0.5 * g.rows_per_sub * g.max_nnz);
-        if (score > best) { best = score; h->sp_lanes = l; }
-      }
+    double best = -1.0;
+    for (int l : {16, 8, 4, 2}) {
+      SparseProg g;
+      sparse_program(P, 64 / l, g);
+      const size_t lds = nr_sparse_lds_bytes(P.n, g.n_blocks, l);
+      if (lds > CU_LDS) continue;
+      const double waves = (double)std::min<size_t>(CU_LDS / lds, 8);
+      const double score = waves * l / ((double)g.n_phases + 0.5 * g.rows_per_sub * g.max_nnz);
+      if (score > best) { best = score; h->sp_lanes = l; }
     }
-    {                                                  // pinned envs per workgroup (16 / 8 / 4 / 2)
-      const int l = knob_int(cfg->sp_lanes, "MAPDN_SP_LANES");
-      if (l == 16 || l == 8 || l == 4 || l == 2) h->sp_lanes = l;
-      else if (l != 0) { h->err = "sp_lanes (MAPDN_SP_LANES) must be 16, 8, 4 or 2 (0 = automatic)"; return MAPDN_E_INVALID; }
-    }
-    sparse_program(P, 64 / h->sp_lanes, h->sprog);
-    const SparseProg& G = h->sprog;
-    if (nr_sparse_lds_bytes(P.n, G.n_blocks, h->sp_lanes) > 160 * 1024) { h->err = "sp_lanes (MAPDN_SP_LANES): does not fit in LDS"; return MAPDN_E_INVALID; }
-    d.sparse = 1; d.sp_lanes = h->sp_lanes; d.sp_blocks = G.n_blocks; d.sp_fill = (int32_t)G.fill_slots.size();
-    d.sp_phases = G.n_phases; d.sp_rows_per_sub = G.rows_per_sub; d.sp_max_nnz = G.max_nnz;
-    UP(sp_ops, G.ops); d.sp_ops_bytes = (uint32_t)(G.ops.size() * sizeof(SpOp));
-    UP(sp_nz, G.nz); d.sp_nz_bytes = (uint32_t)(G.nz.size() * sizeof(SpNz));
-    { std::vector<int32_t> fs(G.fill_slots); if (fs.empty()) fs.push_back(G.n_blocks - 1); UP(sp_fill_slots, fs); }
-    std::vector<int32_t> sbi(P.n);
-    for (int k = 0; k < P.n; ++k) sbi[k] = k;
-    rc = alloc_nrbuf(0, (size_t)P.n, sbi); if (rc) return rc;
-    if (nr_sparse_prepare(h->sp_lanes) != 0) { (void)hipGetLastError(); h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for k_nr_sparse"; return MAPDN_E_HIP; }
-    h->lds_bytes = nr_sparse_lds_bytes(P.n, G.n_blocks, h->sp_lanes);
-    return MAPDN_OK;
   }
-  // ---- NR launch geometry (settle_tree_geometry above)
-  {
-    hipDeviceProp_t prop;
-    HIPCHK(h, hipGetDeviceProperties(&prop, device));
-    rc = settle_tree_geometry(h, d.Bp, prop.multiProcessorCount); if (rc) return rc;
-  }
+  sparse_program(P, 64 / h->sp_lanes, h->sprog);
+  const SparseProg& G = h->sprog;
+  if (nr_sparse_lds_bytes(P.n, G.n_blocks, h->sp_lanes) > CU_LDS) { h->err = "sp_lanes (MAPDN_SP_LANES): does not fit in LDS"; return MAPDN_E_INVALID; }
+  d.sparse = 1; d.sp_lanes = h->sp_lanes; d.sp_blocks = G.n_blocks; d.sp_fill = (int32_t)G.fill_slots.size();
+  d.sp_phases = G.n_phases; d.sp_rows_per_sub = G.rows_per_sub; d.sp_max_nnz = G.max_nnz;
+  UP(sp_ops, G.ops); d.sp_ops_bytes = (uint32_t)(G.ops.size() * sizeof(SpOp));
+  UP(sp_nz, G.nz); d.sp_nz_bytes = (uint32_t)(G.nz.size() * sizeof(SpNz));
+  { std::vector<int32_t> fs(G.fill_slots); if (fs.empty()) fs.push_back(G.n_blocks - 1); UP(sp_fill_slots, fs); }
+  if (const int rc = alloc_nrbuf(h, 0, (size_t)P.n)) return rc;
+  if (nr_sparse_prepare(h->sp_lanes) != 0) { (void)hipGetLastError(); h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for k_nr_sparse"; return MAPDN_E_HIP; }
+  h->lds_bytes = nr_sparse_lds_bytes(P.n, G.n_blocks, h->sp_lanes);
+  return MAPDN_OK;
+}
+
+// k_nr_tree (nr_tree.hpp): the launch geometry (settle_tree_geometry), its schedule and the NR scratch
+static int setup_tree(mapdn_handle* h) {
+  const Plan& P = h->plan;
+  Dev& d = h->d;
+  hipDeviceProp_t prop;
+  HIPCHK(h, hipGetDeviceProperties(&prop, h->device));
+  if (const int rc = settle_tree_geometry(h, d.Bp, prop.multiProcessorCount)) return rc;
   const mapdn_handle::Geo& G_ = h->geo;
-  const int ncl = G_.ncl, h_lds = G_.h_lds, g_lds = G_.g_lds;
+  const Schedule& S = h->sched;
   d.nr_waves = G_.W; d.nr_lanes = G_.L; d.nr_h_lds = G_.h_lds; d.nr_g_lds = G_.g_lds; d.nr_line_lds = G_.line_lds; d.nr_rec_lds = G_.rec_lds; d.nr_flat_lds = G_.flat_lds;
-  // 1e-7: with quadratic convergence the mismatch after such a step is ~|Y| dx^2 << tol, so a wrong prediction
-  // (which costs one extra mismatch-only sweep for that workgroup) practically never happens
-  d.nr_check_dx = knob_f64(cfg->nr_check_dx, "MAPDN_NR_CHECK_DX", 1e-7);
-  // quadratic extrapolation of the mismatch norm, no safety margin: in 4096-env samples of all three cases it
-  // predicts the last sweep of 95-100 % of the workgroups and never a non-final one (tools/predictor_study.py)
-  d.nr_check_quad = knob_f64(cfg->nr_check_quad, "MAPDN_NR_CHECK_QUAD", 1.0);
-  d.nr_rows = h->sched.R; d.nr_cslots = h->sched.n_cslots; d.nr_xslots = h->sched.n_xslots; d.nr_nclist = ncl;
+  d.nr_check_dx = h->knobs.check_dx; d.nr_check_quad = h->knobs.check_quad;
+  d.nr_rows = S.R; d.nr_cslots = S.n_cslots; d.nr_xslots = S.n_xslots; d.nr_nclist = G_.ncl;
   {
     // the attribute is per kernel function, not per handle: always raise it to the full 160 KB so that
     // handles with different LDS needs can share an instantiation
-    const int lr = nr_set_lds_limit(G_.W, G_.L, G_.h_lds, G_.g_lds, G_.rec_lds, G_.flat_lds, 160 * 1024,
-                                    (d.nr_init == 2 ? NR_VAR_DC : 0) | (d.zip ? NR_VAR_ZIP : 0));
+    const int lr = nr_set_lds_limit(G_.W, G_.L, G_.h_lds, G_.g_lds, G_.rec_lds, G_.flat_lds, CU_LDS, h->nr_var);
     if (lr == -2) { h->err = "this (nr_waves, nr_lanes) combination is not compiled in (csrc/nr_inst_list.hpp)"; return MAPDN_E_INVALID; }
     if (lr != 0) { (void)hipGetLastError(); h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return MAPDN_E_HIP; }
   }
-  UP(sched, h->sched.steps); d.sched_bytes = (uint32_t)(h->sched.steps.size() * sizeof(StepRec));
-  UP(clist, h->sched.clist);
-  UP(mm_ptr, h->sched.mm_ptr); UP(mm_child, h->sched.mm_child);
-  UP(mm_recs, h->sched.mm_recs); d.mm_recs_bytes = (uint32_t)(h->sched.mm_recs.size() * sizeof(StepRec)); d.mm_np = h->sched.mm_np;
+  UP(sched, S.steps); d.sched_bytes = (uint32_t)(S.steps.size() * sizeof(StepRec));
+  UP(clist, S.clist);
+  UP(mm_ptr, S.mm_ptr); UP(mm_child, S.mm_child);
+  UP(mm_recs, S.mm_recs); d.mm_recs_bytes = (uint32_t)(S.mm_recs.size() * sizeof(StepRec)); d.mm_np = S.mm_np;
   d.nr_mm_pass = G_.mm_pass;   // the predicted-final mismatch evaluation as a barrier-free pass over all nodes instead of a tree sweep
-  UP(flat, h->sched.flat); d.flat_bytes = (uint32_t)(h->sched.flat.size() * sizeof(double));
-  if (d.nr_init == 2) { UP(dc_recs, h->sched.dc_recs); d.dc_recs_bytes = (uint32_t)(h->sched.dc_recs.size() * sizeof(DcRec)); }
-  {  // NR scratch: factor blocks (one per node) | 2 x Sbus (one entry per node) | Vout
-    const size_t nblk = (size_t)P.n + 2;           // Sbus by node position (+ slack, + the trash node of idle steps: stays 0)
-    const size_t fb_rows = (h_lds && g_lds) ? 0 : (size_t)(P.n + 2) * NBP;   // pair rows of Bp x 16 bytes: one block per node (+ slack, trash)
-    std::vector<int32_t> sbi(P.n);
-    for (int k = 0; k < P.n; ++k) sbi[k] = k;
-    rc = alloc_nrbuf(fb_rows, nblk, sbi); if (rc) return rc;
-  }
-#undef UP
-  {   // composition of the step() launches
-    const int fi = knob_tri(cfg->fuse_inject, "MAPDN_FUSE_INJECT");
-    const bool can = !d.auto_reset && !h->inject_full;
-    if (fi == 1 && !can) { h->err = "fuse_inject = 1 needs a handle without auto_reset and without inject_full"; return MAPDN_E_INVALID; }
-    h->fuse_inject = can && fi != 2;
-    // XCD-aligned env order of the wide kernels (tree solver; the group size is the solver's envs per workgroup)
-    const int xm = knob_tri(cfg->xcd_map, "MAPDN_XCD_MAP");
-    d.xcd_lanes = (xm == 1 && (64 % d.nr_lanes) == 0) ? d.nr_lanes : 0;     // opt-in: measured a wash (profiles/r04_xcd_map_ab.txt)
-    h->overlap = knob_int(cfg->overlap_advance, "MAPDN_OVERLAP_ADVANCE") != 0;
-    if (h->overlap && d.n_fused) { h->err = "overlap_advance is not available on a net with fused buses (bus_alias)"; return MAPDN_E_INVALID; }
-    if (h->overlap) {
-      HIPCHK(h, hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-      HIPCHK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-      HIPCHK(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    }
-  }
-  return MAPDN_OK;
+  UP(flat, S.flat); d.flat_bytes = (uint32_t)(S.flat.size() * sizeof(double));
+  if (d.nr_init == 2) { UP(dc_recs, S.dc_recs); d.dc_recs_bytes = (uint32_t)(S.dc_recs.size() * sizeof(DcRec)); }
+  // NR scratch: factor blocks (one per node) | 2 x Sbus (one entry per node) | Vout
+  const size_t nblk = (size_t)P.n + 2;           // Sbus by node position (+ slack, + the trash node of idle steps: stays 0)
+  const size_t fb_rows = (G_.h_lds && G_.g_lds) ? 0 : (size_t)(P.n + 2) * NBP;   // pair rows of Bp x 16 bytes: one block per node (+ slack, trash)
+  return alloc_nrbuf(h, fb_rows, nblk);
 }
+
+#undef UP
+#undef AL
+
+static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_env_config* cfg, int32_t B, int32_t device) {
+  if (!net || !cfg) { h->err = "null netspec/config"; return MAPDN_E_INVALID; }
+  if (B < 1) { h->err = "n_envs must be >= 1"; return MAPDN_E_INVALID; }
+  if (cfg->barrier_type < 0 || cfg->barrier_type > MAPDN_BARRIER_BUMP) { h->err = "unknown voltage_barrier_type"; return MAPDN_E_INVALID; }
+  if (!cfg->use_line_weight && !cfg->use_q_weight) {   // voltage_control_env.py:616-617
+    h->err = "NotImplementedError: Please at least give one weight, either q_weight or line_weight."; return MAPDN_E_INVALID; }
+  if (cfg->episode_limit < 2) { h->err = "episode_limit must be >= 2"; return MAPDN_E_INVALID; }
+  h->cfg = *cfg;
+  h->knobs = resolve_knobs(*cfg);
+  int rc = build_plan(*net, *cfg, h->plan, h->err);
+  if (!rc) rc = choose_solver(h);
+  if (!rc) rc = validate(h, *cfg);
+  if (rc) return rc;
+  h->nr_var = (cfg->nr_init == 2 ? NR_VAR_DC : 0) | (h->plan.zip ? NR_VAR_ZIP : 0);
+  // composition of the step() launches: the PV-bus injection runs in the prologue of k_nr_tree unless the handle auto-resets (its
+  // restarting envs refresh all their loads in the injection launch), rebuilds all of Sbus on every call, or pins fuse_inject = 2
+  h->fuse_inject = h->solver == 0 && !cfg->auto_reset && !h->knobs.inject_full && h->knobs.fuse_inject != 2;
+  h->device = device;
+  std::memset(&h->d, 0, sizeof(h->d));
+  h->d.B = B; h->d.Bp = (B + 63) / 64 * 64;
+  if (device == -1) {                                            // plan only (CPU tests): no device work
+    h->host_only = true;
+    return h->solver == 0 ? settle_tree_geometry(h, h->d.Bp, 256) : MAPDN_OK;   // (an MI355X has 256 CUs)
+  }
+  int ndev = 0;
+  HIPCHK(h, hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) { h->err = "device index out of range"; return MAPDN_E_HIP; }
+  HIPCHK(h, hipSetDevice(device));
+  if ((rc = upload_topology(h)) || (rc = setup_pv_buses(h)) || (rc = setup_env_state(h)) || (rc = setup_gather_tables(h))) return rc;
+  return h->solver == 2 ? setup_dense(h) : h->solver == 1 ? setup_sparse(h) : setup_tree(h);
+}
+
+extern "C" {
+
+const char* mapdn_last_error(const mapdn_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
+
+#ifndef MAPDN_SRC_HASH
+#define MAPDN_SRC_HASH "unknown"
+#endif
+// "MAPDN_SRC_HASH=<sha256 of the sources and flags this library was built from>" (mapdn_amd/build.py): the loader compares it with the
+// sources on disk, so that a prebuilt library can never silently disagree with them
+const char* mapdn_build_info(void) { return "MAPDN_SRC_HASH=" MAPDN_SRC_HASH; }
 
 int mapdn_create(const mapdn_netspec* net, const mapdn_env_config* cfg, int32_t n_envs, int32_t device, mapdn_handle** out) {
   if (!out) { g_create_err = "null out pointer"; return MAPDN_E_INVALID; }
@@ -622,9 +642,6 @@ void mapdn_destroy(mapdn_handle* h) {
   if (!h) return;
   for (void* p : h->allocs) (void)hipFree(p);
   for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-  if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-  if (h->side) (void)hipStreamDestroy(h->side);
   delete h;
 }
 
@@ -674,10 +691,8 @@ int mapdn_set_profiles(mapdn_handle* h, const double* pv, const double* load_p, 
       if (it != h->allocs.end()) { (void)hipFree(*it); h->allocs.erase(it); }
     }
   }
-  const double* tmp;
-  int rc = dupload(h, &tmp, tab); if (rc) return rc; h->table = (double*)tmp;
-  rc = dupload(h, &tmp, stdv); if (rc) return rc; h->stdv = (double*)tmp;
-  rc = dupload(h, &tmp, smax); if (rc) return rc; h->smax = (double*)tmp;
+  int rc;
+  if ((rc = dupload(h, &h->table, tab)) || (rc = dupload(h, &h->stdv, stdv)) || (rc = dupload(h, &h->smax, smax))) return rc;
   d.table = h->table; d.stdv = h->stdv; d.smax = h->smax; d.T = T;
   h->stdv_host = stdv; h->smax_host = smax;
   h->have_profiles = true;
@@ -706,53 +721,30 @@ static void nr_launch(mapdn_handle* h, int mode, double* reward, uint8_t* term, 
 // the injection of a step() / reset() call: PV buses only when Sbus and bus_ld are known to reflect the current loads
 static void inject_launch(mapdn_handle* h, int mode, const void* actions, int dtype, int add_noise, hipStream_t st) {
   const Dev& d = h->d;
-  if (h->sbus_stale || h->inject_full) {
+  if (h->sbus_stale || h->knobs.inject_full) {
     launch_inject(d, mode, actions, dtype, d.cur_pl, d.cur_ql, d.cur_pv, nullptr, add_noise, st);
     h->sbus_stale = false;
   } else launch_inject_sgen(d, mode, actions, dtype, add_noise, st);
 }
 
 // The launches of one step(): injection (its own launch, or the prologue of k_nr_tree: fuse_inject) -> solve + reward ->
-// profile advance (-> the Sbus buffer of the next solve) + res_bus commit.  With `overlap` the profile rows, which do not
-// depend on the solve, run on the side stream beside the solver launch.
-static int step_launches(mapdn_handle* h, const void* actions, int32_t actions_dtype, int32_t add_noise, double* reward,
-                         uint8_t* terminated, double* info, hipStream_t st) {
+// profile advance (-> the Sbus buffer of the next solve) + res_bus commit.
+static void step_launches(mapdn_handle* h, const void* actions, int32_t actions_dtype, int32_t add_noise, double* reward,
+                          uint8_t* terminated, double* info, hipStream_t st) {
   const Dev& d = h->d;
-  const bool fused = h->fuse_inject && h->solver == 0 && !h->sbus_stale;
+  const bool fused = h->fuse_inject && !h->sbus_stale;
   if (!fused) inject_launch(h, MODE_STEP, actions, actions_dtype, add_noise, st);
-  if (h->overlap && !fused) {
-    // fork after the injection (it queues the row / draw the advance uses), join before the commit rows.  The side stream's
-    // profile rows write cur_pv / cur_pl / bus_ld while the solver runs: safe only because the NON-fused k_nr_tree never reads them
-    // (mapdn_create refuses overlap together with the fused prologue).  On an error between fork and join the side stream is
-    // drained and the Sbus buffers are declared stale, so that the next call rebuilds them instead of reading a half-written one.
-    auto bail = [&](const char* what, hipError_t e) {
-      (void)hipStreamSynchronize(h->side);
-      h->sbus_stale = true;
-      h->err = std::string(what) + ": " + hipGetErrorString(e);
-      return MAPDN_E_HIP;
-    };
-    hipError_t e_;
-    if ((e_ = hipEventRecord(h->ev_fork, st)) != hipSuccess) return bail("hipEventRecord(fork)", e_);
-    if ((e_ = hipStreamWaitEvent(h->side, h->ev_fork, 0)) != hipSuccess) return bail("hipStreamWaitEvent(side, fork)", e_);
-    launch_advance(d, add_noise, 1, 0, d.sb_off_alt, h->side);
-    if ((e_ = hipEventRecord(h->ev_join, h->side)) != hipSuccess) return bail("hipEventRecord(join)", e_);
-    nr_launch(h, MODE_STEP, reward, terminated, info, st);
-    if ((e_ = hipStreamWaitEvent(st, h->ev_join, 0)) != hipSuccess) return bail("hipStreamWaitEvent(join)", e_);
-    launch_commit_fused(d, st);     // (with fused buses the side stream's profile rows race with this: overlap is an experiment switch)
-    launch_advance(d, 0, 0, 1, d.sb_off_alt, st);
-  } else if (d.zip) {
+  nr_launch(h, MODE_STEP, reward, terminated, info, st, fused ? actions : nullptr, actions_dtype);
+  if (d.zip) {
     // voltage-dependent loads: the commit of a ZIP bus reads the loads the solve used (cur_pl / cur_ql), so it runs before the profile
-    // rows overwrite them (two launches; no fused buses and no overlap with ZIP loads)
-    nr_launch(h, MODE_STEP, reward, terminated, info, st, fused ? actions : nullptr, actions_dtype);
+    // rows overwrite them (two launches; no fused buses with ZIP loads)
     launch_advance(d, 0, 0, 1, d.sb_off_alt, st);
     launch_advance(d, add_noise, 1, 0, d.sb_off_alt, st);
   } else {
-    nr_launch(h, MODE_STEP, reward, terminated, info, st, fused ? actions : nullptr, actions_dtype);
     launch_commit_fused(d, st);     // (only with fused buses: their own p_mw / q_mvar, before the element tables advance)
     launch_advance(d, add_noise, 1, 1, d.sb_off_alt, st);   // next profile row (-> the Sbus buffer of the next solve) + res_bus commit
   }
   std::swap(h->d.sb_off, h->d.sb_off_alt);
-  return MAPDN_OK;
 }
 
 int mapdn_reset(mapdn_handle* h, const int64_t* start_rows, int32_t add_noise, int32_t max_tries, void* stream) try {
@@ -785,9 +777,7 @@ int mapdn_step(mapdn_handle* h, const void* actions, int32_t actions_dtype, int3
   NEEDDEV(h);
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  const Dev& d = h->d;
-  { const int rc = step_launches(h, actions, actions_dtype, add_noise, reward, terminated, info, st); if (rc) return rc; }
-  (void)d;
+  step_launches(h, actions, actions_dtype, add_noise, reward, terminated, info, st);
   HIPCHK(h, hipGetLastError());
   return MAPDN_OK;
 } MAPDN_CATCH(h)
@@ -804,7 +794,7 @@ int mapdn_step_obs(mapdn_handle* h, const void* actions, int32_t actions_dtype, 
   hipStream_t st = (hipStream_t)stream;
   const Dev& d = h->d;
   const int C = h->plan.n_agents * h->plan.obs_size;
-  { const int rc = step_launches(h, actions, actions_dtype, add_noise, reward, terminated, info, st); if (rc) return rc; }
+  step_launches(h, actions, actions_dtype, add_noise, reward, terminated, info, st);
   launch_gather(d, d.gbuf, h->obs_rows, h->obs_scale, 1.0, h->obs_xptr, h->obs_xrow, obs, obs_dtype, C, st);
   HIPCHK(h, hipGetLastError());
   return MAPDN_OK;
@@ -941,11 +931,9 @@ int mapdn_get_obs_index(const mapdn_handle* h, int32_t* kind, int32_t* index) tr
 int mapdn_get_nr_geometry(const mapdn_handle* h, int32_t* out) try {
   if (!h || !out) return MAPDN_E_INVALID;
   const mapdn_handle::Geo& g = h->geo;
-  const bool fuse_possible = h->solver == 0 && !h->cfg.auto_reset && !knob_int(h->cfg.inject_full, "MAPDN_INJECT_FULL") &&
-                             knob_tri(h->cfg.fuse_inject, "MAPDN_FUSE_INJECT") != 2;
   const int32_t v[20] = {h->solver, g.W, g.L, g.lean, g.rows, g.h_lds, g.g_lds, g.rec_lds, g.flat_lds, g.line_lds, g.mm_pass,
                          (int32_t)h->lds_bytes, (int32_t)g.wgs, g.resident, g.rounds, (int32_t)std::min(g.model_ns, 2.0e9),
-                         (h->host_only ? fuse_possible : h->fuse_inject) ? 1 : 0, (int32_t)h->plan.fused_obus.size(), h->plan.nb, h->cfg.nr_init};
+                         h->fuse_inject ? 1 : 0, (int32_t)h->plan.fused_obus.size(), h->plan.nb, h->cfg.nr_init};
   std::memcpy(out, v, sizeof(v));
   if (h->solver == 1) out[2] = h->sp_lanes;
   return MAPDN_OK;

@@ -175,7 +175,7 @@ k_nr_dense(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ t
   double sbr = 0.0, sbi = 0.0;
   int p0 = 0, p1 = 0;
   if (bus) {
-    const double2 sb = ((const double2*)((const char*)d.nrbuf + d.sb_off))[(size_t)d.sb_index[tid] * d.Bp + e];
+    const double2 sb = ((const double2*)((const char*)d.nrbuf + d.sb_off))[(size_t)tid * d.Bp + e];
     sbr = sb.x; sbi = sb.y;
     p0 = yptr[tid]; p1 = yptr[tid + 1];
   }

@@ -130,8 +130,8 @@ k_inject(Dev d, int mode, const AT* __restrict__ actions, const double* __restri
     }
     P -= p * d.sgen_scale[j]; Q -= q * d.sgen_scale[j];
   }
-  if (k < d.n) {   // scheduled injection as an (re, im) pair, stored in the order the NR workers consume it
-    const size_t o = (size_t)d.sb_index[k] * d.Bp + e;
+  if (k < d.n) {   // scheduled injection as an (re, im) pair, stored by node position
+    const size_t o = (size_t)k * d.Bp + e;
     const double2 v = make_double2(-P / d.sn, -Q / d.sn);
     ((double2*)((char*)d.nrbuf + d.sb_off))[o] = v;
     if (mode != MODE_SOLVE) ((double2*)((char*)d.nrbuf + d.sb_off_alt))[o] = v;   // both Sbus buffers (see k_advance) are current afterwards
@@ -189,7 +189,7 @@ k_inject_sgen(Dev d, int mode, const AT* __restrict__ actions, int add_noise) {
     if (ar || k >= d.n) return;
     double Ps, Qs;
     stored_load_sum(k, Ps, Qs);
-    sbp[(size_t)d.sb_index[k] * d.Bp] = make_double2(-Ps / d.sn, -Qs / d.sn);
+    sbp[(size_t)k * d.Bp] = make_double2(-Ps / d.sn, -Qs / d.sn);
     return;
   }
   double2* const bl = (double2*)d.bus_ld + (size_t)jb * d.Bp + e;
@@ -214,8 +214,8 @@ k_inject_sgen(Dev d, int mode, const AT* __restrict__ actions, int add_noise) {
       load_sum(kk, Ps, Qs);
       if (kk < d.n) {                             // a restarting env is not advanced by this call's k_advance: both Sbus buffers
         const double2 v = make_double2(-Ps / d.sn, -Qs / d.sn);
-        sbp[(size_t)d.sb_index[kk] * d.Bp] = v;
-        ((double2*)((char*)d.nrbuf + d.sb_off_alt))[(size_t)d.sb_index[kk] * d.Bp + e] = v;
+        sbp[(size_t)kk * d.Bp] = v;
+        ((double2*)((char*)d.nrbuf + d.sb_off_alt))[(size_t)kk * d.Bp + e] = v;
       }
     }
   } else if (d.load_ptr[k + 1] - d.load_ptr[k] > 1) stored_load_sum(k, P, Q);
@@ -239,7 +239,7 @@ k_inject_sgen(Dev d, int mode, const AT* __restrict__ actions, int add_noise) {
     d.q_new[o] = q;
     P -= p * d.sgen_scale[j]; Q -= q * d.sgen_scale[j];
   }
-  if (k < d.n) sbp[(size_t)d.sb_index[k] * d.Bp] = make_double2(-P / d.sn, -Q / d.sn);
+  if (k < d.n) sbp[(size_t)k * d.Bp] = make_double2(-P / d.sn, -Q / d.sn);
 }
 
 // =================================================================================================
@@ -310,7 +310,7 @@ __device__ __forceinline__ void commit_bus(const Dev& d, int b_, int e, size_t S
   const int k = d.pos_of_obus[b_];               // elimination position of its node, n == slack
   if (k < d.n) {
     const double* vo = d.nrbuf + ((size_t)d.r_vout + (size_t)VOF * k) * S + e;
-    const double2 sb = ((const double2*)((const char*)d.nrbuf + d.sb_off))[(size_t)d.sb_index[k] * S + e];
+    const double2 sb = ((const double2*)((const char*)d.nrbuf + d.sb_off))[(size_t)k * S + e];
     const double ek = vo[(size_t)VO_E * S], fk = vo[(size_t)VO_F * S];
     v = sqrt(ek * ek + fk * fk);
     va = atan2(fk, ek);
@@ -398,8 +398,8 @@ __device__ __forceinline__ void advance_load_pair(const Dev& d, int e, int b, in
 
 __device__ __forceinline__ void advance_body(const Dev& d, int add_noise, int do_profiles, int do_commit, uint32_t sb_write_off,
                                              unsigned blk_x, unsigned blk_y) {
-  const int e = d.xcd_lanes ? xcd_env(blk_x, threadIdx.x, 256u, (unsigned)d.xcd_lanes, (unsigned)(d.Bp / d.xcd_lanes)) : (int)(blk_x * 256u + threadIdx.x);
-  if (e < 0 || e >= d.B) return;
+  const int e = (int)(blk_x * 256u + threadIdx.x);
+  if (e >= d.B) return;
   const int npv = (d.ns + 1) >> 1, npl = (d.nl + 1) >> 1;
   const int npairs = do_profiles ? npv + npl : 0;
   const size_t S = (size_t)d.Bp;
@@ -468,10 +468,10 @@ __global__ void __launch_bounds__(256) k_commit_fused(Dev d) {
 //                both the env-minor reads and the env-major writes are coalesced.
 // =================================================================================================
 #define GATHER_HAS_EXTRA 0x40000000   // flag bit in a row descriptor: the column has add-back rows (x_ptr/x_row)
-template <typename T, bool XM>
+template <typename T>
 __device__ __forceinline__ void gather_body(const double* __restrict__ base, const int32_t* rows_g, const double* scales_g,
                                             double scale_all, const int32_t* x_ptr_g, const int32_t* x_row_g,
-                                            T* __restrict__ out, int C, int B, int Bp, unsigned blk_x, unsigned blk_y, unsigned grd_x, unsigned grd_y, int xl) {
+                                            T* __restrict__ out, int C, int B, int Bp, unsigned blk_x, unsigned blk_y, unsigned grd_x, unsigned grd_y) {
   __shared__ T tile[64][65];                      // output-typed tile: 16.6 KB for f32 -> 8 workgroups per CU
   // descriptors are wave-uniform (a wave handles whole columns): read them through the constant
   // address space -> s_load on the scalar unit, no VMEM round trip ahead of the data loads
@@ -489,9 +489,7 @@ __device__ __forceinline__ void gather_body(const double* __restrict__ base, con
   }
   const int c0 = (int)bx * 64, e0 = (int)by * 64;
   const int tx = threadIdx.x & 63, ty = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // the 64 envs of this tile: consecutive, or (xl: XCD-aligned order) the tile's groups of xl envs of XCD by % 8
-  auto env_of = [&](int r) { if constexpr (XM) return xcd_env(by, (unsigned)r, 64u, (unsigned)xl, (unsigned)(Bp / xl)); else return e0 + r; };
-  const int etx = max(env_of(tx), 0);                // (a slot beyond the batch reads env 0 and is never written)
+  const int etx = e0 + tx;                       // (a pad env beyond the batch is read and never written)
   int rw[16]; double sc[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) {                 // all descriptor reads first, then the data
@@ -518,8 +516,8 @@ __device__ __forceinline__ void gather_body(const double* __restrict__ base, con
   const bool vec = (C % 4) == 0 && ((unsigned long long)out % (sizeof(T) * 4)) == 0;
 #pragma unroll
   for (int pass = 0; pass < 4; ++pass) {
-    const int r = er + 16 * pass, e = env_of(r), c = c0 + q4;
-    if (e < 0 || e >= B || c >= C) continue;
+    const int r = er + 16 * pass, e = e0 + r, c = c0 + q4;
+    if (e >= B || c >= C) continue;
     T* o = out + (size_t)e * C + c;
     if (vec) {                                   // C % 4 == 0 and c % 4 == 0: the 4 columns exist and are aligned
       struct alignas(sizeof(T) * 4) V4 { T a, b, c, d; };
@@ -531,12 +529,12 @@ __device__ __forceinline__ void gather_body(const double* __restrict__ base, con
   }
 }
 
-template <typename T, bool XM>
+template <typename T>
 __global__ void __launch_bounds__(256)
 k_gather(const double* __restrict__ base, const int32_t* rows_g, const double* scales_g,
          double scale_all, const int32_t* x_ptr_g, const int32_t* x_row_g,
-         T* __restrict__ out, int C, int B, int Bp, int xl) {
-  gather_body<T, XM>(base, rows_g, scales_g, scale_all, x_ptr_g, x_row_g, out, C, B, Bp, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, xl);
+         T* __restrict__ out, int C, int B, int Bp) {
+  gather_body<T>(base, rows_g, scales_g, scale_all, x_ptr_g, x_row_g, out, C, B, Bp, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
 }
 
 // env-major [B, n] -> env-minor [n][Bp] (zero-fills the pad lanes)
@@ -700,8 +698,7 @@ void launch_reset_begin(const Dev& d, const int64_t* start_rows, int first_try, 
 void launch_advance(const Dev& d, int add_noise, int do_profiles, int do_commit, uint32_t sb_write_off, hipStream_t st) {
   const int rows = (do_profiles ? ((d.ns + 1) >> 1) + ((d.nl + 1) >> 1) : 0) + (do_commit ? d.nbo : 0);
   if (rows == 0) return;
-  const unsigned gx = d.xcd_lanes ? xcd_blocks((unsigned)d.Bp, 256u, (unsigned)d.xcd_lanes) : (unsigned)((d.B + 255) / 256);
-  hipLaunchKernelGGL(k_advance, dim3(gx, rows), dim3(256), 0, st, d, add_noise, do_profiles, do_commit, sb_write_off);
+  hipLaunchKernelGGL(k_advance, dim3((d.B + 255) / 256, rows), dim3(256), 0, st, d, add_noise, do_profiles, do_commit, sb_write_off);
 }
 void launch_commit_fused(const Dev& d, hipStream_t st) {
   if (d.n_fused > 0) hipLaunchKernelGGL(k_commit_fused, dim3((d.B + 255) / 256, d.n_fused), dim3(256), 0, st, d);
@@ -713,15 +710,9 @@ void launch_inject_sgen(const Dev& d, int mode, const void* actions, int dtype, 
 }
 void launch_gather(const Dev& d, const double* base, const int32_t* rows, const double* scales, double scale_all,
                    const int32_t* x_ptr, const int32_t* x_row, void* out, int dtype, int C, hipStream_t st) {
-  const int xl = d.xcd_lanes;
-  dim3 grid((C + 63) / 64, xl ? xcd_blocks((unsigned)d.Bp, 64u, (unsigned)xl) : (unsigned)(d.Bp / 64));
-  if (dtype == MAPDN_F32) {
-    if (xl) hipLaunchKernelGGL((k_gather<float, true>), grid, dim3(256), 0, st, base, rows, scales, scale_all, x_ptr, x_row, (float*)out, C, d.B, d.Bp, xl);
-    else hipLaunchKernelGGL((k_gather<float, false>), grid, dim3(256), 0, st, base, rows, scales, scale_all, x_ptr, x_row, (float*)out, C, d.B, d.Bp, 0);
-  } else {
-    if (xl) hipLaunchKernelGGL((k_gather<double, true>), grid, dim3(256), 0, st, base, rows, scales, scale_all, x_ptr, x_row, (double*)out, C, d.B, d.Bp, xl);
-    else hipLaunchKernelGGL((k_gather<double, false>), grid, dim3(256), 0, st, base, rows, scales, scale_all, x_ptr, x_row, (double*)out, C, d.B, d.Bp, 0);
-  }
+  const dim3 grid((C + 63) / 64, d.Bp / 64);
+  if (dtype == MAPDN_F32) hipLaunchKernelGGL(k_gather<float>, grid, dim3(256), 0, st, base, rows, scales, scale_all, x_ptr, x_row, (float*)out, C, d.B, d.Bp);
+  else hipLaunchKernelGGL(k_gather<double>, grid, dim3(256), 0, st, base, rows, scales, scale_all, x_ptr, x_row, (double*)out, C, d.B, d.Bp);
 }
 void launch_to_envminor(const Dev& d, const double* src, double* dst, int n, hipStream_t st) {
   hipLaunchKernelGGL(k_to_envminor, dim3((n + 63) / 64, d.Bp / 64), dim3(256), 0, st, src, dst, n, d.B, d.Bp);

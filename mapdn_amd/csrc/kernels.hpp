@@ -15,9 +15,9 @@ enum { STREAM_PV = 0, STREAM_LOAD_P = 1, STREAM_LOAD_Q = 2, STREAM_ACTION = 3, S
 //                                step works on): the LU factors (G0,G1) (G2,G3) (h0,h1) written in the forward sweep and
 //                                read back in the backward sweep — only for the factors that do not fit in LDS
 //                                (nr_h_lds / nr_g_lds)
-//   Sbus           2 x [nblk] pair rows   (Re, Im) of the scheduled injection, stored in SCHEDULE order (k_inject writes
-//                                entry sb_index[k]; the NR workers prefetch theirs by (worker,row)); idle steps stay 0;
-//                                two buffers, flipped by the host after every step (k_advance fills the next one)
+//   Sbus           2 x [nblk] pair rows   (Re, Im) of the scheduled injection, by node position k (n, n+1: slack and
+//                                trash node, stay 0); two buffers, flipped by the host after every step (k_advance fills
+//                                the next one)
 //   Vout           [n+1][4] rows of Bp doubles   per position (n == slack): e f |V| angle — the solution (k_nr_tree)
 // Voltages and everything that crosses workers live in LDS during the solve.
 enum { NB_G01 = 0, NB_G23, NB_H, NBP };
@@ -63,7 +63,6 @@ struct Dev {
   // ---- NR scratch (see NB_* / VO_*): row offsets of the Sbus and Vout regions
   double* nrbuf; uint32_t nrbuf_bytes; uint32_t sb_off, r_vout;   // sb_off: byte offset of the Sbus region the solve reads
   uint32_t sb_off_alt;                                            // ... of the other Sbus buffer (double-buffered, see k_advance)
-  const int32_t* sb_index;                                           // [n] Sbus entry (schedule step) of elimination position k
   int32_t* iters; uint8_t* conv;
   // ---- NR schedule (k_nr_tree): W waves per workgroup, L envs per workgroup (64/L lane-group workers per wave), R rows
   int32_t nr_waves, nr_lanes, nr_rows, nr_cslots, nr_xslots, nr_nclist, nr_h_lds, nr_g_lds, nr_line_lds, nr_rec_lds, nr_flat_lds;
@@ -85,11 +84,6 @@ struct Dev {
   int32_t dense, dn_N, dn_lda;
   double* dn_A;              // k_nr_dense beyond 65 buses: per-env slabs [Bp][dn_N][dn_lda] of global memory for the Jacobian (else nullptr: LDS)
   const int32_t *gy_ptr, *gy_col; const double* gy_val;
-  // ---- XCD-aligned env order of the wide kernels (0 = off: block b serves envs 256 b ...): a k_nr_tree workgroup i serves envs
-  // [L i, L i + L) and lands on XCD i % 8 (observed), so env e "lives" on XCD (e / L) % 8; with xcd_lanes = L the wide kernels give
-  // block b the L-env groups of XCD b % 8, and what one kernel writes the next reads from the same XCD's L2 (the L2s of the eight XCDs
-  // are not coherent with each other: a line written on another XCD comes back from memory)
-  int32_t xcd_lanes;
   // ---- bus fusion (plan.hpp): original buses, nbo of them, vs electrical nodes (nb); all nullptr / 0 / nbo == nb without fusion
   int32_t nbo, n_fused, n_alias, n_slack_group;
   const int32_t *pos_of_obus, *cm_kind, *fused_obus, *ob_load_ptr, *ob_load_idx, *ob_sgen_ptr, *ob_sgen_idx, *slack_group, *alias_pos;
@@ -146,14 +140,6 @@ int nr_dense_prepare(const Dev& d);
 void launch_nr_dense(const Dev& d, int mode, double* reward, uint8_t* term, double* info, hipStream_t st);
 int dense_solve_debug(const double* A, const double* b, double* x, int n, int batch, hipStream_t st);
 void launch_reset_begin(const Dev& d, const int64_t* start_rows, int first_try, hipStream_t st);
-// slot t of block `blk` (T slots per block) of a wide kernel -> env (XCD-aligned order, see Dev::xcd_lanes); -1 beyond the batch
-__host__ __device__ static inline int xcd_env(unsigned blk, unsigned t, unsigned T, unsigned L, unsigned NG) {
-  const unsigned c = blk & 7u, chunk = blk >> 3, gpb = T / L;
-  const unsigned gid = (chunk * gpb + t / L) * 8u + c;
-  return gid < NG ? (int)(gid * L + t % L) : -1;
-}
-// blocks of T env slots that cover a padded batch of Bp envs in that order (a multiple of 8)
-static inline unsigned xcd_blocks(unsigned Bp, unsigned T, unsigned L) { const unsigned ng = Bp / L, gpb = T / L; return 8u * (((ng + 7u) / 8u + gpb - 1u) / gpb); }
 void launch_advance(const Dev& d, int add_noise, int do_profiles, int do_commit, uint32_t sb_write_off, hipStream_t st);
 // res_bus p_mw / q_mvar of the buses of fused groups (their OWN elements), after the solve and before the profile advance
 void launch_commit_fused(const Dev& d, hipStream_t st);

@@ -381,3 +381,44 @@ def test_tolerance_options(lib):
     for tuning, ok in ((None, True), (dict(tolerance_is_pu=1), True), (dict(tolerance_mva=1e-6), True), (dict(tolerance_mva=-1.0), False)):
         rc, g = _geometry(lib, net, 64, tuning)
         assert (rc == 0) == ok, g
+
+
+def test_step_composition_switches_are_validated_for_every_solver(lib, monkeypatch):
+    """fuse_inject = 1 exists on the tree solver only and needs a handle without auto_reset and inject_full; overlap_advance and
+    xcd_map were removed and are refused on every solver.  mapdn_create checks all of it before the device set-up, so a host-only
+    handle refuses what a device handle refuses.  The geometry export reports the fuse_inject the handle was created with, whatever
+    the environment says afterwards."""
+    for v in ("MAPDN_FUSE_INJECT", "MAPDN_INJECT_FULL", "MAPDN_NR_SPARSE", "MAPDN_NR_DENSE"):
+        monkeypatch.delenv(v, raising=False)
+    net, _ = make_case("case33")
+
+    def create(tuning, **args):
+        cn, keep = _lib.make_cnetspec(net)
+        cc = _lib.make_cconfig(dict(ARGS, **args), 0, tuning)
+        h = C.c_void_p()
+        rc = lib.mapdn_create(C.byref(cn), C.byref(cc), 8, -1, C.byref(h))
+        return rc, h, "" if rc == 0 else lib.mapdn_last_error(None).decode()
+
+    for solver in ("tree", "sparse", "dense"):
+        for removed in ("overlap_advance", "xcd_map"):
+            rc, _, msg = create(dict(nr_solver=solver, **{removed: 1}))
+            assert rc == -1 and removed in msg and "removed" in msg, (solver, msg)
+        rc, h, msg = create(dict(nr_solver=solver, fuse_inject=1))
+        if solver == "tree":
+            assert rc == 0, msg
+            assert _lib.nr_geometry(h)["fuse_inject"] == 1
+            lib.mapdn_destroy(h)
+        else:
+            assert rc == -1 and "tree solver only" in msg, (solver, msg)
+    rc, _, msg = create(dict(fuse_inject=1), auto_reset=True)
+    assert rc == -1 and "auto_reset" in msg, msg
+    rc, _, msg = create(dict(fuse_inject=1, inject_full=1))
+    assert rc == -1 and "inject_full" in msg, msg
+    # what the handle was created with, not what the environment says now
+    for tuning, env, want in ((dict(fuse_inject=2), "2", 0), (None, "0", 1)):
+        rc, h, msg = create(tuning)
+        assert rc == 0, msg
+        monkeypatch.setenv("MAPDN_FUSE_INJECT", env)
+        assert _lib.nr_geometry(h)["fuse_inject"] == want
+        lib.mapdn_destroy(h)
+        monkeypatch.delenv("MAPDN_FUSE_INJECT")

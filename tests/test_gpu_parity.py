@@ -1071,42 +1071,3 @@ def test_tolerance_options_follow_the_oracle_on_a_net_with_sn_mva_100(tuning):
         assert np.abs(vm[e] - r.vm_pu).max() < (1e-9 if "tolerance_mva" not in tuning else 1e-6)
         its.add(int(it[e]))
     assert its
-
-
-@pytest.mark.parametrize("case,B", [("case141", 300), ("case322", 70)])
-def test_xcd_aligned_env_order_changes_nothing(case, B):
-    """mapdn_env_config.xcd_map = 1: the wide kernels walk the envs in XCD-aligned order (a permutation of which thread serves
-    which env) — bit-identical steps, observations, state and result tables, batch sizes that are not multiples of anything"""
-    net, prof, a = make(case, B, tuning=dict(xcd_map=1), episode_limit=6, auto_reset=True)
-    _, _, b = make(case, B, episode_limit=6, auto_reset=True)
-    oa, sa = a.reset(); ob, sb = b.reset()
-    assert torch.equal(oa, ob) and torch.equal(sa, sb)
-    gen = torch.Generator(device="cuda:0"); gen.manual_seed(3)
-    for t in range(8):
-        act = (torch.rand(B, net.n_sgen, device="cuda:0", generator=gen, dtype=torch.float64) * 2 - 1) * SCALE[case]
-        ra, ta, ia = a.step(act); rb, tb, ib = b.step(act)
-        assert torch.equal(ra, rb) and torch.equal(ta, tb) and torch.equal(ia, ib)
-        assert torch.equal(a.get_obs(), b.get_obs()) and torch.equal(a.get_state(), b.get_state())
-        fa, fb = a.results(), b.results()
-        assert all(torch.equal(fa[k], fb[k]) for k in fa)
-    a.close(); b.close()
-
-
-def test_step_composition_switches_are_validated_for_every_solver():
-    """fuse_inject = 1 / overlap_advance / xcd_map exist on the tree solver only and used to be ignored silently on the
-    general solvers (their set-up returned before the check); overlap_advance was also a silent no-op beside the fused prologue."""
-    from mapdn_amd._lib import MapdnError
-    net, prof = make_case("case33")
-    for bad in (dict(nr_solver="sparse", fuse_inject=1), dict(nr_solver="dense", overlap_advance=1), dict(nr_solver="sparse", xcd_map=1)):
-        with pytest.raises(MapdnError, match="tree solver only"):
-            VoltageControlBatch(net, prof, args_for("case33"), n_envs=8, device="cuda:0", tuning=bad)
-    with pytest.raises(MapdnError, match="fuse_inject = 2"):
-        VoltageControlBatch(net, prof, args_for("case33"), n_envs=8, device="cuda:0", tuning=dict(overlap_advance=1))
-    a = VoltageControlBatch(net, prof, args_for("case33"), n_envs=8, device="cuda:0", obs_dtype=torch.float64, tuning=dict(overlap_advance=1, fuse_inject=2))
-    b = VoltageControlBatch(net, prof, args_for("case33"), n_envs=8, device="cuda:0", obs_dtype=torch.float64)
-    oa, _ = a.reset(); ob, _ = b.reset()
-    act = torch.full((8, net.n_sgen), 0.3, device="cuda:0", dtype=torch.float64)
-    for _ in range(3):
-        ra, ta, ia = a.step(act); rb, tb, ib = b.step(act)
-        assert torch.equal(ra, rb) and torch.equal(a.get_obs(), b.get_obs())
-    a.close(); b.close()
