@@ -474,6 +474,13 @@ int mapdn_stats(mapdn_handle* h, int64_t* reset_failures, double* mean_iters, in
 int mapdn_nr_timing(mapdn_handle* h, int32_t enable);
 int mapdn_nr_time_ms(mapdn_handle* h, double* total_ms, int64_t* launches);
 
+/* Host-side export of the power-flow kernel instantiation this handle launches (coverage tests; also for device == -1 handles):
+ * out[8] = solver, then by solver
+ *   0 k_nr_tree<W, L, HL, GL, RES, DC, ZIP>: W, L, HL, GL, RES, DC, ZIP (RES 0: the generic residency body; csrc/nr_inst_list.hpp)
+ *   1 k_nr_sparse<L, DC>:                    L, DC, ZIP (ZIP is decided at run time), 0, 0, 0, 0
+ *   2 k_nr_dense<W, GA>:                     W, GA (the Jacobian in global memory), 0, 0, 0, 0, 0 */
+int mapdn_get_nr_kernel(const mapdn_handle* h, int32_t* out8);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,7 @@ EXPORTS = (
     "mapdn_critic_head_forward", "mapdn_critic_head_scratch_floats", "mapdn_critic_head_backward", "mapdn_critic_head_backward_dot", "mapdn_critic_head_mse", "mapdn_get_profile_stats",
     "mapdn_explore_actions", "mapdn_rollout_stats", "mapdn_copy_segments",
     "mapdn_policy_forward_train", "mapdn_policy_backward", "mapdn_policy_backward_scratch_floats", "mapdn_get_dc_angles",
+    "mapdn_get_nr_kernel",
 )
 
 _pd = C.POINTER(C.c_double)
@@ -174,6 +175,7 @@ def load():
     lib.mapdn_get_flat_factors.argtypes = [vp, _pd, _pi]
     lib.mapdn_get_dc_angles.argtypes = [vp, _pd, _pd]
     lib.mapdn_get_nr_geometry.argtypes = [vp, _pi]
+    lib.mapdn_get_nr_kernel.argtypes = [vp, _pi]
     lib.mapdn_debug_stream.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp]
     lib.mapdn_get_sparse_program.argtypes = [vp, C.c_int32, _pi, _pi, _pi, _pi]
     lib.mapdn_policy_forward.argtypes = [vp] * 14 + [C.c_int32] * 4 + [C.c_float, vp]
@@ -314,3 +316,15 @@ def nr_geometry(handle) -> dict:
     out = (C.c_int32 * 20)()
     check(load().mapdn_get_nr_geometry(handle, out), handle)
     return dict(zip(GEOMETRY_KEYS, [int(x) for x in out]))
+
+
+NR_KERNEL_KEYS = {0: ("W", "L", "HL", "GL", "RES", "DC", "ZIP"), 1: ("L", "DC", "ZIP"), 2: ("W", "GA")}
+
+
+def nr_kernel(handle) -> dict:
+    """the power-flow kernel instantiation this handle launches (mapdn_get_nr_kernel): solver 0 k_nr_tree<W, L, HL, GL, RES, DC, ZIP>,
+    1 k_nr_sparse<L, DC> (+ the run-time ZIP flag), 2 k_nr_dense<W, GA>"""
+    out = (C.c_int32 * 8)()
+    check(load().mapdn_get_nr_kernel(handle, out), handle)
+    solver = int(out[0])
+    return dict(solver=solver, **{k: int(out[1 + i]) for i, k in enumerate(NR_KERNEL_KEYS[solver])})

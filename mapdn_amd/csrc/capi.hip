@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "nr_inst_list.hpp"
 #include "colstats.hpp"
 #include "plan.hpp"
 
@@ -312,6 +313,36 @@ static int validate(mapdn_handle* h, const mapdn_env_config& c) {
   return MAPDN_OK;
 }
 
+// The host part of the general solvers' set-up, for host-only and device handles alike (no device calls): k_nr_sparse's envs per
+// workgroup and its elimination program, k_nr_dense's Jacobian order.  What it settles is what mapdn_get_nr_kernel reports.
+static int settle_general_solver(mapdn_handle* h) {
+  const Plan& P = h->plan;
+  Dev& d = h->d;
+  if (h->solver == 2) { d.dn_N = (2 * P.n + 15) / 16 * 16; d.dn_lda = d.dn_N + 2; return MAPDN_OK; }
+  if (h->solver != 1) return MAPDN_OK;
+  if (h->knobs.sp_lanes) h->sp_lanes = h->knobs.sp_lanes;      // pinned envs per workgroup (16 / 8 / 4 / 2)
+  else {
+    // Envs per (one-wave) workgroup: fewer envs = more sub-lanes per env = fewer phases, and a smaller LDS tile = more
+    // resident waves per CU to hide each other's LDS latency.  Score = envs in flight per CU / length of the per-iteration
+    // instruction stream (phases + assembly entries); measured on case33 / case141 / case322 with tie lines closed
+    // (profiles/r02_sparse_lanes_sweep.txt): the score ranks the four geometries in the measured order.
+    double best = -1.0;
+    for (int l : {16, 8, 4, 2}) {
+      SparseProg g;
+      sparse_program(P, 64 / l, g);
+      const size_t lds = nr_sparse_lds_bytes(P.n, g.n_blocks, l);
+      if (lds > CU_LDS) continue;
+      const double waves = (double)std::min<size_t>(CU_LDS / lds, 8);
+      const double score = waves * l / ((double)g.n_phases + 0.5 * g.rows_per_sub * g.max_nnz);
+      if (score > best) { best = score; h->sp_lanes = l; }
+    }
+  }
+  sparse_program(P, 64 / h->sp_lanes, h->sprog);
+  h->lds_bytes = nr_sparse_lds_bytes(P.n, h->sprog.n_blocks, h->sp_lanes);
+  if (h->lds_bytes > CU_LDS) { h->err = "sp_lanes (MAPDN_SP_LANES): does not fit in LDS"; return MAPDN_E_INVALID; }
+  return MAPDN_OK;
+}
+
 #define UP(field, vec) do { if (const int rc_ = dupload(h, &d.field, vec)) return rc_; } while (0)
 #define AL(field, rows) do { if (const int rc_ = dalloc(h, &d.field, (size_t)(rows) * d.Bp)) return rc_; } while (0)
 
@@ -497,8 +528,8 @@ static int alloc_nrbuf(mapdn_handle* h, size_t fb_rows, size_t nblk) {
 static int setup_dense(mapdn_handle* h) {
   const Plan& P = h->plan;
   Dev& d = h->d;
-  d.dense = 1; d.dn_N = (2 * P.n + 15) / 16 * 16; d.dn_lda = d.dn_N + 2;
-  if (d.dn_N > 128) {                            // beyond 65 buses the Jacobian of every env lives in a slab of global memory
+  d.dense = 1;                                   // (dn_N, dn_lda: settle_general_solver)
+  if (nr_dense_ga(d.dn_N)) {                     // beyond 65 buses the Jacobian of every env lives in a slab of global memory
     const size_t per_env = (size_t)d.dn_N * d.dn_lda;
     if (const int rc = dalloc(h, &d.dn_A, per_env * d.Bp)) return rc;
   }
@@ -509,30 +540,11 @@ static int setup_dense(mapdn_handle* h) {
   return MAPDN_OK;
 }
 
-// k_nr_sparse (sparse.hip): host-compiled block elimination program
+// k_nr_sparse (sparse.hip): host-compiled block elimination program (settle_general_solver)
 static int setup_sparse(mapdn_handle* h) {
   const Plan& P = h->plan;
   Dev& d = h->d;
-  if (h->knobs.sp_lanes) h->sp_lanes = h->knobs.sp_lanes;      // pinned envs per workgroup (16 / 8 / 4 / 2)
-  else {
-    // Envs per (one-wave) workgroup: fewer envs = more sub-lanes per env = fewer phases, and a smaller LDS tile = more
-    // resident waves per CU to hide each other's LDS latency.  Score = envs in flight per CU / length of the per-iteration
-    // instruction stream (phases + assembly entries); measured on case33 / case141 / case322 with tie lines closed
-    // (profiles/r02_sparse_lanes_sweep.txt): the score ranks the four geometries in the measured order.
-    double best = -1.0;
-    for (int l : {16, 8, 4, 2}) {
-      SparseProg g;
-      sparse_program(P, 64 / l, g);
-      const size_t lds = nr_sparse_lds_bytes(P.n, g.n_blocks, l);
-      if (lds > CU_LDS) continue;
-      const double waves = (double)std::min<size_t>(CU_LDS / lds, 8);
-      const double score = waves * l / ((double)g.n_phases + 0.5 * g.rows_per_sub * g.max_nnz);
-      if (score > best) { best = score; h->sp_lanes = l; }
-    }
-  }
-  sparse_program(P, 64 / h->sp_lanes, h->sprog);
   const SparseProg& G = h->sprog;
-  if (nr_sparse_lds_bytes(P.n, G.n_blocks, h->sp_lanes) > CU_LDS) { h->err = "sp_lanes (MAPDN_SP_LANES): does not fit in LDS"; return MAPDN_E_INVALID; }
   d.sparse = 1; d.sp_lanes = h->sp_lanes; d.sp_blocks = G.n_blocks; d.sp_fill = (int32_t)G.fill_slots.size();
   d.sp_phases = G.n_phases; d.sp_rows_per_sub = G.rows_per_sub; d.sp_max_nnz = G.max_nnz;
   UP(sp_ops, G.ops); d.sp_ops_bytes = (uint32_t)(G.ops.size() * sizeof(SpOp));
@@ -540,7 +552,6 @@ static int setup_sparse(mapdn_handle* h) {
   { std::vector<int32_t> fs(G.fill_slots); if (fs.empty()) fs.push_back(G.n_blocks - 1); UP(sp_fill_slots, fs); }
   if (const int rc = alloc_nrbuf(h, 0, (size_t)P.n)) return rc;
   if (nr_sparse_prepare(h->sp_lanes) != 0) { (void)hipGetLastError(); h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for k_nr_sparse"; return MAPDN_E_HIP; }
-  h->lds_bytes = nr_sparse_lds_bytes(P.n, G.n_blocks, h->sp_lanes);
   return MAPDN_OK;
 }
 
@@ -599,6 +610,7 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
   h->device = device;
   std::memset(&h->d, 0, sizeof(h->d));
   h->d.B = B; h->d.Bp = (B + 63) / 64 * 64;
+  if ((rc = settle_general_solver(h))) return rc;
   if (device == -1) {                                            // plan only (CPU tests): no device work
     h->host_only = true;
     return h->solver == 0 ? settle_tree_geometry(h, h->d.Bp, 256) : MAPDN_OK;   // (an MI355X has 256 CUs)
@@ -936,6 +948,26 @@ int mapdn_get_nr_geometry(const mapdn_handle* h, int32_t* out) try {
                          h->fuse_inject ? 1 : 0, (int32_t)h->plan.fused_obus.size(), h->plan.nb, h->cfg.nr_init};
   std::memcpy(out, v, sizeof(v));
   if (h->solver == 1) out[2] = h->sp_lanes;
+  return MAPDN_OK;
+} MAPDN_CATCH(h)
+
+int mapdn_get_nr_kernel(const mapdn_handle* h, int32_t* out) try {
+  if (!h || !out) return MAPDN_E_INVALID;
+  const int dc = h->cfg.nr_init == 2 ? 1 : 0, zip = h->plan.zip ? 1 : 0;
+  int32_t v[8] = {h->solver, 0, 0, 0, 0, 0, 0, 0};
+  if (h->solver == 0) {
+    const mapdn_handle::Geo& g = h->geo;
+    const NrInst* I = nr_inst_of(g.W, g.L, g.h_lds, g.g_lds, g.rec_lds, g.flat_lds, h->nr_var);
+    if (!I) return api_fail(h, MAPDN_E_INTERNAL, "mapdn_get_nr_kernel: the handle's geometry has no k_nr_tree instantiation");
+    const int32_t t[7] = {I->W, I->L, I->HL, I->GL, I->RES, (I->VAR & NR_VAR_DC) ? 1 : 0, (I->VAR & NR_VAR_ZIP) ? 1 : 0};
+    std::memcpy(v + 1, t, sizeof(t));
+  } else if (h->solver == 1) {
+    v[1] = h->sp_lanes; v[2] = dc; v[3] = zip;
+  } else {
+    const bool ga = nr_dense_ga(h->d.dn_N);
+    v[1] = nr_dense_waves(h->d.dn_N, ga); v[2] = ga ? 1 : 0;
+  }
+  std::memcpy(out, v, sizeof(v));
   return MAPDN_OK;
 } MAPDN_CATCH(h)
 

@@ -269,11 +269,12 @@ __global__ void __launch_bounds__(64 * W) k_dense_solve(const double* __restrict
 // waves per workgroup: one thread per matrix row.  LDS-resident Jacobian: N <= 64 -> 1, <= 128 -> 2; global Jacobian: the
 // instantiated W >= N / 64
 static const int DENSE_GA_W[] = {3, 4, 5, 6, 8, 11, 13, 16};
-static int dense_waves(const Dev& d) {
-  if (!d.dn_A) return d.dn_N <= 64 ? 1 : 2;
-  for (int w : DENSE_GA_W) if (64 * w >= d.dn_N) return w;
+int nr_dense_waves(int N, bool ga) {
+  if (!ga) return N <= 64 ? 1 : 2;
+  for (int w : DENSE_GA_W) if (64 * w >= N) return w;
   return 0;
 }
+static int dense_waves(const Dev& d) { return nr_dense_waves(d.dn_N, d.dn_A != nullptr); }
 size_t nr_dense_lds_bytes(const Dev& d) {
   const int W = dense_waves(d);
   return dense_lds_doubles(d.dn_N, d.dn_lda, d.n, 64 * W, d.dn_A != nullptr) * sizeof(double);

@@ -690,6 +690,9 @@ int nr_geometry_compiled(int waves, int lanes, int h_lds, int g_lds, int rec_lds
   const NrInst* I = nr_pick(waves, lanes, h_lds, g_lds, rec_lds, flat_lds, var);
   return I ? (I->RES ? 2 : 1) : 0;
 }
+const NrInst* nr_inst_of(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, int var) {
+  return nr_pick(waves, lanes, h_lds, g_lds, rec_lds, flat_lds, var);
+}
 void launch_reset_begin(const Dev& d, const int64_t* start_rows, int first_try, hipStream_t st) {
   hipLaunchKernelGGL(k_reset_begin, dim3((d.B + 255) / 256), dim3(256), 0, st, d, start_rows, first_try);
 }

@@ -115,6 +115,9 @@ void launch_nr(const Dev& d, int mode, double* reward, uint8_t* term, double* in
 enum { NR_VAR_DC = 1, NR_VAR_ZIP = 2 };
 int nr_set_lds_limit(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, size_t bytes, int var = 0);   // -2: geometry not instantiated
 int nr_geometry_compiled(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, int var = 0);
+// the instantiation launch_nr runs for this geometry / residency / variant (nullptr: none; host-side, mapdn_get_nr_kernel)
+struct NrInst;
+const NrInst* nr_inst_of(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, int var);
 // dynamic LDS of k_nr_tree (W waves, L envs per workgroup => Wt = W*64/L workers), in pair rows of L x 16 bytes:
 // node voltages (n+2: nodes, slack, trash), h (n+2) and G (2(n+2)) when resident, contribution slots (4 rows each),
 // x slots (1 row each); then verdict bytes, step-size partials (64*W doubles), overflow child list (padded to
@@ -134,7 +137,11 @@ static inline size_t nr_lds_bytes(int W, int L, int n, int cslots, int xslots, i
 size_t nr_sparse_lds_bytes(int n, int n_blocks, int L);
 int nr_sparse_prepare(int L);
 void launch_nr_sparse(const Dev& d, int mode, double* reward, uint8_t* term, double* info, hipStream_t st);
-// general-topology kernel (dense.hip): nr_dense_prepare returns -2 when the net is too large for the LDS-resident Jacobian
+// general-topology kernel (dense.hip): the Jacobian of N rows lives in LDS up to 128 rows, beyond that in global memory (GA);
+// nr_dense_waves is W of the k_nr_dense<W, GA> instantiation that serves it (0: none);
+// nr_dense_prepare returns -2 when the net is too large for the LDS-resident Jacobian
+static inline bool nr_dense_ga(int N) { return N > 128; }
+int nr_dense_waves(int N, bool ga);
 size_t nr_dense_lds_bytes(const Dev& d);
 int nr_dense_prepare(const Dev& d);
 void launch_nr_dense(const Dev& d, int mode, double* reward, uint8_t* term, double* info, hipStream_t st);

@@ -361,6 +361,10 @@ class VoltageControlBatch:
         """the NR launch geometry mapdn_create settled on (solver, waves, envs per workgroup, LDS residency, rows, model time)"""
         return _lib.nr_geometry(self._h)
 
+    def nr_kernel(self):
+        """the power-flow kernel instantiation the solves launch (solver and its template arguments; _lib.nr_kernel)"""
+        return _lib.nr_kernel(self._h)
+
     def stats(self):
         rf, mi, mx = _lib.C.c_int64(), _lib.C.c_double(), _lib.C.c_int32()
         with torch.cuda.device(self.device):
