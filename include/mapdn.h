@@ -481,6 +481,30 @@ int mapdn_nr_time_ms(mapdn_handle* h, double* total_ms, int64_t* launches);
  *   2 k_nr_dense<W, GA>:                     W, GA (the Jacobian in global memory), 0, 0, 0, 0, 0 */
 int mapdn_get_nr_kernel(const mapdn_handle* h, int32_t* out8);
 
+/* ---- Volt/VAR droop control: the reference's traditional baseline (traditional_control/pf_droop_matpower_all.m:84-162, law :196-231).
+ * A field left 0 takes the script's value (so an all-zero struct, or NULL, is the script's configuration). */
+typedef struct mapdn_droop_config {
+  double va, vb, vc, vd;            /* breakpoints (p.u.) of the law: 0.95, 1.0, 1.0, 1.05; need va < vb <= vc < vd           */
+  double damping;                   /* a <- (1 - damping) a + damping f(v): 0.1; 0 < damping <= 1                             */
+  int32_t max_iter;                 /* power flows per env at most: 100; 1 ... 10000                                          */
+  double v_tol;                     /* stop when ||v - v_last||_2 < v_tol over the sgen buses: 1e-4; > 0                      */
+  double reactive_ratio;            /* q_max = min(sqrt(s_max^2 - p^2), reactive_ratio s_max): 1; > 0                         */
+} mapdn_droop_config;
+
+/* The droop controller's actions for the env's current state (the loads and PV the next mapdn_step solves with, noise applied):
+ * per env a = 0, v_last = 100, then for i = 1 ... max_iter: power flow with q_j = sqrt(s_max_j^2 - p_j^2) a_j; v_j = |V| at sgen j's
+ * bus; stop when ||v - v_last||_2 < v_tol, else v_last = v, a = (1 - damping) a + damping f(v) min(1, ratio s_max / lim).
+ *   actions    f64 [B, ns]: a of the last solved power flow (step() takes it unclipped)
+ *   vm_pu      f64 [B, nb] or NULL: |V| of that power flow (NaN for status 2 and 3)
+ *   iterations i32 [B]: power flows solved;  status u8 [B]: 0 converged, 1 max_iter reached, 2 a power flow failed (actions = the
+ *              last a whose power flow converged, 0 if the first failed), 3 not solved (terminated / frozen / waiting for its
+ *              auto-reset restart; a = 0)
+ * Device pointers on `stream`.  Not a step-path call: it polls the count of envs still iterating every 4 power flows (a stream
+ * synchronisation) and allocates its workspace on the first call.  The obs, state, results, returns, counters and the next
+ * mapdn_step are what they would have been without the call.  MAPDN_E_INVALID for a config outside the ranges above (checked on host-only handles too). */
+int mapdn_droop_actions(mapdn_handle* h, const mapdn_droop_config* cfg, double* actions, double* vm_pu, int32_t* iterations,
+                        uint8_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,7 +36,7 @@ EXPORTS = (
     "mapdn_critic_head_forward", "mapdn_critic_head_scratch_floats", "mapdn_critic_head_backward", "mapdn_critic_head_backward_dot", "mapdn_critic_head_mse", "mapdn_get_profile_stats",
     "mapdn_explore_actions", "mapdn_rollout_stats", "mapdn_copy_segments",
     "mapdn_policy_forward_train", "mapdn_policy_backward", "mapdn_policy_backward_scratch_floats", "mapdn_get_dc_angles",
-    "mapdn_get_nr_kernel",
+    "mapdn_get_nr_kernel", "mapdn_droop_actions",
 )
 
 _pd = C.POINTER(C.c_double)
@@ -86,6 +86,32 @@ NR_SOLVERS = dict(auto=0, tree=0, sparse=1, dense=2)
 NR_INITS = dict(flat=0, dc=2)   # mapdn_env_config.nr_init: runpp init="flat" / init="dc" (1, init="results", is reserved)
 GEOMETRY_KEYS = ("solver", "waves", "lanes", "lean", "rows", "h_lds", "g_lds", "rec_lds", "flat_lds", "line_lds", "mm_pass",
                  "lds_bytes", "workgroups", "resident_per_cu", "rounds", "model_ns", "fuse_inject", "n_fused_buses", "n_nodes", "nr_init")
+
+
+class CDroopConfig(C.Structure):
+    """mapdn_droop_config: a field left 0 takes the value of the reference's droop script (include/mapdn.h)"""
+    _fields_ = [("va", C.c_double), ("vb", C.c_double), ("vc", C.c_double), ("vd", C.c_double), ("damping", C.c_double),
+                ("max_iter", C.c_int32), ("v_tol", C.c_double), ("reactive_ratio", C.c_double)]
+
+
+DROOP_STATUS = ("converged", "max_iter", "pf_failed", "not_solved")    # mapdn_droop_actions status codes 0 .. 3
+
+
+def make_droop_config(cfg=None) -> CDroopConfig:
+    """CDroopConfig from None (the script's defaults), a dict or an object with the same attribute names (baselines.DroopConfig)"""
+    c = CDroopConfig()
+    if cfg is None:
+        return c
+    get = cfg.get if isinstance(cfg, dict) else (lambda k, _d=None: getattr(cfg, k, _d))
+    if isinstance(cfg, dict):
+        unknown = set(cfg) - {f for f, _ in CDroopConfig._fields_}
+        if unknown:
+            raise KeyError(f"unknown droop config keys {sorted(unknown)}")
+    for name, typ in CDroopConfig._fields_:
+        v = get(name, None)
+        if v is not None:
+            setattr(c, name, int(v) if typ is C.c_int32 else float(v))
+    return c
 
 
 class CDims(C.Structure):
@@ -204,6 +230,7 @@ def load():
     lib.mapdn_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int32), vp]
     lib.mapdn_nr_timing.argtypes = [vp, C.c_int32]
     lib.mapdn_nr_time_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    lib.mapdn_droop_actions.argtypes = [vp, C.POINTER(CDroopConfig), vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("mapdn_last_error", "mapdn_destroy", "mapdn_build_info"):
             getattr(lib, name).restype = C.c_int

@@ -1,0 +1,102 @@
+"""Traditional baselines of the MAPDN paper next to the MARL learners: droop control and no control.
+
+The reference ships them as MATLAB scripts (traditional_control/pf_droop_matpower_all.m, run "pf" = no control).  Here they act on
+the batched env:
+
+``DroopConfig``     the droop script's parameters (breakpoints va < vb <= vc < vd, damping, max_iter, v_tol, reactive_ratio)
+``DroopControl``    the droop controller: per env step, VoltageControlBatch.droop_actions (the fixed-point loop runs on the GPU)
+``NoControl``       a = 0 (the script's "pf" run)
+``BaselineTester``  PGTester's `run` / `batch_run` with a baseline in place of the policy: the same record and `mean_test_*`
+                    formats, so the paper's comparison table and the plotting scripts take baseline results unchanged.
+"""
+from __future__ import annotations
+
+from dataclasses import asdict, dataclass
+
+import torch
+
+from ._lib import INFO_KEYS
+from .tester import RECORD_KEYS, PGTester
+
+
+@dataclass
+class DroopConfig:
+    """pf_droop_matpower_all.m's values (p.u. voltages; the law is +1 below va, a slope to 0 at vb, 0 up to vc, a slope to -1 at vd)"""
+    va: float = 0.95
+    vb: float = 1.0
+    vc: float = 1.0
+    vd: float = 1.05
+    damping: float = 0.1
+    max_iter: int = 100
+    v_tol: float = 1e-4
+    reactive_ratio: float = 1.0
+
+    def as_dict(self):
+        return asdict(self)
+
+
+class DroopControl:
+    """Droop control on a VoltageControlBatch.  `history` (when kept) collects the (iterations, status) tensors of every call."""
+
+    name = "droop"
+
+    def __init__(self, config: DroopConfig | None = None, keep_history: bool = False):
+        self.config = config or DroopConfig()
+        self.history = [] if keep_history else None
+
+    def actions(self, env):
+        a, it, st = env.droop_actions(self.config)
+        if self.history is not None:
+            self.history.append((it.clone(), st.clone()))
+        return a
+
+
+class NoControl:
+    """a = 0 for every sgen (no reactive power)"""
+
+    name = "no_control"
+
+    def actions(self, env):
+        return torch.zeros(env.n_envs, env.n_sgen, dtype=torch.float64, device=env.device)
+
+
+class BaselineTester:
+    """PGTester (mapdn_amd/tester.py) with a baseline controller (anything with `actions(env) -> [B, n_sgen]`) in place of the
+    policy: `run(day, hour, quarter)` records one env's trajectory from a noise-free start, `batch_run(num_episodes)` returns
+    {'mean_test_<info key>': (mean, 2 std)} over all steps of all episodes — the same steps, resets and noise as PGTester."""
+
+    def __init__(self, args, controller, env):
+        self.args, self.controller, self.env = args, controller, env
+
+    _snapshot = PGTester._snapshot
+    save_record = staticmethod(PGTester.save_record)
+    print_info = staticmethod(PGTester.print_info)
+
+    def run(self, day, hour, quarter, env_index: int = 0):
+        env = self.env
+        env.manual_reset(day, hour, quarter)
+        record = {k: [] for k in RECORD_KEYS}
+        self._snapshot(record, env_index)
+        for t in range(self.args.max_steps):
+            _, done, _ = env.step(self.controller.actions(env), add_noise=False)
+            self._snapshot(record, env_index)
+            if bool(done[env_index]) or t == self.args.max_steps - 1:
+                break
+        return record
+
+    def batch_run(self, num_episodes: int = 100):
+        env = self.env
+        rounds = max(1, -(-int(num_episodes) // env.n_envs))
+        samples = []
+        for _ in range(rounds):
+            env.reset()
+            alive = torch.ones(env.n_envs, dtype=torch.bool, device=env.device)
+            infos, masks = [], []
+            for t in range(self.args.max_steps):
+                _, done, info = env.step(self.controller.actions(env), add_noise=False)
+                infos.append(info.clone()); masks.append(alive.clone())
+                alive = alive & ~done.bool()
+            samples.append(torch.stack(infos)[torch.stack(masks)])
+        allv = torch.cat(samples).double()
+        mean, std = allv.mean(0).tolist(), allv.std(0, unbiased=False).tolist()
+        return {"mean_test_" + k: (m, 2.0 * s) for k, m, s in zip(INFO_KEYS, mean, std)}

@@ -18,6 +18,7 @@
 using namespace mapdn;
 
 static constexpr size_t CU_LDS = 160 * 1024;    // LDS of one CU: what one workgroup of any NR kernel may use
+static constexpr int DROOP_MAX_ITER_CAP = 10000;   // mapdn_droop_config.max_iter at most
 
 // ---- tuning knobs: a field of mapdn_env_config (0 = automatic), overridden by an environment variable when one is set (tools,
 // A/B runs).  resolve_knobs reads them all once, at the top of mapdn_create, into the handle; nothing else reads the environment.
@@ -88,6 +89,9 @@ struct mapdn_handle {
   size_t ev_used = 0;
   double acc_ms = 0.0;
   int64_t acc_launches = 0;
+  // droop baseline (mapdn_droop_actions): its workspace, allocated on the first call
+  DroopState droop{};
+  bool droop_ready = false;
 };
 
 static std::string g_create_err;
@@ -711,9 +715,11 @@ int mapdn_set_profiles(mapdn_handle* h, const double* pv, const double* load_p, 
   return MAPDN_OK;
 } MAPDN_CATCH(h)
 
+// dv: the Dev of the launch when it is not the handle's own (the droop solves run with their own active / iters / conv arrays)
 static void nr_launch(mapdn_handle* h, int mode, double* reward, uint8_t* term, double* info, hipStream_t st,
-                      const void* fused_actions = nullptr, int fused_dtype = 0) {
-  if (!h->timing) { launch_nr(h->d, mode, reward, term, info, st, fused_actions, fused_dtype); return; }
+                      const void* fused_actions = nullptr, int fused_dtype = 0, const Dev* dv = nullptr) {
+  const Dev& d = dv ? *dv : h->d;
+  if (!h->timing) { launch_nr(d, mode, reward, term, info, st, fused_actions, fused_dtype); return; }
   if (h->ev_used + 2 > h->ev.size()) {
     if (h->ev.size() >= 2 * 8192) {   // pool full: drain
       double ms; int64_t n; mapdn_nr_time_ms(h, &ms, &n); h->acc_ms = ms; h->acc_launches = n;
@@ -726,7 +732,7 @@ static void nr_launch(mapdn_handle* h, int mode, double* reward, uint8_t* term, 
   hipEvent_t a = h->ev[h->ev_used], b = h->ev[h->ev_used + 1];
   h->ev_used += 2;
   (void)hipEventRecord(a, st);
-  launch_nr(h->d, mode, reward, term, info, st, fused_actions, fused_dtype);
+  launch_nr(d, mode, reward, term, info, st, fused_actions, fused_dtype);
   (void)hipEventRecord(b, st);
 }
 
@@ -1108,6 +1114,98 @@ int mapdn_nr_time_ms(mapdn_handle* h, double* total_ms, int64_t* launches) try {
   if (total_ms) *total_ms = ms;
   if (launches) *launches = n;
   return MAPDN_OK;
+} MAPDN_CATCH(h)
+
+// ---- droop baseline (droop.hip): the script's defaults for the fields left 0, and its refusals
+static const char* droop_resolve(const mapdn_droop_config* in, mapdn_droop_config& c) {
+  if (in) c = *in; else std::memset(&c, 0, sizeof(c));
+  if (c.va == 0.0) c.va = 0.95;                  // pf_droop_matpower_all.m: the law's breakpoints, damping, stopping rule,
+  if (c.vb == 0.0) c.vb = 1.0;                   // reactive_ratio of q_max = min(sqrt(S^2 - p^2), ratio S)
+  if (c.vc == 0.0) c.vc = 1.0;
+  if (c.vd == 0.0) c.vd = 1.05;
+  if (c.damping == 0.0) c.damping = 0.1;
+  if (c.max_iter == 0) c.max_iter = 100;
+  if (c.v_tol == 0.0) c.v_tol = 1e-4;
+  if (c.reactive_ratio == 0.0) c.reactive_ratio = 1.0;
+  if (!(c.va < c.vb && c.vb <= c.vc && c.vc < c.vd)) return "droop: the breakpoints must satisfy va < vb <= vc < vd";
+  if (!(c.damping > 0.0 && c.damping <= 1.0)) return "droop: damping must lie in (0, 1]";
+  if (c.max_iter < 1 || c.max_iter > DROOP_MAX_ITER_CAP) return "droop: max_iter must lie in 1 ... 10000";
+  if (!(c.v_tol > 0.0)) return "droop: v_tol must be > 0";
+  if (!(c.reactive_ratio > 0.0)) return "droop: reactive_ratio must be > 0";
+  return nullptr;
+}
+
+// the workspace of the droop loop (DroopState), once per handle
+static int droop_prepare(mapdn_handle* h) {
+  if (h->droop_ready) return MAPDN_OK;
+  const Plan& P = h->plan;
+  DroopState& s = h->droop;
+  const size_t Bp = h->d.Bp, ns = (size_t)P.ns;
+  int32_t *iters = nullptr, *nr_iters = nullptr, *n_active = nullptr; uint8_t *status = nullptr, *act = nullptr, *nr_conv = nullptr;
+  int rc;
+  if ((rc = dalloc(h, &s.a, ns * Bp)) || (rc = dalloc(h, &s.a_sol, ns * Bp)) || (rc = dalloc(h, &s.v_last, ns * Bp)) ||
+      (rc = dalloc(h, &s.dv2, ns * Bp)) ||
+      (rc = dalloc(h, &iters, Bp)) || (rc = dalloc(h, &nr_iters, Bp)) || (rc = dalloc(h, &status, Bp)) || (rc = dalloc(h, &act, Bp)) ||
+      (rc = dalloc(h, &nr_conv, Bp)) || (rc = dalloc(h, &n_active, (size_t)DROOP_MAX_ITER_CAP + 1)))
+    return rc;
+  s.iters = iters; s.nr_iters = nr_iters; s.status = status; s.act = act; s.nr_conv = nr_conv; s.n_active = n_active;
+  std::vector<int32_t> vrow(std::max<size_t>(ns, 1), 0);           // |V| of sgen j's bus: the Vout row of its node (alloc_nrbuf)
+  for (size_t j = 0; j < ns; ++j) vrow[j] = (int32_t)h->d.r_vout + VOF * P.pos_of_obus[P.sgen_bus[j]] + VO_VM;
+  const int32_t* vr = nullptr;
+  if ((rc = dupload(h, &vr, vrow))) return rc;
+  s.sg_vrow = vr; s.vm_row = h->vm_row;
+  h->droop_ready = true;
+  return MAPDN_OK;
+}
+
+// The loop of pf_droop_matpower_all.m:84-162 for every env at once: the start launch, then per iteration the solve (MODE_SOLVE, with
+// the droop's own active set: envs that stopped are skipped) and k_droop_update.  The host reads the number of envs still iterating
+// every DROOP_POLL iterations only, so at most DROOP_POLL - 1 solves run after the last env stopped.  Writes only what the next
+// step() overwrites before it reads it: the PV-bus and several-load-bus entries of the Sbus buffer that solve reads (d.sb_off; all of
+// it when Sbus is stale after mapdn_solve_only, as the next step() rebuilds it then anyway) and the solver's Vout rows.
+static int droop_run(mapdn_handle* h, const mapdn_droop_config& c, double* actions, double* vm_pu, int32_t* iterations,
+                     uint8_t* status, hipStream_t st) {
+  constexpr int DROOP_POLL = 4;
+  if (const int rc = droop_prepare(h)) return rc;
+  const Dev& d = h->d;
+  DroopState s = h->droop;
+  s.va = c.va; s.vb = c.vb; s.vc = c.vc; s.vd = c.vd; s.damping = c.damping; s.v_tol = c.v_tol; s.ratio = c.reactive_ratio;
+  s.max_iter = c.max_iter; s.vm_out = vm_pu;
+  HIPCHK(h, hipMemsetAsync(s.n_active, 0, ((size_t)c.max_iter + 1) * sizeof(int32_t), st));
+  if (h->sbus_stale) {                           // Sbus holds mapdn_solve_only's inputs: rebuild it from the env's loads (q = 0)
+    HIPCHK(h, hipMemsetAsync(s.a, 0, (size_t)d.ns * d.Bp * sizeof(double), st));
+    launch_inject(d, MODE_SOLVE, nullptr, MAPDN_F64, d.cur_pl, d.cur_ql, d.cur_pv, s.a, 0, st);
+  }
+  launch_droop_update(d, s, 0, st);
+  Dev dd = d;
+  dd.active = s.act; dd.iters = const_cast<int32_t*>(s.nr_iters); dd.conv = const_cast<uint8_t*>(s.nr_conv);
+  for (int i = 0; i < c.max_iter; ++i) {         // i power flows solved so far
+    if (i % DROOP_POLL == 0) {
+      int32_t left = 0;
+      HIPCHK(h, hipMemcpyAsync(&left, s.n_active + i, sizeof(left), hipMemcpyDeviceToHost, st));
+      HIPCHK(h, hipStreamSynchronize(st));
+      if (left == 0) break;
+    }
+    nr_launch(h, MODE_SOLVE, nullptr, nullptr, nullptr, st, nullptr, 0, &dd);
+    launch_droop_update(d, s, i + 1, st);
+  }
+  transpose_out(h, s.a_sol, 1.0, h->iota_idx, actions, d.ns, st);
+  launch_copy_i32(s.iters, iterations, d.B, st);
+  launch_copy_u8(s.status, status, d.B, st);
+  HIPCHK(h, hipGetLastError());
+  return MAPDN_OK;
+}
+
+int mapdn_droop_actions(mapdn_handle* h, const mapdn_droop_config* cfg, double* actions, double* vm_pu, int32_t* iterations,
+                        uint8_t* status, void* stream) try {
+  if (!h) return MAPDN_E_INVALID;
+  mapdn_droop_config c;
+  if (const char* why = droop_resolve(cfg, c)) return api_fail(h, MAPDN_E_INVALID, why);
+  if (!actions || !iterations || !status) { h->err = "droop_actions: null buffer"; return MAPDN_E_INVALID; }
+  NEEDDEV(h);
+  if (!h->was_reset) { h->err = "droop_actions before reset"; return MAPDN_E_STATE; }
+  HIPCHK(h, hipSetDevice(h->device));
+  return droop_run(h, c, actions, vm_pu, iterations, status, (hipStream_t)stream);
 } MAPDN_CATCH(h)
 
 }  // extern "C"

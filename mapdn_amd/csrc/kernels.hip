@@ -725,3 +725,6 @@ void launch_copy_u8(const uint8_t* s, uint8_t* dd, int B, hipStream_t st) { hipL
 void launch_stats(const Dev& d, long long* out, hipStream_t st) { hipLaunchKernelGGL(k_stats, dim3(1), dim3(256), 0, st, d, out); }
 
 }  // namespace mapdn
+
+// the droop baseline's kernel (droop.hip) is compiled in this translation unit: one object per source file of build.SOURCES
+#include "droop.hip"

@@ -157,4 +157,22 @@ void launch_copy_i32(const int32_t* s, int32_t* dd, int B, hipStream_t st);
 void launch_copy_u8(const uint8_t* s, uint8_t* dd, int B, hipStream_t st);
 void launch_stats(const Dev& d, long long* out, hipStream_t st);
 
+// ---- droop baseline (droop.hip; mapdn_droop_actions).  Per-env status as in include/mapdn.h; RUNNING only between launches.
+enum { DROOP_CONVERGED = 0, DROOP_MAX_ITER = 1, DROOP_PF_FAILED = 2, DROOP_STOPPED = 3, DROOP_RUNNING = 255 };
+struct DroopState {
+  double va, vb, vc, vd, damping, v_tol, ratio;
+  int32_t max_iter;
+  double *a, *a_sol, *v_last, *dv2;  // [ns][Bp]: the action of the next solve, the action of the last converged solve, |V| of the last
+                                     // solve, the terms (v - v_last)^2 of the stop test
+  int32_t* iters;                    // [Bp] solves so far
+  uint8_t* status;                   // [Bp]
+  uint8_t* act;                      // [Bp] the solver's active flags of the droop solves (Dev::active of those launches)
+  const int32_t* nr_iters; const uint8_t* nr_conv;   // [Bp] Dev::iters / conv of those launches
+  const int32_t* sg_vrow;            // [ns] row of nrbuf that holds |V| of sgen j's bus (Vout, VO_VM)
+  const int32_t* vm_row;             // [nbo] the same for every original bus
+  int32_t* n_active;                 // [max_iter + 1] envs still iterating after update i
+  double* vm_out;                    // [B][nbo] env-major, or nullptr
+};
+void launch_droop_update(const Dev& d, const DroopState& s, int iter, hipStream_t st);
+
 }  // namespace mapdn

@@ -343,6 +343,24 @@ class VoltageControlBatch:
                                                   it.data_ptr(), cv.data_ptr(), self._stream()), self._h)
         return vm, va, it, cv.bool()
 
+    def droop_actions(self, config=None, vm_pu=False):
+        """The reference's Volt/VAR droop controller (traditional_control/pf_droop_matpower_all.m) on the current state of every env:
+        the actions the next step() should take (mapdn_droop_actions, include/mapdn.h).  config: None (the script's values), a
+        baselines.DroopConfig or a dict of its fields.  Returns (actions float64 [B, n_sgen], iterations int32 [B] power flows solved,
+        status uint8 [B]: 0 converged, 1 max_iter reached, 2 a power flow failed, 3 not solved — done / waiting for its restart),
+        and vm_pu float64 [B, n_bus] (|V| of the last solved power flow; NaN for status 2 and 3) when vm_pu=True.  The env's state
+        and its next step() are not affected."""
+        cc = _lib.make_droop_config(config)
+        B, dv = self.n_envs, self.device
+        act = torch.empty(B, self.n_sgen, dtype=torch.float64, device=dv)
+        it = torch.empty(B, dtype=torch.int32, device=dv)
+        st = torch.empty(B, dtype=torch.uint8, device=dv)
+        vm = torch.empty(B, self.n_bus, dtype=torch.float64, device=dv) if vm_pu else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mapdn_droop_actions(self._h, _lib.C.byref(cc), act.data_ptr(), vm.data_ptr() if vm_pu else None,
+                                                     it.data_ptr(), st.data_ptr(), self._stream()), self._h)
+        return (act, it, st, vm) if vm_pu else (act, it, st)
+
     def ybus_dense(self):
         """Ybus over the ELECTRICAL nodes (n_nodes x n_nodes; == buses unless closed bus-bus switches fuse some: include/mapdn.h)"""
         nn = self.geometry()["n_nodes"]
@@ -542,6 +560,12 @@ class VoltageControl(MultiAgentEnv):
         if terminated:
             print(f"Episode terminated at time: {self.steps} with return: {self.sum_rewards:2.4f}.")   # :209
         return reward, terminated, {k: float(v) for k, v in zip(INFO_KEYS, vals)}
+
+    def droop_action(self, config=None, vm_pu=False):
+        """VoltageControlBatch.droop_actions for this one env, as numpy: (action [n_sgen], iterations, status[, vm_pu [n_bus]])"""
+        out = self._b.droop_actions(config, vm_pu=vm_pu)
+        a, it, st = out[0][0].cpu().numpy(), int(out[1][0].item()), int(out[2][0].item())
+        return (a, it, st, out[3][0].cpu().numpy()) if vm_pu else (a, it, st)
 
     def _obs_list(self, obs):
         o = obs[0].double().cpu().numpy()
