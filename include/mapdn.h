@@ -353,7 +353,12 @@ int mapdn_dense_solve(const double* a, const double* b, double* x, int32_t n, in
  * models/model.py:101-139): fc1 (+ one-hot agent-id column) -> LayerNorm -> ReLU -> GRUCell -> fc2, one launch, inference only.
  * Device pointers, fp32, contiguous: obs [rows, obs_dim] (rows = envs x agents, agent = row % n_agents), hid_in / hid_out
  * [rows, 64], w1 [64, obs_dim + id_dim] (id_dim = n_agents or 0), w_ih / w_hh [192, 64] (torch.nn.GRUCell layout: r, z, n),
- * w2 [1, 64]; means [rows].  Hidden size 64, action_dim 1 (the reference's defaults).  hid_out may be NULL (the new hidden state is not stored). */
+ * w2 [1, 64]; means [rows].  Hidden size 64, action_dim 1 (the reference's defaults).  hid_out may be NULL (the new hidden state is not stored).
+ * Arithmetic: every product is an fp32 fmaf chain on the matrix cores, LayerNorm as the modules'; the GRU gates are
+ * sigmoid(v) = rcp(1 + exp(-v)) and tanh(v) = 1 - 2 rcp(exp(2 v) + 1) on the hardware exp / rcp (~1e-7 absolute error each, finite
+ * and saturating for any finite v), not the library's division and tanhf — so means / hid_out follow the f32 modules to a few 1e-7,
+ * not bit for bit; DESIGN.md ("Learner kernels against float64") holds the errors measured per launch geometry and over a 240-step
+ * recurrent episode.  MAPDN_POLICY_FWD_V1=1 (read at every call) selects the earlier form of the kernel (division + tanhf gates). */
 int mapdn_policy_forward(const float* obs, const float* hid_in, const float* w1, const float* b1, const float* ln_g,
                          const float* ln_b, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
                          const float* w2, const float* b2, float* means, float* hid_out, int32_t rows, int32_t n_agents,
@@ -372,7 +377,10 @@ int mapdn_policy_forward_train(const float* obs, const float* hid_in, const floa
  *                        dW_hh = dgates[:, [0:128, 192:256]]^T hid_in);  xn [rows, 64] = relu(LayerNorm(x1));
  *   small [512] = db_r | db_z | db_ni | db_nh | dgamma | dbeta | dw2 (64 each) | db2 (1) + pad, reduced in a fixed order (no atomics):
  *                 b_ih gradient = db_r | db_z | db_ni, b_hh gradient = db_r | db_z | db_nh;
- *   scratch: mapdn_policy_backward_scratch_floats(rows) floats.  Hidden size 64, one action output; fp32, contiguous device pointers. */
+ *   scratch: mapdn_policy_backward_scratch_floats(rows) floats.  Hidden size 64, one action output; fp32, contiguous device pointers.
+ * Pad rule (this call and mapdn_critic_head_backward / _mse alike): the pad elements of an OUTPUT (small[449 .. 511], grads[4354 .. 4415])
+ * are written as zero; `scratch` need not be initialised — its pad columns are neither read nor written, every other element is written
+ * before it is read. */
 int64_t mapdn_policy_backward_scratch_floats(int64_t rows);
 int mapdn_policy_backward(const float* dmeans, const float* x1, const float* hid_in, const float* ln_g, const float* ln_b, float ln_eps,
                           const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* w2, float* dx1,
@@ -381,6 +389,10 @@ int mapdn_policy_backward(const float* dmeans, const float* x1, const float* hid
 /* 1 when mapdn_policy_forward has a launch shape for this observation width (the parameter set and a tile's activations must
  * fit the 160 KB LDS of a CU: obs_dim up to ~2 400 columns without ids), else 0 — callers then keep their own forward. */
 int mapdn_policy_forward_fits(int32_t obs_dim, int32_t id_dim);
+/* The launch shape behind that answer (host only, no device needed; returns what mapdn_policy_forward_fits returns): threads per
+ * workgroup (512 / 256 = k_policy_fwd2<512> / <256>, or k_policy_fwd<...> under MAPDN_POLICY_FWD_V1), whether the id columns of fc1 are
+ * staged in LDS, and the dynamic LDS in bytes; all three 0 when nothing fits.  Any pointer may be NULL.  The launch calls the same function. */
+int mapdn_policy_forward_geometry(int32_t obs_dim, int32_t id_dim, int32_t* threads, int32_t* ids_lds, int32_t* lds_bytes);
 
 /* LayerNorm over 64 features (+ fused ReLU when relu != 0) for the learner's training-time passes (agents/rnn_agent.py:16-21,
  * critics/mlp_critic.py:22-27: fc1 -> LayerNorm -> ReLU), forward and backward; device pointers, fp32, contiguous [rows, 64].
@@ -416,14 +428,21 @@ int mapdn_relu_dot64_backward(const float* dv, const float* pre, const float* w,
  * Device pointers, contiguous; gamma, beta, b2, w3 [64], w2 [64][64] (out, in), b3 [1]; rows < 2^31.
  * backward recomputes the forward from the same inputs (nothing is saved but them):
  *   dx      [rows][64]                       (x read)   — or dbase [rows / n][64] = sum of dx over every group of n rows (x formed);
- *   grads   [4416 (+ n * 64)] when param_grads != 0 or x is formed:  dW2 [64][64] | dgamma | dbeta | db2 | dw3 [64 each] | db3 [1] + pad to
- *           4416 | dper_n [n][64] (formed rows only; with param_grads == 0 only dper_n is written);
+ *   grads   [4416 (+ n * 64)] when param_grads != 0 or x is formed:  dW2 [64][64] | dgamma | dbeta | db2 | dw3 [64 each] | db3 [1] |
+ *           [4353] the loss of _mse (0 otherwise) | pad to 4416, written as zero | dper_n [n][64] (formed rows only; with param_grads == 0
+ *           only dper_n is written);
  *   scratch mapdn_critic_head_scratch_floats(rows, n, formed) floats (per-workgroup partial sums — the wavefronts of a workgroup are summed through LDS —, reduced in a fixed order: deterministic).
  * _backward_dot: only dact[row] = dx[row] . dot_w[row % n] (dot_w [n][64]; n = 1 when x is read) — the policy update through the
  * central critic, whose own-action column of fc1 (models/maddpg.py:52-58) is the only gradient path back to the policy. */
 int mapdn_critic_head_forward(const float* x, const float* per_n, int32_t n, const float* gamma, const float* beta, float eps,
                               const float* w2, const float* b2, const float* w3, const float* b3, float* v, int64_t rows, void* stream);
 int64_t mapdn_critic_head_scratch_floats(int64_t rows, int32_t n, int32_t formed);
+/* The backward launch for (rows, n, formed, mode) — mode 0 _backward(param_grads = 1), 1 _backward(param_grads = 0), 2 _backward_dot,
+ * 3 _mse: k_head_bwd<formed, mode, threads> on `blocks` workgroups with `lds_bytes` of dynamic LDS.  cus = 0 asks the current device for
+ * its CU count; cus > 0 answers for that count on the host alone.  Honours MAPDN_HEAD_BWD_THREADS (256 / 512; 512 only where its LDS
+ * fits).  MAPDN_E_INVALID for arguments or an LDS need the launch refuses.  The launch calls the same functions. */
+int mapdn_critic_head_backward_geometry(int64_t rows, int32_t n, int32_t formed, int32_t mode, int32_t cus, int32_t* threads,
+                                        int32_t* blocks, int32_t* lds_bytes);
 int mapdn_critic_head_backward(const float* dv, const float* x, const float* per_n, int32_t n, const float* gamma, const float* beta,
                                float eps, const float* w2, const float* b2, const float* w3, const float* b3, float* dx, float* grads,
                                float* scratch, int64_t rows, int32_t param_grads, void* stream);

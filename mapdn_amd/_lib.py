@@ -36,7 +36,7 @@ EXPORTS = (
     "mapdn_critic_head_forward", "mapdn_critic_head_scratch_floats", "mapdn_critic_head_backward", "mapdn_critic_head_backward_dot", "mapdn_critic_head_mse", "mapdn_get_profile_stats",
     "mapdn_explore_actions", "mapdn_rollout_stats", "mapdn_copy_segments",
     "mapdn_policy_forward_train", "mapdn_policy_backward", "mapdn_policy_backward_scratch_floats", "mapdn_get_dc_angles",
-    "mapdn_get_nr_kernel", "mapdn_droop_actions",
+    "mapdn_get_nr_kernel", "mapdn_droop_actions", "mapdn_policy_forward_geometry", "mapdn_critic_head_backward_geometry",
 )
 
 _pd = C.POINTER(C.c_double)
@@ -206,6 +206,8 @@ def load():
     lib.mapdn_get_sparse_program.argtypes = [vp, C.c_int32, _pi, _pi, _pi, _pi]
     lib.mapdn_policy_forward.argtypes = [vp] * 14 + [C.c_int32] * 4 + [C.c_float, vp]
     lib.mapdn_policy_forward_fits.argtypes = [C.c_int32, C.c_int32]
+    lib.mapdn_policy_forward_geometry.argtypes = [C.c_int32, C.c_int32, _pi, _pi, _pi]
+    lib.mapdn_critic_head_backward_geometry.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _pi, _pi, _pi]
     lib.mapdn_policy_forward_train.argtypes = [vp] * 15 + [C.c_int32] * 4 + [C.c_float, vp]
     lib.mapdn_policy_backward_scratch_floats.argtypes = [C.c_int64]
     lib.mapdn_policy_backward_scratch_floats.restype = C.c_int64
@@ -355,3 +357,19 @@ def nr_kernel(handle) -> dict:
     check(load().mapdn_get_nr_kernel(handle, out), handle)
     solver = int(out[0])
     return dict(solver=solver, **{k: int(out[1 + i]) for i, k in enumerate(NR_KERNEL_KEYS[solver])})
+
+
+def policy_forward_geometry(obs_dim: int, id_dim: int):
+    """(threads, ids_lds, lds_bytes) of the policy forward's launch for this width (mapdn_policy_forward_geometry), or None when no
+    launch shape fits"""
+    t, il, lds = C.c_int32(), C.c_int32(), C.c_int32()
+    ok = load().mapdn_policy_forward_geometry(int(obs_dim), int(id_dim), C.byref(t), C.byref(il), C.byref(lds))
+    return (t.value, il.value, lds.value) if ok else None
+
+
+def critic_head_backward_geometry(rows: int, n: int, formed: bool, mode: int, cus: int = 0):
+    """(threads, blocks, lds_bytes) of the critic head's backward launch (mapdn_critic_head_backward_geometry), or None when the
+    library refuses it"""
+    t, b, lds = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = load().mapdn_critic_head_backward_geometry(int(rows), int(n), int(bool(formed)), int(mode), int(cus), C.byref(t), C.byref(b), C.byref(lds))
+    return (t.value, b.value, lds.value) if rc == 0 else None

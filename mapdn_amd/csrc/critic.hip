@@ -401,7 +401,7 @@ k_head_bwd(HeadArgs p, const float* __restrict__ dv, float* __restrict__ dx, con
       const float t = sum_j(ab3), tl = sum_j(aloss);           // (lanes with g != 0 hold 0)
       if (lane == 0) { red[4352] = t; red[4353] = tl; }
       __syncthreads();
-      for (int col = tid; col < 4354; col += NT) {
+      for (int col = tid; col < HW; col += NT) {
         float v = sm[col];
 #pragma unroll
         for (int ww = 1; ww < NW; ++ww) v += sm[(size_t)ww * HP + col];
@@ -411,12 +411,14 @@ k_head_bwd(HeadArgs p, const float* __restrict__ dv, float* __restrict__ dx, con
   }
 }
 
-// out[col] = sum over wavefronts of partial[w][col] in a fixed order: four strided sub-sums, then those in order
-__global__ void __launch_bounds__(256) k_head_reduce(const float* __restrict__ partial, int nw, int pstride, int lo, int hi, float* __restrict__ out) {
+// out[col] = sum over wavefronts of partial[w][col] in a fixed order: four strided sub-sums, then those in order, for lo <= col < hi;
+// columns from `written` on are pad that the producer left alone: out[col] becomes zero there without a read of the partials
+__global__ void __launch_bounds__(256) k_head_reduce(const float* __restrict__ partial, int nw, int pstride, int lo, int hi, int written,
+                                                     float* __restrict__ out) {
   __shared__ float s_acc[4][64];
   const int c = threadIdx.x & 63, grp = threadIdx.x >> 6, col = lo + blockIdx.x * 64 + c;
   float acc = 0.0f;
-  if (col < hi) for (int i = grp; i < nw; i += 4) acc += partial[(size_t)i * pstride + col];
+  if (col < written) for (int i = grp; i < nw; i += 4) acc += partial[(size_t)i * pstride + col];
   s_acc[grp][c] = acc;
   __syncthreads();
   if (grp == 0 && col < hi) out[col] = (s_acc[0][c] + s_acc[1][c]) + (s_acc[2][c] + s_acc[3][c]);
@@ -431,9 +433,9 @@ static int head_cus() {
 }
 // workgroups of the backward launch: one per CU (its wavefronts keep dW2 in registers, the weights in LDS), never more wavefronts
 // than units of work (groups of n formed rows / tiles of 16 rows); nw = wavefronts per workgroup (4, or 8 for the 512-thread build)
-static int head_bwd_blocks(int64_t rows, int32_t n, bool bc, int nw) {
+static int head_bwd_blocks(int64_t rows, int32_t n, bool bc, int nw, int cus = 0) {
   const int64_t units = bc ? rows / n : (rows + 15) / 16;
-  return (int)std::max<int64_t>(1, std::min<int64_t>((units + nw - 1) / nw, head_cus()));
+  return (int)std::max<int64_t>(1, std::min<int64_t>((units + nw - 1) / nw, cus ? cus : head_cus()));
 }
 static size_t head_bwd_lds(int threads, int32_t n, bool accn) {
   const int nw = threads / 64, tiles = threads == 512 ? 1 : 2;
@@ -441,13 +443,13 @@ static size_t head_bwd_lds(int threads, int32_t n, bool accn) {
 }
 // 512 threads (two wavefronts per SIMD) when its LDS fits a CU and the batch is big enough to give every wavefront work;
 // MAPDN_HEAD_BWD_THREADS = 256 / 512 forces one (A/B measurements)
-static int head_bwd_threads(int64_t rows, int32_t n, bool bc, bool accn) {
+static int head_bwd_threads(int64_t rows, int32_t n, bool bc, bool accn, int cus = 0) {
   const char* e = getenv("MAPDN_HEAD_BWD_THREADS");
   const bool fits = head_bwd_lds(512, n, accn) <= (size_t)160 * 1024;
   if (e && atoi(e) == 256) return 256;
   if (e && atoi(e) == 512 && fits) return 512;
   const int64_t units = bc ? rows / n : (rows + 15) / 16;
-  return fits && units >= (int64_t)head_cus() * 8 ? 512 : 256;
+  return fits && units >= (int64_t)(cus ? cus : head_cus()) * 8 ? 512 : 256;
 }
 static bool head_args_ok(const float* x, const float* per_n, int32_t n, const float* gamma, const float* beta, const float* w2, const float* b2,
                          const float* w3, const float* b3, int64_t rows) {
@@ -475,6 +477,23 @@ extern "C" int64_t mapdn_critic_head_scratch_floats(int64_t rows, int32_t n, int
   return blocks * (mapdn::HP + (formed ? n * 64 : 0));       // one partial per workgroup (whichever launch shape the backward picks)
 }
 
+// the launch head_bwd_launch takes for (rows, n, formed, mode) — host only with cus > 0; cus = 0: the current device's CU count
+extern "C" int mapdn_critic_head_backward_geometry(int64_t rows, int32_t n, int32_t formed, int32_t mode, int32_t cus, int32_t* threads,
+                                                   int32_t* blocks, int32_t* lds_bytes) {
+  if (rows < 1 || rows > 0x7fffffff || mode < 0 || mode > 3 || cus < 0 || (formed && (n < 1 || n > 256 || rows % n))) return MAPDN_E_INVALID;
+  const bool bc = formed != 0;
+  if (!bc) n = 1;
+  const int c = cus ? cus : head_cus();
+  const int nt = head_bwd_threads(rows, n, bc, bc && mode != 2, c);
+  size_t lds = head_bwd_lds(nt, n, bc && mode != 2);
+  if (mode == 0 || mode == 3) lds = std::max(lds, (size_t)(nt / 64) * mapdn::HP * 4);
+  if (lds > (size_t)160 * 1024) return MAPDN_E_INVALID;        // (what the launch refuses)
+  if (threads) *threads = nt;
+  if (blocks) *blocks = head_bwd_blocks(rows, n, bc, nt / 64, c);
+  if (lds_bytes) *lds_bytes = (int32_t)lds;
+  return MAPDN_OK;
+}
+
 template <bool BC, int MODE, int NT>
 static int head_bwd_launch_nt(const mapdn::HeadArgs& a, const float* dv, float* dx, const float* dot_w, float* dact, float* scratch, float* grads,
                               int64_t rows, hipStream_t st, const float* wrow, const float* scale) {
@@ -488,8 +507,8 @@ static int head_bwd_launch_nt(const mapdn::HeadArgs& a, const float* dv, float* 
   const void* fn = (const void*)k_head_bwd<BC, MODE, NT>;
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return MAPDN_E_HIP;
   hipLaunchKernelGGL((k_head_bwd<BC, MODE, NT>), dim3(blocks), dim3(NT), lds, st, a, dv, dx, dot_w, dact, scratch, pstride, (long)rows, wrow, scale);
-  if (MODE == 0 || MODE == 3) hipLaunchKernelGGL(k_head_reduce, dim3((HP + 63) / 64), dim3(256), 0, st, scratch, nw, pstride, 0, HP, grads);
-  if (BC && MODE != 2) hipLaunchKernelGGL(k_head_reduce, dim3(a.n), dim3(256), 0, st, scratch, nw, pstride, HP, HP + a.n * 64, grads);
+  if (MODE == 0 || MODE == 3) hipLaunchKernelGGL(k_head_reduce, dim3((HP + 63) / 64), dim3(256), 0, st, scratch, nw, pstride, 0, HP, HW, grads);
+  if (BC && MODE != 2) hipLaunchKernelGGL(k_head_reduce, dim3(a.n), dim3(256), 0, st, scratch, nw, pstride, HP, HP + a.n * 64, HP + a.n * 64, grads);
   return hipGetLastError() == hipSuccess ? MAPDN_OK : MAPDN_E_HIP;
 }
 template <bool BC, int MODE>

@@ -174,7 +174,10 @@ k_policy_fwd(const float* __restrict__ obs, const float* __restrict__ hid_in, co
 // 16 c + 4 g + q): the D registers of x1^T = W1 obs^T and of gates^T = W x^T line up element by element with the row's hidden state,
 // which is loaded once (as B operand AND for the gate arithmetic) and stored as float4; LayerNorm is 16 in-lane adds + two row swaps;
 // no LDS round trip for the activations and no per-element global accesses (the first form issued 16 scalar loads and 16 scalar
-// stores of the hidden state per lane and tile, plus an LDS transposition of x).  Same LDS weight images, same arithmetic per element.
+// stores of the hidden state per lane and tile, plus an LDS transposition of x).  Same LDS weight images and the same products; the
+// GATES differ: fast_sigmoid / fast_tanh (rowtile.hpp: v_exp_f32 + v_rcp_f32, ~1e-7 absolute) where the first form divides and calls
+// tanhf.  Both forms are held to the float64 modules per geometry and over a 240-step recurrent episode by
+// tests/test_learner_kernel_matrix_gpu.py; the measured errors are the table "Learner kernels against float64" of DESIGN.md.
 template <int PT>
 __global__ void __launch_bounds__(PT)
 k_policy_fwd2(const float* __restrict__ obs, const float* __restrict__ hid_in, const float* __restrict__ w1, const float* __restrict__ b1,
@@ -539,6 +542,16 @@ extern "C" int mapdn_policy_forward_fits(int32_t obs_dim, int32_t id_dim) {
   return obs_dim >= 1 && id_dim >= 0 && policy_geometry(obs_dim, id_dim, pt, il, lds) ? 1 : 0;
 }
 
+// the launch shape policy_forward_launch takes for this width (host only: no device is touched); returns what _fits returns
+extern "C" int mapdn_policy_forward_geometry(int32_t obs_dim, int32_t id_dim, int32_t* threads, int32_t* ids_lds, int32_t* lds_bytes) {
+  int pt = 0, il = 0; size_t lds = 0;
+  const bool ok = obs_dim >= 1 && id_dim >= 0 && policy_geometry(obs_dim, id_dim, pt, il, lds);
+  if (threads) *threads = ok ? pt : 0;
+  if (ids_lds) *ids_lds = ok ? il : 0;
+  if (lds_bytes) *lds_bytes = ok ? (int32_t)lds : 0;
+  return ok ? 1 : 0;
+}
+
 static int policy_forward_launch(const float* obs, const float* hid_in, const float* w1, const float* b1, const float* ln_g,
                                  const float* ln_b, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
                                  const float* w2, const float* b2, float* means, float* hid_out, float* x1_out, int32_t rows, int32_t n_agents,
@@ -549,7 +562,8 @@ static int policy_forward_launch(const float* obs, const float* hid_in, const fl
   size_t lds = 0;
   if (!policy_geometry(obs_dim, id_dim, pt, ids_lds, lds)) return MAPDN_E_INVALID;   // callers ask mapdn_policy_forward_fits first
   // (per call, not once per process: the attribute belongs to the current device)
-  static const bool v1 = [] { const char* e = getenv("MAPDN_POLICY_FWD_V1"); return e && atoi(e) != 0; }();   // A/B: the rounds-2-5 form
+  const char* e_v1 = getenv("MAPDN_POLICY_FWD_V1");           // A/B: the rounds-2-5 form; read per call, so that one process can run both
+  const bool v1 = e_v1 && atoi(e_v1) != 0;
   const void* fn = v1 ? (pt == 512 ? (const void*)k_policy_fwd<512> : (const void*)k_policy_fwd<256>)
                       : (pt == 512 ? (const void*)k_policy_fwd2<512> : (const void*)k_policy_fwd2<256>);
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return MAPDN_E_HIP;

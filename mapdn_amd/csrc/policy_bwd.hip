@@ -26,6 +26,7 @@
 namespace mapdn {
 
 constexpr int PBP = 512;        // partials per workgroup: db_r | db_z | db_ni | db_nh | dgamma | dbeta | dw2 [64 each] | db2 | pad
+constexpr int PBW = 449;        // ... of which k_policy_bwd writes the first PBW; the pad columns of a partial are neither written nor read
 
 struct PolBwdArgs {
   const float* x1; const float* h; const float* dmeans;
@@ -185,15 +186,16 @@ k_policy_bwd(PolBwdArgs p) {
   const float tb = sum_j(ab2);
   if (lane == 0) red[448] = tb;
   __syncthreads();
-  for (int col = tid; col < 449; col += 256) p.partial[(size_t)blockIdx.x * PBP + col] = (sm[col] + sm[PBP + col]) + (sm[2 * PBP + col] + sm[3 * PBP + col]);
+  for (int col = tid; col < PBW; col += 256) p.partial[(size_t)blockIdx.x * PBP + col] = (sm[col] + sm[PBP + col]) + (sm[2 * PBP + col] + sm[3 * PBP + col]);
 }
 
-// out[col] = sum over workgroups of partial[b][col]: four strided sub-sums, then those in order
+// out[col] = sum over workgroups of partial[b][col]: four strided sub-sums, then those in order; the pad columns (PBW .. PBP - 1) of
+// `out` become zero without a read of the partials' pad
 __global__ void __launch_bounds__(256) k_policy_bwd_reduce(const float* __restrict__ partial, int nb, float* __restrict__ out) {
   __shared__ float s_acc[4][64];
   const int c = threadIdx.x & 63, grp = threadIdx.x >> 6, col = blockIdx.x * 64 + c;
   float acc = 0.0f;
-  for (int i = grp; i < nb; i += 4) acc += partial[(size_t)i * PBP + col];
+  if (col < PBW) for (int i = grp; i < nb; i += 4) acc += partial[(size_t)i * PBP + col];
   s_acc[grp][c] = acc;
   __syncthreads();
   if (grp == 0) out[col] = (s_acc[0][c] + s_acc[1][c]) + (s_acc[2][c] + s_acc[3][c]);
@@ -210,7 +212,7 @@ static int polbwd_blocks(int64_t rows) {
 
 extern "C" int64_t mapdn_policy_backward_scratch_floats(int64_t rows) { return rows < 1 ? 0 : (int64_t)polbwd_blocks(rows) * mapdn::PBP; }
 
-// small [512] = db_r | db_z | db_ni | db_nh | dgamma | dbeta | dw2 [64 each] | db2 [1] (+ pad); scratch: mapdn_policy_backward_scratch_floats(rows)
+// small [512] = db_r | db_z | db_ni | db_nh | dgamma | dbeta | dw2 [64 each] | db2 [1] | pad (written as zero); scratch: mapdn_policy_backward_scratch_floats(rows)
 extern "C" int mapdn_policy_backward(const float* dmeans, const float* x1, const float* hid_in, const float* ln_g, const float* ln_b, float ln_eps,
                                      const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* w2, float* dx1,
                                      float* dgates, float* xn, float* small, float* scratch, int64_t rows, void* stream) {
