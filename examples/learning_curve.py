@@ -25,7 +25,7 @@ SCALE = {"case33": 0.8, "case141": 0.6, "case322": 0.8}
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="case33")
-    ap.add_argument("--alg", default="iddpg", choices=["maddpg", "iddpg"])
+    ap.add_argument("--alg", default="iddpg", choices=["maddpg", "iddpg", "matd3"])
     ap.add_argument("--envs", type=int, default=256)
     ap.add_argument("--episodes", type=int, default=300)
     ap.add_argument("--ckpt-every", type=int, default=25)

@@ -456,6 +456,30 @@ int mapdn_critic_head_backward_dot(const float* dv, const float* x, const float*
                                    float eps, const float* w2, const float* b2, const float* w3, const float* b3, const float* dot_w,
                                    float* dact, int64_t rows, void* stream);
 
+/* MATD3's twin critic (models/matd3.py:35-86: ONE critic valued twice, with one more input column that is 0 for values1 and 1 for
+ * values2) behind its first layer as ONE launch over both heads (csrc/critic_twin.hip): the formed row of the central critic,
+ * x1[row] = base[row / n] + per_n[row % n], and x2[row] = x1[row] + flag_col (flag_col [64] = the last column of fc1.weight); both go
+ * through the head of mapdn_critic_head_forward with the same parameters.  Arguments as there (rows a multiple of n, n <= 256); a tile
+ * of rows is formed once and the W2 operand loaded once for both heads.
+ * _forward: v1, v2, vmin [rows] — each may be NULL, not all three; vmin[row] = min(v1[row], v2[row]) (matd3.py:141-142; NaN wins, as torch.min).
+ * _mse: loss = scale[0] * sum_rows wrow[row / n] * 1/2 [(ret[row] - v1[row])^2 + (ret[row] - v2[row])^2] (matd3.py:143-150; wrow [rows / n]
+ *   or NULL: 1) and every gradient of it, without a forward launch:
+ *   dbase [rows / n][64] = dx of both heads summed over each group of n rows;
+ *   grads [4480 + n * 64] = dW2 | dgamma | dbeta | db2 | dw3 | db3 | [4353] the loss | pad to 4416 written as zero — laid out as the grads of
+ *           mapdn_critic_head_mse, every entry summed over both heads — | [4416 .. 4479] d flag_col = the second head's dx summed over all
+ *           rows | [4480 ..] dper_n [n][64] (both heads);
+ *   scratch mapdn_critic_twin_scratch_floats(rows, n) floats (per-workgroup partials, reduced in a fixed order: deterministic; pad rule as above).
+ * _geometry: the launch _mse takes — k_twin_mse<threads> on `blocks` workgroups with `lds_bytes` of dynamic LDS (cus as in
+ *   mapdn_critic_head_backward_geometry); MAPDN_E_INVALID where the per-wavefront [n][64] accumulators do not fit LDS (n > 88). */
+int mapdn_critic_twin_forward(const float* base, const float* per_n, int32_t n, const float* flag_col, const float* gamma, const float* beta,
+                              float eps, const float* w2, const float* b2, const float* w3, const float* b3, float* v1, float* v2,
+                              float* vmin, int64_t rows, void* stream);
+int64_t mapdn_critic_twin_scratch_floats(int64_t rows, int32_t n);
+int mapdn_critic_twin_geometry(int64_t rows, int32_t n, int32_t cus, int32_t* threads, int32_t* blocks, int32_t* lds_bytes);
+int mapdn_critic_twin_mse(const float* ret, const float* wrow, const float* scale, const float* base, const float* per_n, int32_t n,
+                          const float* flag_col, const float* gamma, const float* beta, float eps, const float* w2, const float* b2,
+                          const float* w3, const float* b3, float* dbase, float* grads, float* scratch, int64_t rows, void* stream);
+
 /* The glue of one batched rollout step (models/model.py:197-262) as three launches instead of ~45 one-line PyTorch kernels
  * (csrc/rollout.hip).  Device pointers, contiguous.
  * mapdn_explore_actions: action = tanh(mean + std * eps) (utilities/util.py:57-66; no tanh when tanh_bound == 0), action_pol =

@@ -37,6 +37,7 @@ EXPORTS = (
     "mapdn_explore_actions", "mapdn_rollout_stats", "mapdn_copy_segments",
     "mapdn_policy_forward_train", "mapdn_policy_backward", "mapdn_policy_backward_scratch_floats", "mapdn_get_dc_angles",
     "mapdn_get_nr_kernel", "mapdn_droop_actions", "mapdn_policy_forward_geometry", "mapdn_critic_head_backward_geometry",
+    "mapdn_critic_twin_forward", "mapdn_critic_twin_scratch_floats", "mapdn_critic_twin_geometry", "mapdn_critic_twin_mse",
 )
 
 _pd = C.POINTER(C.c_double)
@@ -227,6 +228,11 @@ def load():
     lib.mapdn_rollout_stats.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, vp]
     lib.mapdn_copy_segments.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64), C.c_int32, vp]
     lib.mapdn_critic_head_mse.argtypes = [vp] * 5 + [C.c_int32, vp, vp, C.c_float] + [vp] * 7 + [C.c_int64, vp]
+    lib.mapdn_critic_twin_forward.argtypes = [vp, vp, C.c_int32, vp, vp, vp, C.c_float] + [vp] * 7 + [C.c_int64, vp]
+    lib.mapdn_critic_twin_scratch_floats.argtypes = [C.c_int64, C.c_int32]
+    lib.mapdn_critic_twin_scratch_floats.restype = C.c_int64
+    lib.mapdn_critic_twin_geometry.argtypes = [C.c_int64, C.c_int32, C.c_int32, _pi, _pi, _pi]
+    lib.mapdn_critic_twin_mse.argtypes = [vp] * 5 + [C.c_int32, vp, vp, vp, C.c_float] + [vp] * 7 + [C.c_int64, vp]
     lib.mapdn_critic_head_backward_dot.argtypes = [vp, vp, vp, C.c_int32, vp, vp, C.c_float] + [vp] * 6 + [C.c_int64, vp]
     lib.mapdn_dense_solve.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp]
     lib.mapdn_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int32), vp]
@@ -372,4 +378,11 @@ def critic_head_backward_geometry(rows: int, n: int, formed: bool, mode: int, cu
     library refuses it"""
     t, b, lds = C.c_int32(), C.c_int32(), C.c_int32()
     rc = load().mapdn_critic_head_backward_geometry(int(rows), int(n), int(bool(formed)), int(mode), int(cus), C.byref(t), C.byref(b), C.byref(lds))
+    return (t.value, b.value, lds.value) if rc == 0 else None
+
+
+def critic_twin_geometry(rows: int, n: int, cus: int = 0):
+    """(threads, blocks, lds_bytes) of the twin critic's loss launch (mapdn_critic_twin_geometry), or None when the library refuses it"""
+    t, b, lds = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = load().mapdn_critic_twin_geometry(int(rows), int(n), int(cus), C.byref(t), C.byref(b), C.byref(lds))
     return (t.value, b.value, lds.value) if rc == 0 else None

@@ -556,3 +556,5 @@ extern "C" int mapdn_critic_head_mse(const float* ret, const float* wrow, const 
   return per_n ? head_bwd_launch<true, 3>(a, ret, dx, nullptr, nullptr, scratch, grads, rows, st, wrow, scale)
                : head_bwd_launch<false, 3>(a, ret, dx, nullptr, nullptr, scratch, grads, rows, st, wrow, scale);
 }
+
+#include "critic_twin.hip"      // MATD3: both heads of the twin critic on one tile (k_twin_*)

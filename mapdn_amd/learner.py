@@ -1,9 +1,9 @@
-"""MADDPG / IDDPG learners for the batched env (BASELINE.json configs[4]).
+"""MADDPG / IDDPG / MATD3 learners for the batched env (BASELINE.json configs[4]).
 
 What is learned, and every quirk of how, follows the reference (file:line cited at each piece):
-`models/maddpg.py`, `models/iddpg.py`, `learning_algorithms/ddpg.py`, `models/model.py`,
+`models/maddpg.py`, `models/iddpg.py`, `models/matd3.py`, `learning_algorithms/ddpg.py`, `models/model.py`,
 `agents/rnn_agent.py`, `critics/mlp_critic.py`, `utilities/trainer.py`, `utilities/util.py`,
-defaults from `args/default.yaml` + `args/alg_args/{maddpg,iddpg}.yaml`.  Module and parameter names
+defaults from `args/default.yaml` + `args/alg_args/{maddpg,iddpg,matd3}.yaml` (the three are equal).  Module and parameter names
 are the reference's (`policy_dicts.0.fc1.weight`, `value_dicts.0.fc3.bias`, `target_net.…`,
 `batchnorm.…`), so a reference `model.pt` (`{"model_state_dict": …}`, train.py:119) loads with
 `strict=True` and vice versa.
@@ -13,7 +13,8 @@ a batch is a dict of device tensors straight from `mapdn_amd.replay`; the centra
 never materialises the reference's [batch, n, n·obs] input (maddpg.py:41-66) — its first layer is
 evaluated as (shared observation term) + (agent-id column) + (joint-action term), with the
 "other agents' actions are detached" rule (maddpg.py:52-58) kept by a zero-valued, gradient-carrying
-own-action term; data-parallel ranks average gradients through one flat RCCL all-reduce per update.
+own-action term; MATD3's twin (matd3.py:35-86: ONE critic valued twice, with one more input column that is 0 or 1) is that
+first layer and the same plus the last column of fc1.weight, both heads in one HIP launch; data-parallel ranks average gradients through one flat RCCL all-reduce per update.
 
 Only the configuration the DDPG family trains with exists: continuous actions, deterministic
 (non-Gaussian) policy head.  Anything else raises.
@@ -419,6 +420,75 @@ class _CriticHeadMSE(torch.autograd.Function):
                 gs[:4096].view(64, 64), gs[4224:4288], gs[4288:4352].view(1, 64), gs[4352:4353], None, None, None)
 
 
+class _CriticTwinMSE(torch.autograd.Function):
+    """MATD3's value loss (models/matd3.py:143-150) on the twin of the central critic,
+        loss = sum_rows w[row] 1/2 [(returns - v1)^2 + (returns - v2)^2],   w[row] = scale * wrow[row / n]   (wrow None: 1),
+    v1 / v2 = the critic head on base[b] + per_n[i] / on the same + flag_col — ONE launch for the loss and every gradient of it
+    (mapdn_critic_twin_mse, csrc/critic_twin.hip): dbase, dper_n and the head's parameter gradients arrive summed over both heads,
+    d flag_col is the second head's dx summed over all rows.  NOT the default route: at config 5's 10 M rows it takes 6.6 ms where two
+    mapdn_critic_head_mse launches take 5.9; DDPGNet.value_mse takes it under MAPDN_TWIN_MSE_KERNEL=1."""
+    launches = 0           # how often the kernel was reached (tests count through the wrapper)
+
+    @staticmethod
+    def forward(ctx, base, per_n, flag, ln_w, ln_b, eps, w2, b2, w3, b3, returns, wrow, scale):
+        from . import _lib
+        lib = _lib.load()
+        x2, pn, fl = base.detach().contiguous(), per_n.detach().contiguous(), flag.detach().contiguous()
+        n = pn.shape[0]
+        rows, dev = x2.shape[0] * n, x2.device
+        prm = tuple(t.detach().contiguous() for t in (ln_w, ln_b, w2, b2, w3.reshape(64), b3.reshape(1)))
+        ret = returns.detach().reshape(rows).contiguous().float()
+        wr = wrow.detach().contiguous().float() if wrow is not None else None
+        sc = scale.detach().reshape(1).contiguous().float()
+        dbase = torch.empty_like(x2)
+        with torch.cuda.device(dev):
+            grads = torch.empty(4480 + n * 64, dtype=torch.float32, device=dev)
+            scratch = torch.empty(max(1, lib.mapdn_critic_twin_scratch_floats(rows, n)), dtype=torch.float32, device=dev)
+            _lib.check(lib.mapdn_critic_twin_mse(ret.data_ptr(), wr.data_ptr() if wr is not None else None, sc.data_ptr(), x2.data_ptr(), pn.data_ptr(), n,
+                                                 fl.data_ptr(), prm[0].data_ptr(), prm[1].data_ptr(), float(eps), prm[2].data_ptr(), prm[3].data_ptr(),
+                                                 prm[4].data_ptr(), prm[5].data_ptr(), dbase.data_ptr(), grads.data_ptr(), scratch.data_ptr(), rows,
+                                                 torch.cuda.current_stream(dev).cuda_stream))
+        _CriticTwinMSE.launches += 1
+        ctx.save_for_backward(dbase, grads)
+        ctx.n = n
+        return grads[4353].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        dbase, grads = ctx.saved_tensors
+        n, need = ctx.n, ctx.needs_input_grad
+        gs = grads * g
+        return (dbase * g if need[0] else None, gs[4480:].view(n, 64) if need[1] else None, gs[4416:4480] if need[2] else None, gs[4096:4160],
+                gs[4160:4224], None, gs[:4096].view(64, 64), gs[4224:4288], gs[4288:4352].view(1, 64), gs[4352:4353], None, None, None)
+
+
+def critic_twin_forward(cr: "MLPCritic", base: torch.Tensor, per_n: torch.Tensor, flag: torch.Tensor, want=("v1", "v2")):
+    """the twin head without autograd (target values, evaluation): {name: [b * n, 1]} for the names in `want` out of v1, v2, vmin —
+    one mapdn_critic_twin_forward launch"""
+    from . import _lib
+    lib = _lib.load()
+    x2, pn, fl = base.detach().contiguous(), per_n.detach().contiguous(), flag.detach().contiguous()
+    n = pn.shape[0]
+    rows, dev, ln = x2.shape[0] * n, x2.device, cr.layernorm
+    prm = tuple(t.detach().contiguous() for t in (ln.weight, ln.bias, cr.fc2.weight, cr.fc2.bias, cr.fc3.weight.reshape(64), cr.fc3.bias.reshape(1)))
+    out = {k: torch.empty(rows, 1, dtype=torch.float32, device=dev) for k in want}
+    ptr = [out[k].data_ptr() if k in out else None for k in ("v1", "v2", "vmin")]
+    with torch.cuda.device(dev):
+        _lib.check(lib.mapdn_critic_twin_forward(x2.data_ptr(), pn.data_ptr(), n, fl.data_ptr(), prm[0].data_ptr(), prm[1].data_ptr(), float(ln.eps),
+                                                 prm[2].data_ptr(), prm[3].data_ptr(), prm[4].data_ptr(), prm[5].data_ptr(), ptr[0], ptr[1], ptr[2], rows,
+                                                 torch.cuda.current_stream(dev).cuda_stream))
+    critic_twin_forward.launches += 1
+    return out
+
+
+critic_twin_forward.launches = 0
+
+
+class twin_pair_mse:
+    """how often MATD3's value loss took the pair of single-head loss launches (tests count the routes)"""
+    launches = 0
+
+
 HEAD_MAX_FORMED_N = 88      # formed rows keep one [n][64] LDS accumulator per wavefront: n <= 88 fits the 160 KB of a CU with four of them
 
 
@@ -429,6 +499,14 @@ def critic_head_ok(cr: "MLPCritic", x: torch.Tensor, rows: int, formed_n: int = 
             and cr.act is F.relu and cr.layernorm.elementwise_affine and cr.layernorm.bias is not None and cr.fc2.in_features == 64
             and cr.fc2.out_features == 64 and cr.fc2.bias is not None and cr.fc3.out_features == 1 and cr.fc3.bias is not None
             and cr.fc2.weight.dtype == torch.float32 and os.environ.get("MAPDN_FUSED_HEAD", "1") != "0")
+
+
+def critic_twin_ok(cr: "MLPCritic", base: torch.Tensor, rows: int, n: int) -> bool:
+    """the one-launch twin head (csrc/critic_twin.hip) covers what critic_head_ok covers for formed rows — the default critic in fp32 on
+    the GPU, enough rows, n <= 88 —; MAPDN_FUSED_TWIN=0 switches it off (the PyTorch route and the single-head kernels remain).  It gates
+    the forward launch (target min, value()) and both fused forms of the value loss; of those the default is two mapdn_critic_head_mse
+    launches, MAPDN_TWIN_MSE_KERNEL=1 takes mapdn_critic_twin_mse (one launch, 12 % slower at 10 M rows: DESIGN section 11)"""
+    return critic_head_ok(cr, base, rows, n) and n >= 1 and os.environ.get("MAPDN_FUSED_TWIN", "1") != "0"
 
 
 def critic_head(cr: "MLPCritic", x: torch.Tensor, per_n: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -584,12 +662,12 @@ class MLPCritic(nn.Module):
 
 
 class DDPGNet(nn.Module):
-    """`MADDPG(Model)` (models/maddpg.py:10) or `IDDPG(Model)` (models/iddpg.py:9): behaviour net holding
+    """`MADDPG(Model)` (models/maddpg.py:10), `IDDPG(Model)` (models/iddpg.py:9) or `MATD3(Model)` (models/matd3.py:10): behaviour net holding
     its target net, the per-agent reward BatchNorm (models/model.py:26) and the DDPG loss."""
 
     def __init__(self, args, alg: str = "maddpg", target_net: Optional["DDPGNet"] = None):
         super().__init__()
-        if alg not in ("maddpg", "iddpg"):
+        if alg not in ("maddpg", "iddpg", "matd3"):
             raise KeyError(alg)                                    # models/model_registry.py:14-25
         self.args, self.alg = args, alg
         self.n_, self.obs_dim, self.act_dim, self.hid_dim = args.agent_num, args.obs_size, args.action_dim, args.hid_size
@@ -599,8 +677,9 @@ class DDPGNet(nn.Module):
         self.batchnorm = nn.BatchNorm1d(n)
         # advantage normalisation: MADDPG re-uses `batchnorm` (maddpg.py:17,120); IDDPG's lives in its DDPG
         # helper object, which is not an nn.Module — so it is NOT part of the state_dict (ddpg.py:10,34)
-        self.__dict__["_adv_batchnorm"] = self.batchnorm if alg == "maddpg" else nn.BatchNorm1d(n)
-        critic_in = (o + a) * n + ids if alg == "maddpg" else o + a + ids     # maddpg.py:20-24, iddpg.py:19-23
+        # (MATD3's is `batchnorm` too: matd3.py:18,146-147)
+        self.__dict__["_adv_batchnorm"] = self.batchnorm if alg in ("maddpg", "matd3") else nn.BatchNorm1d(n)
+        critic_in = {"maddpg": (o + a) * n + ids, "iddpg": o + a + ids, "matd3": (o + a) * n + ids + 1}[alg]   # maddpg.py:20-24, iddpg.py:19-23, matd3.py:20-25
         copies = 1 if args.shared_params else n
         self.value_dicts = nn.ModuleList([MLPCritic(critic_in, 1, args) for _ in range(copies)])
         self.policy_dicts = nn.ModuleList([RNNAgent(o + ids, args) for _ in range(copies)])   # model.py:141-164
@@ -720,7 +799,11 @@ class DDPGNet(nn.Module):
     def value(self, obs: torch.Tensor, act: torch.Tensor, own_action_only: bool = False) -> torch.Tensor:
         """obs [b, n, o], act [b, n, a] -> [b, n, 1].  own_action_only: the caller differentiates with respect to `act` alone (the policy
         loss): the central critic may then skip the gradients of its own parameters, which the policy optimiser never reads."""
-        return self._value_central(obs, act, own_action_only) if self.alg == "maddpg" else self._value_independent(obs, act)
+        if self.alg == "iddpg":
+            return self._value_independent(obs, act)
+        if self.alg == "matd3" and not own_action_only:            # matd3.py:86: [2b, n, 1] = values1 over values2
+            return torch.cat(self._value_twin(obs, act), 0)
+        return self._value_central(obs, act, own_action_only)      # (MATD3's policy loss reads the first head only — flag column times 0)
 
     def _independent_first_layer(self, cr, obs, act):
         """IDDPG's shared critic, first layer on [obs_i | id_i | act_i] (iddpg.py:32-58) as  W_obs obs + id column + W_act act, [b, n, h];
@@ -759,6 +842,29 @@ class DDPGNet(nn.Module):
             return v.view(b, n, -1)
         return torch.stack([cr.trunk(first_layer(cr, obs[:, i], act[:, i], i))[0] for i, cr in enumerate(self.value_dicts)], 1)
 
+    def _central_first_layer(self, cr, obs_all, act_all, own, who, obs_term=None):
+        """first layer of a central critic (maddpg.py:35-79, matd3.py:35-69 with the flag column at 0) = W_obs·obs_all + b1 + W_id[:, i]
+        + W_act·act_all, where the joint action enters detached and agent i's own (act_i - act_i.detach()) — zero in value — restores
+        its gradient path; [b, n, h] for who None, [b, h] for agent `who`.  obs_term: W_obs·obs_all + b1 when the caller holds it."""
+        b, n, o, a = obs_all.shape[0], self.n_, self.obs_dim, self.act_dim
+        ids = n if self.args.agent_id else 0
+        w = cr.fc1.weight
+        w_act = w[:, n * o + ids:n * o + ids + n * a]
+        base = (F.linear(obs_all, w[:, :n * o], cr.fc1.bias) if obs_term is None else obs_term) + F.linear(act_all.detach(), w_act)      # [b, h]
+        if who is None:                                              # all agents at once: [b, n, h]
+            x = base.unsqueeze(1)
+            if ids:
+                x = x + w[:, n * o:n * o + n].t().unsqueeze(0)
+            else:
+                x = x.expand(b, n, -1)
+            if own is not None:
+                x = x + torch.einsum("bna,hna->bnh", own, w_act.reshape(-1, n, a))
+            return x
+        x = base + w[:, n * o + who] if ids else base
+        if own is not None:
+            x = x + F.linear(own[:, who], w_act[:, who * a:(who + 1) * a])
+        return x
+
     def _value_central(self, obs, act, own_action_only=False):
         """MADDPG (maddpg.py:35-79): agent i's critic sees [all obs | id_i | all actions] and only its OWN
         action carries gradient.  First layer = W_obs·obs_all + W_id[:, i] + W_act·act_all, where the joint
@@ -768,24 +874,10 @@ class DDPGNet(nn.Module):
         ids = n if self.args.agent_id else 0
         obs_all, act_all = obs.reshape(b, n * o), act.reshape(b, n * a)
         own = (act - act.detach()) if act.requires_grad else None
+        na = n * o + ids + n * a                                         # end of the action columns (MATD3: the flag column follows)
 
         def first_layer(cr, who):
-            w = cr.fc1.weight
-            w_act = w[:, n * o + ids:]
-            base = F.linear(obs_all, w[:, :n * o], cr.fc1.bias) + F.linear(act_all.detach(), w_act)      # [b, h]
-            if who is None:                                              # all agents at once: [b, n, h]
-                x = base.unsqueeze(1)
-                if ids:
-                    x = x + w[:, n * o:n * o + n].t().unsqueeze(0)
-                else:
-                    x = x.expand(b, n, -1)
-                if own is not None:
-                    x = x + torch.einsum("bna,hna->bnh", own, w_act.reshape(-1, n, a))
-                return x
-            x = base + w[:, n * o + who] if ids else base
-            if own is not None:
-                x = x + F.linear(own[:, who], w_act[:, who * a:(who + 1) * a])
-            return x
+            return self._central_first_layer(cr, obs_all, act_all, own, who)
 
         if self.args.shared_params:
             cr = self.value_dicts[0]
@@ -794,16 +886,16 @@ class DDPGNet(nn.Module):
                 # value), gradient = d/d act[b, i] only, from the kernel; the critic's own parameters are not differentiated
                 w = cr.fc1.weight.detach()
                 with torch.no_grad():
-                    base = F.linear(obs_all, w[:, :n * o], cr.fc1.bias.detach()) + F.linear(act_all.detach(), w[:, n * o + ids:])
+                    base = F.linear(obs_all, w[:, :n * o], cr.fc1.bias.detach()) + F.linear(act_all.detach(), w[:, n * o + ids:na])
                 ln = cr.layernorm
-                v = _CriticHeadOwnAction.apply(act, base, w[:, n * o:n * o + n].t(), w[:, n * o + ids:].t(), ln.weight, ln.bias, ln.eps,
+                v = _CriticHeadOwnAction.apply(act, base, w[:, n * o:n * o + n].t(), w[:, n * o + ids:na].t(), ln.weight, ln.bias, ln.eps,
                                                cr.fc2.weight, cr.fc2.bias, cr.fc3.weight, cr.fc3.bias)
                 return v.view(b, n, 1)
             if ids and own is None and cr.use_ln:
                 # no gradient path through the actions (value loss, target values): the first layer's output is base[b] + id_column[i] —
                 # LayerNorm + ReLU straight from the two small operands, the [b, n, h] sum is never written
                 w = cr.fc1.weight
-                base = tall_linear_w(obs_all, w[:, :n * o], cr.fc1.bias) + tall_linear_w(act_all.detach(), w[:, n * o + ids:])
+                base = tall_linear_w(obs_all, w[:, :n * o], cr.fc1.bias) + tall_linear_w(act_all.detach(), w[:, n * o + ids:na])
                 if critic_head_ok(cr, base, b * n, n):
                     return critic_head(cr, base, w[:, n * o:n * o + n].t()).view(b, n, 1)
                 xn = layernorm_act_bc(cr.layernorm, cr.act, base, w[:, n * o:n * o + n].t())
@@ -812,6 +904,37 @@ class DDPGNet(nn.Module):
             v, _ = cr.trunk(first_layer(cr, None).reshape(b * n, -1))
             return v.view(b, n, 1)
         return torch.stack([cr.trunk(first_layer(cr, i))[0] for i, cr in enumerate(self.value_dicts)], 1)
+
+    def _value_twin(self, obs, act, want="both", obs_term=None):
+        """MATD3 (matd3.py:35-86): the central critic valued twice, its input one column wider — 0 for values1, 1 for values2 —, i.e.
+        first layer = that of _value_central, and the same + fc1.weight[:, -1].  Returns (values1, values2), each [b, n, 1], or with
+        want="min" their minimum (matd3.py:141-142).  obs_term [b, h]: W_obs·obs_all + b1 of the shared critic when the caller holds it
+        (PGTrainer caches it per update round).  Without a gradient path the default critic on the GPU takes ONE launch for both heads."""
+        b, n, o, a = obs.shape[0], self.n_, self.obs_dim, self.act_dim
+        ids = n if self.args.agent_id else 0
+        obs_all, act_all = obs.reshape(b, n * o), act.reshape(b, n * a)
+        own = (act - act.detach()) if act.requires_grad else None
+        out = (lambda v1, v2: torch.minimum(v1, v2)) if want == "min" else (lambda v1, v2: (v1, v2))
+        if self.args.shared_params:
+            cr = self.value_dicts[0]
+            w = cr.fc1.weight
+            flag = w[:, -1]
+            if ids and own is None and cr.use_ln:
+                w_act = w[:, n * o + ids:n * o + ids + n * a]
+                base = (tall_linear_w(obs_all, w[:, :n * o], cr.fc1.bias) if obs_term is None else obs_term) + tall_linear_w(act_all.detach(), w_act)
+                per_n = w[:, n * o:n * o + n].t()
+                if not (torch.is_grad_enabled() and (base.requires_grad or w.requires_grad)) and critic_twin_ok(cr, base, b * n, n):
+                    if want == "min":
+                        return critic_twin_forward(cr, base, per_n, flag, ("vmin",))["vmin"].view(b, n, 1)
+                    r = critic_twin_forward(cr, base, per_n, flag, ("v1", "v2"))
+                    return r["v1"].view(b, n, 1), r["v2"].view(b, n, 1)
+                if critic_head_ok(cr, base, b * n, n):
+                    return out(critic_head(cr, base, per_n).view(b, n, 1), critic_head(cr, base, per_n + flag).view(b, n, 1))
+            x = self._central_first_layer(cr, obs_all, act_all, own, None, obs_term)
+            return out(cr.trunk(x.reshape(b * n, -1))[0].view(b, n, 1), cr.trunk((x + flag).reshape(b * n, -1))[0].view(b, n, 1))
+        xs = [self._central_first_layer(cr, obs_all, act_all, own, i) for i, cr in enumerate(self.value_dicts)]
+        return out(torch.stack([cr.trunk(x)[0] for x, cr in zip(xs, self.value_dicts)], 1),
+                   torch.stack([cr.trunk(x + cr.fc1.weight[:, -1])[0] for x, cr in zip(xs, self.value_dicts)], 1))
 
     def value_mse(self, obs, act, returns, valid=None):
         """mean over (batch, agent) of (returns - Q(obs, act))^2 — the value loss of maddpg.py:122-124 / ddpg.py:36-38 — weighted by
@@ -825,12 +948,14 @@ class DDPGNet(nn.Module):
             cr = self.value_dicts[0]
             w = cr.fc1.weight
             x = per_n = None
-            if self.alg == "maddpg" and ids and cr.use_ln:
-                x = tall_linear_w(obs.reshape(b, n * o), w[:, :n * o], cr.fc1.bias) + tall_linear_w(act.reshape(b, n * self.act_dim), w[:, n * o + ids:])
+            if self.alg in ("maddpg", "matd3") and ids and cr.use_ln:
+                x = tall_linear_w(obs.reshape(b, n * o), w[:, :n * o], cr.fc1.bias) \
+                    + tall_linear_w(act.reshape(b, n * self.act_dim), w[:, n * o + ids:n * o + ids + n * self.act_dim])
                 per_n = w[:, n * o:n * o + n].t()
             elif self.alg == "iddpg":
                 x = self._independent_first_layer(cr, obs, act).reshape(b * n, -1)
-            if x is not None and critic_head_ok(cr, x, b * n, n if per_n is not None else 0):
+            twin = self.alg == "matd3"
+            if x is not None and (critic_twin_ok(cr, x, b * n, n) if twin else critic_head_ok(cr, x, b * n, n if per_n is not None else 0)):
                 if valid is None:
                     scale, wrow = x.new_full((1,), 1.0 / (b * n)), None
                 else:
@@ -838,37 +963,56 @@ class DDPGNet(nn.Module):
                     scale = (1.0 / (vf.sum().clamp(min=1.0) * n)).reshape(1)
                     wrow = vf if per_n is not None else vf.repeat_interleave(n)
                 ln = cr.layernorm
+                if twin and os.environ.get("MAPDN_TWIN_MSE_KERNEL", "0") == "1":      # both heads in ONE launch: measured slower than the pair below
+                    return _CriticTwinMSE.apply(x, per_n, w[:, -1], ln.weight, ln.bias, ln.eps, cr.fc2.weight, cr.fc2.bias, cr.fc3.weight, cr.fc3.bias,
+                                                returns, wrow, scale)
+                if twin:
+                    # matd3.py:143-150, both heads against the same returns: two single-head loss launches, on per_n and on per_n + w_flag,
+                    # each with half the weight; autograd sums the two dbase and hands the second dper_n's column sum to w_flag
+                    twin_pair_mse.launches += 1
+                    head = (ln.weight, ln.bias, ln.eps, cr.fc2.weight, cr.fc2.bias, cr.fc3.weight, cr.fc3.bias, returns, wrow, 0.5 * scale)
+                    return _CriticHeadMSE.apply(x, per_n, *head) + _CriticHeadMSE.apply(x, per_n + w[:, -1], *head)
                 return _CriticHeadMSE.apply(x, per_n, ln.weight, ln.bias, ln.eps, cr.fc2.weight, cr.fc2.bias, cr.fc3.weight, cr.fc3.bias,
                                             returns, wrow, scale)
+        wm = (lambda d2: d2.mean()) if valid is None else \
+            (lambda d2: (d2 * valid.float().view(-1, 1)).sum() / (valid.float().sum().clamp(min=1.0) * d2.shape[1]))
+        if self.alg == "matd3":                          # matd3.py:143-150
+            v1, v2 = self._value_twin(obs, act)
+            return 0.5 * (wm((returns - v1.view(-1, n)).pow(2)) + wm((returns - v2.view(-1, n)).pow(2)))
         values = self.value(obs, act).view(-1, n)
         d2 = (returns - values).pow(2)
         return d2.mean() if valid is None else (d2 * valid.float().view(-1, 1)).sum() / (valid.float().sum().clamp(min=1.0) * d2.shape[1])
 
     # ---- action selection (maddpg.py:81-101 == iddpg.py:60-80; utilities/util.py:52-98) ----------
-    def get_actions(self, state, status, exploration, actions_avail, target=False, last_hid=None, means_grad_only=False):
+    def get_actions(self, state, status, exploration, actions_avail, target=False, last_hid=None, means_grad_only=False, clip=False, noise=None):
         net = self.target_net if (target and self.args.target) else self
         means, log_stds, hiddens = net.policy(state, last_hid, means_grad_only)
         if means.size(-1) > 1:                                   # maddpg.py:85-87 (action_dim > 1 sums over agents)
             means_, log_stds_ = means.sum(dim=1, keepdim=True), log_stds.sum(dim=1, keepdim=True)
         else:
             means_, log_stds_ = means, log_stds
-        actions, log_prob = self._select_action(means_, log_stds_, status, exploration)
+        actions, log_prob = self._select_action(means_, log_stds_, status, exploration, clip, noise)
         restore_mask = 1.0 - (actions_avail == 0).to(actions.dtype)
         return actions, restore_mask * actions, log_prob, (means, log_stds), hiddens
 
-    def _select_action(self, mean, log_std, status, exploration):
+    def _select_action(self, mean, log_std, status, exploration, clip=False, noise=None):
+        """utilities/util.py:52-87.  clip (matd3.py:119-124 passes True for the next actions) is read ONLY without action_enforcebound: the
+        bounded branch ignores it (util.py:58-66), as the reference does.  noise: the standard-normal draw to use instead of drawing."""
         a = self.args
+        draw = (lambda: torch.randn_like(mean)) if noise is None else (lambda: noise.to(mean.dtype).view_as(mean))
         if status == "train":
             if not exploration:
                 return mean, None
             std = log_std.exp()
             if a.action_enforcebound:                            # util.py:57-66
-                x_t = mean + std * torch.randn_like(mean)        # Normal(mean, std).rsample()
+                x_t = mean + std * draw()                        # Normal(mean, std).rsample()
                 y_t = torch.tanh(x_t)
                 log_prob = -((x_t - mean) ** 2) / (2 * std ** 2) - log_std - math.log(math.sqrt(2 * math.pi))
                 return y_t, log_prob - torch.log(1 - y_t.pow(2) + 1e-6)
-            x_t = std * torch.randn_like(mean)                   # util.py:67-76
+            x_t = std * draw()                                   # util.py:67-76
             log_prob = -(x_t ** 2) / (2 * std ** 2) - log_std - math.log(math.sqrt(2 * math.pi))
+            if clip:
+                return mean + torch.clamp(x_t, min=-a.clip_c, max=a.clip_c), log_prob
             return mean + x_t, log_prob
         if status == "test":                                     # util.py:80-87
             return (torch.tanh(mean) if a.action_enforcebound else mean), None
@@ -898,10 +1042,27 @@ class DDPGNet(nn.Module):
         y = (reward - mean.to(reward.dtype)) * torch.rsqrt(var.to(reward.dtype) + bn.eps)
         return y * bn.weight + bn.bias
 
+    def smoothed_actions(self, means: torch.Tensor, avail: torch.Tensor, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """MATD3's next actions from the next-state policy means (matd3.py:119-124: exploration=True, clip=True — see _select_action for
+        what clip does), with the restore mask of get_actions; one [bs, n, 1] draw unless `noise` is given"""
+        assert means.size(-1) == 1, "one action per agent (get_actions sums wider means and log_stds over the agents: not built here)"
+        log_std = torch.full_like(means, math.log(self.args.fixed_policy_std)) if self.args.shared_params else torch.zeros_like(means)
+        actions, _ = self._select_action(means, log_std, "train", True, True, noise)
+        return (1.0 - (avail == 0).to(actions.dtype)) * actions
+
+    def _matd3_next_values(self, batch: Batch) -> torch.Tensor:
+        """min(Q1', Q2') of the target critic at the smoothed next actions (matd3.py:119-142).  The noise is drawn anew in every call, after
+        the noise-free policy forward; batch["next_noise"] [bs, n, 1] replaces the draw.  PGTrainer hands over what does not change within
+        an update round: the policy means (next_mean_cached) and the target critic's observation term (next_obs_term_cached)."""
+        pol = self if self.args.double_q else (self.target_net if self.args.target else self)
+        means = batch["next_mean_cached"] if "next_mean_cached" in batch else pol.policy(batch["next_state"], batch["hid"], True)[0]
+        next_actions = self.smoothed_actions(means, batch["action_avail"], batch.get("next_noise"))
+        return self.target_net._value_twin(batch["next_state"], next_actions, "min", batch.get("next_obs_term_cached"))
+
     def get_loss(self, batch: Batch, want=("policy", "value")):
         """batch: state/next_state [bs, n, o], action/action_avail [bs, n, a], reward [bs, n], done [bs, 1],
         last_hid/hid [bs, n, h] float32 (the `unpack_data` tensors, model.py:304-319); optional `valid`
-        [bs] weights the means (1 everywhere = the reference).  Returns (policy_loss, value_loss,
+        [bs] weights the means (1 everywhere = the reference); MATD3: optional `next_noise` [bs, n, 1] (see _matd3_next_values).  Returns (policy_loss, value_loss,
         (means, log_stds)); a loss not in `want` is None and its forward passes are skipped."""
         n = self.n_
         state, actions, next_state = batch["state"], batch["action"], batch["next_state"]
@@ -918,9 +1079,17 @@ class DDPGNet(nn.Module):
             if self.args.normalize_advantages:
                 advantages = self._adv_batchnorm.to(advantages.device)(advantages)
             policy_loss = wmean(-advantages)
+        elif self.alg == "matd3" and self.args.normalize_advantages and self.batchnorm.training:
+            # the reference evaluates BOTH losses in every get_loss call (matd3.py:113-151), so with normalize_advantages its `batchnorm`
+            # — part of the state_dict — sees the advantages in the value updates too: keep its running statistics the reference's
+            with torch.no_grad():
+                _, a_pol, _, _, _ = self.get_actions(state, "train", False, avail, False, last_hid, means_grad_only=True)
+                self._adv_batchnorm.to(a_pol.device)(self.value(state, a_pol, own_action_only=True).view(-1, n))
         if "value" in want:
             with torch.no_grad():
-                if "next_value_cached" in batch:                 # PGTrainer precomputed both for the whole replay ring (same values)
+                if self.alg == "matd3":
+                    next_values = self._matd3_next_values(batch).view(-1, n)
+                elif "next_value_cached" in batch:                 # PGTrainer precomputed both for the whole replay ring (same values)
                     next_values = batch["next_value_cached"].view(-1, n)
                 else:
                     if "next_action_cached" in batch:
@@ -1097,7 +1266,12 @@ class PGTrainer:
         same kernels on the same inputs as the per-epoch passes, same values — and handed out with the sampled windows as two more
         (temporary) fields of the replay store.  Only when that is the cheaper order: a ring longer than the transitions the round's
         value epochs sample (the reference's own defaults: a 5000-transition ring against 10 x 32) keeps the per-epoch passes.
-        MAPDN_CACHE_NEXT_ACTIONS=0 disables it."""
+        MAPDN_CACHE_NEXT_ACTIONS=0 disables it.
+        MATD3's target is NOT constant over the round: it values tanh(mean + std·eps) with eps drawn anew in every get_loss call
+        (matd3.py:119-142), so no action and no value is cached — one draw would otherwise serve every epoch that samples the transition.
+        Cached is what is deterministic: the next-state policy MEANS and, for the shared critic, the target's observation term
+        W_obs·next_obs_all + b1 ([ring, h]; the K = n·o product is the expensive part of the target's first layer).  The smoothed action,
+        the K = n action term and the twin head are formed per epoch (DDPGNet._matd3_next_values)."""
         rb, net, a = self.replay_buffer, self.behaviour_net, self.args
         if not isinstance(rb, TransReplayBuffer) or os.environ.get("MAPDN_CACHE_NEXT_ACTIONS", "1") == "0" or len(rb) == 0:
             return False
@@ -1107,6 +1281,8 @@ class PGTrainer:
         n_ring = rb.size if len(rb) == rb.size else len(rb)      # (the ring fills from position 0: a partly filled ring is [0, len))
         if n_ring > int(a.value_update_epochs) * int(a.batch_size):
             return False
+        if net.alg == "matd3":
+            return self._cache_matd3(n_ring)
         cache = torch.empty_like(st["action"])
         values = torch.empty(st["action"].shape[0], net.n_, dtype=torch.float32, device=cache.device) if a.target else None
         chunk = max(int(a.batch_size), 1)
@@ -1128,6 +1304,31 @@ class PGTrainer:
             st["next_value_cached"] = values
         return True
 
+    def _cache_matd3(self, n_ring: int) -> bool:
+        rb, net, a = self.replay_buffer, self.behaviour_net, self.args
+        st = rb.store
+        pol = net if a.double_q else (net.target_net if a.target else net)
+        tgt = net.target_net
+        means = torch.empty_like(st["action"])
+        cr = tgt.value_dicts[0]
+        term = torch.empty(st["action"].shape[0], cr.fc1.out_features, dtype=cr.fc1.weight.dtype, device=means.device) if a.shared_params else None
+        chunk, no = max(int(a.batch_size), 1), net.n_ * net.obs_dim
+        with torch.no_grad():
+            for lo in range(0, n_ring, chunk):
+                hi = min(lo + chunk, n_ring)
+                means[lo:hi] = pol.policy(st["next_state"][lo:hi], st["hid"][lo:hi], True)[0]
+                if term is not None:
+                    term[lo:hi] = F.linear(st["next_state"][lo:hi].reshape(hi - lo, no), cr.fc1.weight[:, :no], cr.fc1.bias)
+            if rb.window:
+                m = min(rb.window, n_ring)
+                means[rb.size:rb.size + m] = means[:m]
+                if term is not None:
+                    term[rb.size:rb.size + m] = term[:m]
+        st["next_mean_cached"] = means
+        if term is not None:
+            st["next_obs_term_cached"] = term
+        return True
+
     def transition_update(self, trans: Batch, stat):
         """models/model.py:39-70 with replay=True, mixer=False"""
         a = self.args
@@ -1142,6 +1343,8 @@ class PGTrainer:
                 if cached:
                     self.replay_buffer.store.pop("next_action_cached", None)
                     self.replay_buffer.store.pop("next_value_cached", None)
+                    self.replay_buffer.store.pop("next_mean_cached", None)
+                    self.replay_buffer.store.pop("next_obs_term_cached", None)
             for _ in range(a.policy_update_epochs):
                 self.policy_replay_process(stat)
         if a.target and self.steps % a.target_update_freq == 0:
