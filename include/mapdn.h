@@ -480,6 +480,20 @@ int mapdn_critic_twin_mse(const float* ret, const float* wrow, const float* scal
                           const float* flag_col, const float* gamma, const float* beta, float eps, const float* w2, const float* b2,
                           const float* w3, const float* b3, float* dbase, float* grads, float* scratch, int64_t rows, void* stream);
 
+/* COMA's counterfactual baseline (models/coma.py:139-151: the critic valued sample_size more times per transition and agent, with that
+ * agent's action replaced by a draw from its policy, and the values averaged) as ONE forward launch (csrc/critic_cf.hip).  The first
+ * layer is linear in the actions, so with one action per agent a sampled row is the taken row plus a rank-1 term:
+ *   baseline[row] = 1/S sum_s head(x[row] + delta[s][row] * act_col[row % n]),  head = that of mapdn_critic_head_forward;
+ * x [rows][64] the first layer at the TAKEN actions, act_col [n][64] = fc1's action columns (row i: the column of agent i's action),
+ * delta [S][rows] = sampled - taken action of the row's own agent.  The sampled row is formed by one fused multiply-add per element;
+ * the sum runs in the order s = 0 .. S - 1 and is divided by S.  v0 [rows] or NULL: head(x[row]), the value at the taken actions
+ * (coma.py:152) from the same read of x.  The tile of x, its act_col rows and the W2 operand are loaded once for all S samples.
+ * No gradient exists: the advantage is detached (coma.py:182).  Device pointers, contiguous; rows < 2^31 (need not be a multiple of n),
+ * 1 <= S <= 64, n >= 1; anything else is MAPDN_E_INVALID and nothing is launched. */
+int mapdn_critic_head_counterfactual(const float* x, int32_t n, const float* act_col, const float* delta, int32_t S, const float* gamma,
+                                     const float* beta, float eps, const float* w2, const float* b2, const float* w3, const float* b3,
+                                     float* baseline, float* v0, int64_t rows, void* stream);
+
 /* The glue of one batched rollout step (models/model.py:197-262) as three launches instead of ~45 one-line PyTorch kernels
  * (csrc/rollout.hip).  Device pointers, contiguous.
  * mapdn_explore_actions: action = tanh(mean + std * eps) (utilities/util.py:57-66; no tanh when tanh_bound == 0), action_pol =

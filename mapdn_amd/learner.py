@@ -1,9 +1,9 @@
-"""MADDPG / IDDPG / MATD3 learners for the batched env (BASELINE.json configs[4]).
+"""MADDPG / IDDPG / MATD3 / COMA learners for the batched env (BASELINE.json configs[4]).
 
 What is learned, and every quirk of how, follows the reference (file:line cited at each piece):
-`models/maddpg.py`, `models/iddpg.py`, `models/matd3.py`, `learning_algorithms/ddpg.py`, `models/model.py`,
+`models/maddpg.py`, `models/iddpg.py`, `models/matd3.py`, `models/coma.py`, `learning_algorithms/ddpg.py`, `models/model.py`,
 `agents/rnn_agent.py`, `critics/mlp_critic.py`, `utilities/trainer.py`, `utilities/util.py`,
-defaults from `args/default.yaml` + `args/alg_args/{maddpg,iddpg,matd3}.yaml` (the three are equal).  Module and parameter names
+defaults from `args/default.yaml` + `args/alg_args/{maddpg,iddpg,matd3,coma}.yaml` (equal but for COMA's `sample_size`).  Module and parameter names
 are the reference's (`policy_dicts.0.fc1.weight`, `value_dicts.0.fc3.bias`, `target_net.â€¦`,
 `batchnorm.â€¦`), so a reference `model.pt` (`{"model_state_dict": â€¦}`, train.py:119) loads with
 `strict=True` and vice versa.
@@ -14,7 +14,9 @@ never materialises the reference's [batch, n, nÂ·obs] input (maddpg.py:41-66) â€
 evaluated as (shared observation term) + (agent-id column) + (joint-action term), with the
 "other agents' actions are detached" rule (maddpg.py:52-58) kept by a zero-valued, gradient-carrying
 own-action term; MATD3's twin (matd3.py:35-86: ONE critic valued twice, with one more input column that is 0 or 1) is that
-first layer and the same plus the last column of fc1.weight, both heads in one HIP launch; data-parallel ranks average gradients through one flat RCCL all-reduce per update.
+first layer and the same plus the last column of fc1.weight, both heads in one HIP launch; COMA's counterfactual baseline (coma.py:139-151:
+the critic valued sample_size more times with one agent's action redrawn) is one HIP launch over the first layer's output, a sampled row
+being the taken row plus a rank-1 term; data-parallel ranks average gradients through one flat RCCL all-reduce per update.
 
 Only the configuration the DDPG family trains with exists: continuous actions, deterministic
 (non-Gaussian) policy head.  Anything else raises.
@@ -34,7 +36,7 @@ from ._lib import INFO_KEYS
 from .replay import TransReplayBuffer
 from .rollout import translate_action
 
-# args/default.yaml:6-51 merged with args/alg_args/maddpg.yaml (== iddpg.yaml)
+# args/default.yaml:6-51 merged with args/alg_args/maddpg.yaml (== iddpg.yaml); sample_size: args/alg_args/coma.yaml (read by COMA only)
 ALG_DEFAULTS = dict(
     gumbel_softmax=False, epsilon_softmax=False, softmax_eps=None, episodic=False, cuda=True, grad_clip_eps=1.0,
     save_model_freq=40, replay_warmup=0, policy_lrate=1.0e-4, value_lrate=1.0e-4, mixer_lrate=None, target=True,
@@ -44,7 +46,7 @@ ALG_DEFAULTS = dict(
     action_enforcebound=True, double_q=True, clip_c=1.0, gamma=0.99, hid_size=64, continuous=True,
     normalize_advantages=False, train_episodes_num=400, behaviour_update_freq=60, target_update_freq=120,
     policy_update_epochs=1, value_update_epochs=10, mixer_update_epochs=None, reward_normalisation=True,
-    eval_freq=20, num_eval_episodes=10,
+    eval_freq=20, num_eval_episodes=10, sample_size=10,
 )
 
 Batch = Dict[str, torch.Tensor]
@@ -509,6 +511,37 @@ def critic_twin_ok(cr: "MLPCritic", base: torch.Tensor, rows: int, n: int) -> bo
     return critic_head_ok(cr, base, rows, n) and n >= 1 and os.environ.get("MAPDN_FUSED_TWIN", "1") != "0"
 
 
+def critic_cf_ok(cr: "MLPCritic", x: torch.Tensor, rows: int, act_dim: int) -> bool:
+    """the one-launch counterfactual baseline (csrc/critic_cf.hip) covers what critic_head_ok covers for rows that are read â€” the default
+    critic in fp32 on the GPU, enough rows â€” with one action per agent; MAPDN_FUSED_CF=0 switches it off (the PyTorch loop over the samples
+    remains)"""
+    return act_dim == 1 and critic_head_ok(cr, x, rows) and os.environ.get("MAPDN_FUSED_CF", "1") != "0"
+
+
+def critic_counterfactual(cr: "MLPCritic", x: torch.Tensor, act_col: torch.Tensor, delta: torch.Tensor, want_v0: bool = True):
+    """(baseline [rows], v0 [rows] or None) without autograd: baseline = mean over s of the head on x + delta[s] * act_col[row % n], v0 = the
+    head on x â€” one mapdn_critic_head_counterfactual launch.  x [rows, 64], act_col [n, 64], delta [S, rows]."""
+    from . import _lib
+    lib = _lib.load()
+    x2, col, dl = x.detach().contiguous(), act_col.detach().contiguous(), delta.detach().contiguous()
+    rows, dev, ln = x2.shape[0], x2.device, cr.layernorm
+    if dl.dim() != 2 or dl.shape[1] != rows or col.dim() != 2 or col.shape[1] != 64 or dl.dtype != torch.float32 or col.dtype != torch.float32:
+        raise ValueError("critic_counterfactual: x [rows, 64], act_col [n, 64], delta [S, rows], float32")
+    prm = tuple(t.detach().contiguous() for t in (ln.weight, ln.bias, cr.fc2.weight, cr.fc2.bias, cr.fc3.weight.reshape(64), cr.fc3.bias.reshape(1)))
+    baseline = torch.empty(rows, dtype=torch.float32, device=dev)
+    v0 = torch.empty(rows, dtype=torch.float32, device=dev) if want_v0 else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.mapdn_critic_head_counterfactual(x2.data_ptr(), col.shape[0], col.data_ptr(), dl.data_ptr(), dl.shape[0], prm[0].data_ptr(),
+                                                        prm[1].data_ptr(), float(ln.eps), prm[2].data_ptr(), prm[3].data_ptr(), prm[4].data_ptr(),
+                                                        prm[5].data_ptr(), baseline.data_ptr(), v0.data_ptr() if v0 is not None else None, rows,
+                                                        torch.cuda.current_stream(dev).cuda_stream))
+    critic_counterfactual.launches += 1
+    return baseline, v0
+
+
+critic_counterfactual.launches = 0           # how often the kernel was reached (tests count the routes)
+
+
 def critic_head(cr: "MLPCritic", x: torch.Tensor, per_n: Optional[torch.Tensor] = None) -> torch.Tensor:
     ln = cr.layernorm
     return _CriticHead.apply(x, per_n, ln.weight, ln.bias, ln.eps, cr.fc2.weight, cr.fc2.bias, cr.fc3.weight, cr.fc3.bias)
@@ -662,12 +695,14 @@ class MLPCritic(nn.Module):
 
 
 class DDPGNet(nn.Module):
-    """`MADDPG(Model)` (models/maddpg.py:10), `IDDPG(Model)` (models/iddpg.py:9) or `MATD3(Model)` (models/matd3.py:10): behaviour net holding
-    its target net, the per-agent reward BatchNorm (models/model.py:26) and the DDPG loss."""
+    """`MADDPG(Model)` (models/maddpg.py:10), `IDDPG(Model)` (models/iddpg.py:9), `MATD3(Model)` (models/matd3.py:10): behaviour net
+    holding its target net, the per-agent reward BatchNorm (models/model.py:26) and the DDPG loss.  `COMA(Model)` is the subclass COMANet."""
+
+    ALGS = ("maddpg", "iddpg", "matd3")         # the algorithms this class is; COMANet (below) is "coma"; net_class(alg) picks the class
 
     def __init__(self, args, alg: str = "maddpg", target_net: Optional["DDPGNet"] = None):
         super().__init__()
-        if alg not in ("maddpg", "iddpg", "matd3"):
+        if alg not in self.ALGS:
             raise KeyError(alg)                                    # models/model_registry.py:14-25
         self.args, self.alg = args, alg
         self.n_, self.obs_dim, self.act_dim, self.hid_dim = args.agent_num, args.obs_size, args.action_dim, args.hid_size
@@ -677,9 +712,10 @@ class DDPGNet(nn.Module):
         self.batchnorm = nn.BatchNorm1d(n)
         # advantage normalisation: MADDPG re-uses `batchnorm` (maddpg.py:17,120); IDDPG's lives in its DDPG
         # helper object, which is not an nn.Module â€” so it is NOT part of the state_dict (ddpg.py:10,34)
-        # (MATD3's is `batchnorm` too: matd3.py:18,146-147)
-        self.__dict__["_adv_batchnorm"] = self.batchnorm if alg in ("maddpg", "matd3") else nn.BatchNorm1d(n)
-        critic_in = {"maddpg": (o + a) * n + ids, "iddpg": o + a + ids, "matd3": (o + a) * n + ids + 1}[alg]   # maddpg.py:20-24, iddpg.py:19-23, matd3.py:20-25
+        # (MATD3's is `batchnorm` too: matd3.py:18,146-147; COMA's as well: coma.py:19,183-184)
+        self.__dict__["_adv_batchnorm"] = self.batchnorm if alg in ("maddpg", "matd3", "coma") else nn.BatchNorm1d(n)
+        critic_in = {"maddpg": (o + a) * n + ids, "iddpg": o + a + ids, "matd3": (o + a) * n + ids + 1,
+                     "coma": (n + 1) * o + n * a + ids}[alg]       # maddpg.py:20-24, iddpg.py:19-23, matd3.py:20-25, coma.py:21-27
         copies = 1 if args.shared_params else n
         self.value_dicts = nn.ModuleList([MLPCritic(critic_in, 1, args) for _ in range(copies)])
         self.policy_dicts = nn.ModuleList([RNNAgent(o + ids, args) for _ in range(copies)])   # model.py:141-164
@@ -801,6 +837,8 @@ class DDPGNet(nn.Module):
         loss): the central critic may then skip the gradients of its own parameters, which the policy optimiser never reads."""
         if self.alg == "iddpg":
             return self._value_independent(obs, act)
+        if self.alg == "coma":
+            return self._value_coma(obs, act)
         if self.alg == "matd3" and not own_action_only:            # matd3.py:86: [2b, n, 1] = values1 over values2
             return torch.cat(self._value_twin(obs, act), 0)
         return self._value_central(obs, act, own_action_only)      # (MATD3's policy loss reads the first head only â€” flag column times 0)
@@ -954,6 +992,8 @@ class DDPGNet(nn.Module):
                 per_n = w[:, n * o:n * o + n].t()
             elif self.alg == "iddpg":
                 x = self._independent_first_layer(cr, obs, act).reshape(b * n, -1)
+            elif self.alg == "coma" and cr.use_ln:                 # coma.py:179-180: the same loss on rows that are read, as IDDPG's
+                x = self._coma_first_layer(cr, obs, act).reshape(b * n, -1)
             twin = self.alg == "matd3"
             if x is not None and (critic_twin_ok(cr, x, b * n, n) if twin else critic_head_ok(cr, x, b * n, n if per_n is not None else 0)):
                 if valid is None:
@@ -1062,7 +1102,8 @@ class DDPGNet(nn.Module):
     def get_loss(self, batch: Batch, want=("policy", "value")):
         """batch: state/next_state [bs, n, o], action/action_avail [bs, n, a], reward [bs, n], done [bs, 1],
         last_hid/hid [bs, n, h] float32 (the `unpack_data` tensors, model.py:304-319); optional `valid`
-        [bs] weights the means (1 everywhere = the reference); MATD3: optional `next_noise` [bs, n, 1] (see _matd3_next_values).  Returns (policy_loss, value_loss,
+        [bs] weights the means (1 everywhere = the reference); MATD3: optional `next_noise` [bs, n, 1] (see _matd3_next_values); COMA:
+        optional `cf_noise` [S, bs, n, a] (see _coma_policy_loss; its loss is coma.py:128-191, the value half shared with the others).  Returns (policy_loss, value_loss,
         (means, log_stds)); a loss not in `want` is None and its forward passes are skipped."""
         n = self.n_
         state, actions, next_state = batch["state"], batch["action"], batch["next_state"]
@@ -1073,7 +1114,9 @@ class DDPGNet(nn.Module):
         wmean = (lambda t: t.mean()) if valid is None else \
             (lambda t: (t * valid.float().view(-1, 1)).sum() / (valid.float().sum().clamp(min=1.0) * t.shape[1]))
         policy_loss = value_loss = action_out = None
-        if "policy" in want:
+        if self.alg == "coma":
+            policy_loss, action_out = self._coma_policy_loss(batch, wmean, "policy" in want)
+        elif "policy" in want:
             _, actions_pol, _, action_out, _ = self.get_actions(state, "train", False, avail, False, last_hid, means_grad_only=True)
             advantages = self.value(state, actions_pol, own_action_only=True).view(-1, n)
             if self.args.normalize_advantages:
@@ -1103,6 +1146,119 @@ class DDPGNet(nn.Module):
         return policy_loss, value_loss, action_out
 
 
+class COMANet(DDPGNet):
+    """`COMA(Model)` (models/coma.py:11): the policy, target handling, reward BatchNorm and value half of the loss are DDPGNet's; the
+    critic input, the counterfactual baseline and the policy loss are its own.  On-policy: PGTrainer empties the replay ring after every
+    update round (models/model.py:53-56)."""
+    ALGS = ("coma",)
+
+    def __init__(self, args, alg: str = "coma", target_net: Optional["COMANet"] = None):
+        if alg in self.ALGS and int(args.sample_size) < 2:
+            # coma.py:44 tells the sampled actions [S b, n, n a] from taken ones [b, n, a] by the batch dimension: equal at S == 1
+            raise ValueError(f"sample_size must be at least 2 for COMA (got {args.sample_size})")
+        super().__init__(args, alg, target_net)
+
+    def _coma_first_layer(self, cr, obs, act, who=None):
+        """first layer of COMA's critic on [all obs (n o) | own obs (o) | ids (n) | joint action (n a)] (coma.py:24, 53-80) as
+        W_allÂ·obs_all + b1 + W_actÂ·act_all (per batch element) + W_ownÂ·obs[b, i] + id column (per agent): [b, n, h] for who None, [b, h]
+        for agent `who`; never built at input width.  Every action carries gradient (coma.py has no detach in value())."""
+        b, n, o, a = obs.shape[0], self.n_, self.obs_dim, self.act_dim
+        ids = n if self.args.agent_id else 0
+        w = cr.fc1.weight
+        na = (n + 1) * o + ids
+        base = tall_linear_w(obs.reshape(b, n * o), w[:, :n * o], cr.fc1.bias) + tall_linear_w(act.reshape(b, n * a), w[:, na:na + n * a])      # [b, h]
+        if who is not None:
+            x = base + F.linear(obs[:, who], w[:, n * o:(n + 1) * o])
+            return x + w[:, (n + 1) * o + who] if ids else x
+        x = tall_linear_w(obs.reshape(b * n, o), w[:, n * o:(n + 1) * o]).view(b, n, -1) + base.unsqueeze(1)
+        if ids:
+            x = x + w[:, (n + 1) * o:na].t().unsqueeze(0)
+        return x
+
+    def _value_coma(self, obs, act):
+        """coma.py:43-104 on taken actions (obs and act of the same batch size): [b, n, 1]"""
+        b, n = obs.shape[0], self.n_
+        if self.args.shared_params:
+            cr = self.value_dicts[0]
+            return cr.trunk(self._coma_first_layer(cr, obs, act).reshape(b * n, -1))[0].view(b, n, 1)
+        return torch.stack([cr.trunk(self._coma_first_layer(cr, obs, act, i))[0] for i, cr in enumerate(self.value_dicts)], 1)
+
+    def sampled_actions(self, means: torch.Tensor, log_stds: torch.Tensor, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """coma.py:139-143: th.normal(means, std) for sample_size repeats of the batch, [S, b, n, a] â€” ONE draw per get_loss call, taken as
+        means + std * randn (the same numbers from the same generator state; tests/golden/make_coma_golden.py asserts it), or with
+        `noise` [S, b, n, a] in the place of randn"""
+        S = int(self.args.sample_size)
+        eps = torch.randn((S,) + tuple(means.shape), dtype=means.dtype, device=means.device) if noise is None else noise.to(means.dtype).view((S,) + tuple(means.shape))
+        return means.detach().unsqueeze(0) + log_stds.detach().exp().unsqueeze(0) * eps
+
+    @torch.no_grad()
+    def counterfactual(self, obs: torch.Tensor, act: torch.Tensor, sampled: torch.Tensor):
+        """(baselines [b, n], values [b, n]) of coma.py:144-152: baselines[b, i] = mean over s of Q_i(obs, act with agent i's action
+        replaced by sampled[s, b, i]); values = Q(obs, act).  The critic's first layer is linear in the actions, so the replaced input
+        is the taken one plus (sampled - act)[b, i] Â· W_act[:, i]: the [S b, n, (n + 1) o + n + n a] input of the reference is never
+        built.  The default critic on the GPU with one action per agent: ONE launch for all samples and the values
+        (critic_counterfactual); otherwise a loop over the samples through the PyTorch modules."""
+        b, n, o, a = obs.shape[0], self.n_, self.obs_dim, self.act_dim
+        ids = n if self.args.agent_id else 0
+        na = (n + 1) * o + ids
+        S = sampled.shape[0]
+        delta = sampled - act.unsqueeze(0)                                           # [S, b, n, a]
+        if self.args.shared_params:
+            cr = self.value_dicts[0]
+            x = self._coma_first_layer(cr, obs, act).reshape(b * n, -1)
+            w_act = cr.fc1.weight[:, na:na + n * a]
+            if critic_cf_ok(cr, x, b * n, a):
+                base, v0 = critic_counterfactual(cr, x, w_act.t(), delta.reshape(S, b * n))
+                return base.view(b, n), v0.view(b, n)
+            own_col = w_act.reshape(-1, n, a)                                        # [h, n, a]: agent i's own action columns
+            values = cr.trunk(x)[0].view(b, n)
+            total = torch.zeros_like(values)
+            for s in range(S):
+                total += cr.trunk(x + torch.einsum("bna,hna->bnh", delta[s], own_col).reshape(b * n, -1))[0].view(b, n)
+            return total / S, values
+        xs = [self._coma_first_layer(cr, obs, act, i) for i, cr in enumerate(self.value_dicts)]
+        values = torch.stack([cr.trunk(x)[0] for x, cr in zip(xs, self.value_dicts)], 1).view(b, n)
+        total = torch.zeros_like(values)
+        for s in range(S):
+            total += torch.stack([cr.trunk(x + F.linear(delta[s][:, i], cr.fc1.weight[:, na + i * a:na + (i + 1) * a]))[0]
+                                  for i, (x, cr) in enumerate(zip(xs, self.value_dicts))], 1).view(b, n)
+        return total / S, values
+
+    def _coma_policy_loss(self, batch: Batch, wmean, want_loss: bool):
+        """coma.py:131-152, 181-190: policy_loss = -mean(advantages * log_prob), advantages = (Q(s, a) - baseline).detach() (through
+        `batchnorm` with normalize_advantages), log_prob of the STORED action under N(mean, std), masked by the available actions.
+        The sample_size draws are taken in every call, as the reference does (coma.py:143 runs for the value update too);
+        batch["cf_noise"] [S, bs, n, a] replaces the standard-normal draw.  want_loss False (a value update): only what the call
+        changes besides the loss is done â€” the draw, and with normalize_advantages the running statistics of `batchnorm`."""
+        n = self.n_
+        state, actions, avail = batch["state"], batch["action"], batch["action_avail"]
+        if not want_loss and not (self.args.normalize_advantages and self.batchnorm.training):
+            if batch.get("cf_noise") is None:                    # the call's one draw, so that the generator goes the reference's way
+                torch.randn((int(self.args.sample_size),) + tuple(actions.shape), dtype=torch.float32, device=actions.device)
+            return None, None
+        with torch.set_grad_enabled(want_loss and torch.is_grad_enabled()):
+            means, log_stds, _ = self.policy(state, batch["last_hid"], means_grad_only=True)
+        sampled = self.sampled_actions(means, log_stds, batch.get("cf_noise"))
+        baselines, values = self.counterfactual(state, actions, sampled)
+        advantages = (values - baselines).detach()
+        if self.args.normalize_advantages:
+            advantages = self._adv_batchnorm.to(advantages.device)(advantages)
+        if not want_loss:
+            return None, None
+        std = log_stds.exp()
+        log_prob = -((actions - means) ** 2) / (2 * std ** 2) - log_stds - math.log(math.sqrt(2 * math.pi))      # util.py:44-46
+        log_prob = ((1.0 - (avail == 0).to(log_prob.dtype)) * log_prob).sum(-1).view(-1, n)
+        return wmean(-advantages * log_prob), (means, log_stds)
+
+
+def net_class(alg: str):
+    """the module class of an algorithm name (models/model_registry.py:14-25); KeyError for a name that is not built"""
+    for c in (DDPGNet, COMANet):
+        if alg in c.ALGS:
+            return c
+    raise KeyError(alg)
+
+
 def normal_entropy(log_stds: torch.Tensor) -> torch.Tensor:
     """Normal(mean, std).entropy().mean() (utilities/util.py:37-38)"""
     return (0.5 + 0.5 * math.log(2 * math.pi) + log_stds).mean()
@@ -1121,8 +1277,9 @@ class PGTrainer:
     def __init__(self, args, alg: str, env, device=None, data_parallel: Optional[bool] = None):
         self.args, self.env = args, env
         self.device = torch.device(device if device is not None else getattr(env, "device", "cpu"))
-        target = DDPGNet(args, alg).to(self.device) if args.target else None
-        self.behaviour_net = DDPGNet(args, alg, target).to(self.device)
+        Net = net_class(alg)
+        target = Net(args, alg).to(self.device) if args.target else None
+        self.behaviour_net = Net(args, alg, target).to(self.device)
         self.replay_buffer = TransReplayBuffer(int(args.replay_buffer_size), device=self.device, window=int(args.batch_size))   # windows are views
         rms = dict(alpha=0.99, eps=1e-5)                                                   # trainer.py:26-27
         self.policy_optimizer = torch.optim.RMSprop(self.behaviour_net.policy_dicts.parameters(), lr=args.policy_lrate, **rms)
@@ -1347,6 +1504,8 @@ class PGTrainer:
                     self.replay_buffer.store.pop("next_obs_term_cached", None)
             for _ in range(a.policy_update_epochs):
                 self.policy_replay_process(stat)
+            if self.behaviour_net.alg == "coma":                 # on-policy: the ring is emptied after every update round (model.py:53-56)
+                self.replay_buffer.clear()
         if a.target and self.steps % a.target_update_freq == 0:
             with self._phase("target_update"):
                 self.behaviour_net.update_target()

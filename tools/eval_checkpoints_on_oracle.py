@@ -24,7 +24,7 @@ SCALE = {"case33": 0.8, "case141": 0.6, "case322": 0.8}
 
 def run_episode(job):
     kind, path, meta, ep = job
-    from mapdn_amd.learner import DDPGNet, make_alg_args
+    from mapdn_amd.learner import make_alg_args, net_class
     from mapdn_amd.netspec import make_case
     from mapdn_amd.rollout import translate_action
     from oracle.env_restated import INFO_KEYS, VoltageControlOracle
@@ -39,7 +39,8 @@ def run_episode(job):
     pol = None
     if kind == "ckpt":
         args = make_alg_args(n, o, 1, SCALE[case], 0.0)
-        pol = DDPGNet(args, meta["alg"], DDPGNet(args, meta["alg"]))      # behaviour net + its target, as PGTrainer builds it
+        Net = net_class(meta["alg"])
+        pol = Net(args, meta["alg"], Net(args, meta["alg"]))      # behaviour net + its target, as PGTrainer builds it
         pol.load_state_dict(torch.load(path, map_location="cpu")["model_state_dict"])
         pol.eval()
         hid = pol.init_hidden(1)
