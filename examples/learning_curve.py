@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Seeded IDDPG / MADDPG / MATD3 / COMA training on the batched GPU env with periodic checkpoints — the evidence run that the learner
+"""Seeded IDDPG / MADDPG / MATD3 / COMA / MAAC training on the batched GPU env with periodic checkpoints — the evidence run that the learner
 learns.  Checkpoints (`model.pt` layout, train.py:119) are evaluated afterwards on the CPU ORACLE env
 (tools/eval_checkpoints_on_oracle.py), i.e. outside the product.
 
@@ -25,7 +25,7 @@ SCALE = {"case33": 0.8, "case141": 0.6, "case322": 0.8}
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="case33")
-    ap.add_argument("--alg", default="iddpg", choices=["maddpg", "iddpg", "matd3", "coma"])
+    ap.add_argument("--alg", default="iddpg", choices=["maddpg", "iddpg", "matd3", "coma", "maac"])
     ap.add_argument("--envs", type=int, default=256)
     ap.add_argument("--episodes", type=int, default=300)
     ap.add_argument("--ckpt-every", type=int, default=25)
@@ -44,7 +44,7 @@ def main():
     env = VoltageControlBatch(net, prof, dict(episode_limit=240, action_scale=SCALE[a.case], action_bias=0.0,
                                                voltage_barrier_type=a.voltage_barrier, seed=a.seed), n_envs=a.envs, device=dev, copy=True)
     batch = 32 * a.envs
-    args = make_alg_args(env.n_agents, env.obs_size, env.n_actions, SCALE[a.case], 0.0, max_steps=240, batch_size=batch,
+    args = make_alg_args(env.n_agents, env.obs_size, env.n_actions, SCALE[a.case], 0.0, alg=a.alg, max_steps=240, batch_size=batch,
                          replay_buffer_size=a.envs * 160, num_eval_episodes=a.envs)
     tr = PGTrainer(args, a.alg, env, device=dev)
     meta = dict(case=a.case, alg=a.alg, envs=a.envs, seed=a.seed, barrier=a.voltage_barrier, batch_size=batch,

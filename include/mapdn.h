@@ -494,6 +494,23 @@ int mapdn_critic_head_counterfactual(const float* x, int32_t n, const float* act
                                      const float* beta, float eps, const float* w2, const float* b2, const float* w3, const float* b3,
                                      float* baseline, float* v0, int64_t rows, void* stream);
 
+/* The core of MAAC's attention critic (critics/maac_critic.py:116-136, 156-157) as one forward and one backward launch
+ * (csrc/critic_attn.hip).  sel, key, val [B][n][64] f32; head h owns columns h d .. (h + 1) d, d = 64 / H.  For sample b, agent i, head h:
+ *   logit_ij = sel_i . key_j over j != i,  p_ij = softmax_j(logit_ij / sqrt(d)) (row maximum subtracted),  out_i = sum_j p_ij val_j,
+ *   logit_sq[i][h] = sum_b sum_{j != i} logit_ij^2   ([n][H]; the regulariser is 1e-3 sum_h logit_sq[i][h] / (B (n - 1))).
+ * _forward: out [B][n][64], logit_sq [n][H]; scratch: mapdn_attention_scratch_floats(B, n, H) floats (one partial of logit_sq per
+ *   workgroup, summed in a fixed order: deterministic, no atomics).  Nothing but the operands is saved for the backward.
+ * _backward: recomputes the probabilities; dout [B][n][64], dlogit_sq [n][H] (enters as 2 logit_ij dlogit_sq[i][h]) -> dsel, dkey, dval
+ *   [B][n][64].
+ * Device pointers, contiguous, the [B][n][64] ones 16-byte aligned.  B >= 1, 2 <= n <= mapdn_attention_max_agents() (48), H in {1, 2, 4},
+ * B n 64 < 2^31; a null or misaligned pointer or any other shape is MAPDN_E_INVALID and nothing is launched. */
+int mapdn_attention_forward(const float* sel, const float* key, const float* val, int64_t B, int32_t n, int32_t H, float* out,
+                            float* logit_sq, float* scratch, void* stream);
+int mapdn_attention_backward(const float* dout, const float* dlogit_sq, const float* sel, const float* key, const float* val, int64_t B,
+                             int32_t n, int32_t H, float* dsel, float* dkey, float* dval, void* stream);
+int64_t mapdn_attention_scratch_floats(int64_t B, int32_t n, int32_t H);
+int32_t mapdn_attention_max_agents(void);
+
 /* The glue of one batched rollout step (models/model.py:197-262) as three launches instead of ~45 one-line PyTorch kernels
  * (csrc/rollout.hip).  Device pointers, contiguous.
  * mapdn_explore_actions: action = tanh(mean + std * eps) (utilities/util.py:57-66; no tanh when tanh_bound == 0), action_pol =

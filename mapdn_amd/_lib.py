@@ -39,6 +39,7 @@ EXPORTS = (
     "mapdn_get_nr_kernel", "mapdn_droop_actions", "mapdn_policy_forward_geometry", "mapdn_critic_head_backward_geometry",
     "mapdn_critic_twin_forward", "mapdn_critic_twin_scratch_floats", "mapdn_critic_twin_geometry", "mapdn_critic_twin_mse",
     "mapdn_critic_head_counterfactual",
+    "mapdn_attention_forward", "mapdn_attention_backward", "mapdn_attention_scratch_floats", "mapdn_attention_max_agents",
 )
 
 _pd = C.POINTER(C.c_double)
@@ -235,6 +236,11 @@ def load():
     lib.mapdn_critic_twin_geometry.argtypes = [C.c_int64, C.c_int32, C.c_int32, _pi, _pi, _pi]
     lib.mapdn_critic_twin_mse.argtypes = [vp] * 5 + [C.c_int32, vp, vp, vp, C.c_float] + [vp] * 7 + [C.c_int64, vp]
     lib.mapdn_critic_head_counterfactual.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_float] + [vp] * 6 + [C.c_int64, vp]
+    lib.mapdn_attention_forward.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp]
+    lib.mapdn_attention_backward.argtypes = [vp] * 5 + [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp]
+    lib.mapdn_attention_scratch_floats.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    lib.mapdn_attention_scratch_floats.restype = C.c_int64
+    lib.mapdn_attention_max_agents.argtypes = []
     lib.mapdn_critic_head_backward_dot.argtypes = [vp, vp, vp, C.c_int32, vp, vp, C.c_float] + [vp] * 6 + [C.c_int64, vp]
     lib.mapdn_dense_solve.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp]
     lib.mapdn_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int32), vp]

@@ -1,4 +1,4 @@
-"""End-to-end MADDPG / IDDPG / MATD3 / COMA loop on the batched GPU env (BASELINE.json configs[4]; SURVEY 8(f) rows 1-3 wired together): rollout of B envs
+"""End-to-end MADDPG / IDDPG / MATD3 / COMA / MAAC loop on the batched GPU env (BASELINE.json configs[4]; SURVEY 8(f) rows 1-3 wired together): rollout of B envs
 per GPU through the HIP hot path, GPU-resident replay, DDPG updates.  One function, used by examples/train_ddpg.py (the CLI) and by
 bench.py's `e2e` block (so that a driver run records the loop the env feeds, not only the env).
 
@@ -41,7 +41,7 @@ def run(case="case322", envs=8192, alg="maddpg", episodes=3, max_steps=240, inte
             total = updates_per_env_step * update_freq * envs / batch
             p_ep = max(1, round(total / 11)); v_ep = max(1, round(total - p_ep))
     ratio = (v_ep + p_ep) * batch / (update_freq * envs)
-    args = make_alg_args(env.n_agents, env.obs_size, env.n_actions, SCALE[case], 0.0, max_steps=max_steps,
+    args = make_alg_args(env.n_agents, env.obs_size, env.n_actions, SCALE[case], 0.0, alg=alg, max_steps=max_steps,
                          batch_size=batch, replay_buffer_size=envs * max(replay_steps, 2 * batch // envs),
                          behaviour_update_freq=update_freq, target_update_freq=2 * update_freq, num_eval_episodes=envs,
                          value_update_epochs=v_ep, policy_update_epochs=p_ep)

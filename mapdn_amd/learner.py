@@ -1,4 +1,4 @@
-"""MADDPG / IDDPG / MATD3 / COMA learners for the batched env (BASELINE.json configs[4]).
+"""MADDPG / IDDPG / MATD3 / COMA / MAAC learners for the batched env (BASELINE.json configs[4]).
 
 What is learned, and every quirk of how, follows the reference (file:line cited at each piece):
 `models/maddpg.py`, `models/iddpg.py`, `models/matd3.py`, `models/coma.py`, `learning_algorithms/ddpg.py`, `models/model.py`,
@@ -19,7 +19,9 @@ the critic valued sample_size more times with one agent's action redrawn) is one
 being the taken row plus a rank-1 term; data-parallel ranks average gradients through one flat RCCL all-reduce per update.
 
 Only the configuration the DDPG family trains with exists: continuous actions, deterministic
-(non-Gaussian) policy head.  Anything else raises.
+(non-Gaussian) policy head — and MAAC's (models/maac.py, critics/maac_critic.py, agents/rnn_agent_gaussian.py: Gaussian head, one
+attention critic whose attention over the other agents is one HIP launch each way, csrc/critic_attn.hip), reached through
+make_alg_args(..., alg="maac").  Anything else raises.
 """
 from __future__ import annotations
 
@@ -47,26 +49,52 @@ ALG_DEFAULTS = dict(
     normalize_advantages=False, train_episodes_num=400, behaviour_update_freq=60, target_update_freq=120,
     policy_update_epochs=1, value_update_epochs=10, mixer_update_epochs=None, reward_normalisation=True,
     eval_freq=20, num_eval_episodes=10, sample_size=10,
+    attend_heads=1, norm_in=False, soft=True, reward_scale=100,      # args/alg_args/maac.yaml (read by MAAC only)
 )
+ALG_YAML = {"maac": dict(gaussian_policy=True, action_enforcebound=True)}      # what an algorithm's yaml sets beyond the defaults above
 
 Batch = Dict[str, torch.Tensor]
 
 
 def make_alg_args(agent_num: int, obs_size: int, action_dim: int = 1, action_scale: float = 0.8,
-                  action_bias: float = 0.0, **overrides) -> SimpleNamespace:
-    """The `args` namedtuple train.py:64-67 assembles, as a namespace."""
+                  action_bias: float = 0.0, alg: Optional[str] = None, **overrides) -> SimpleNamespace:
+    """The `args` namedtuple train.py:64-67 assembles, as a namespace.  alg: the algorithm whose yaml is merged over the defaults before the
+    overrides (train.py:60-62) — needed for "maac" alone, whose yaml switches the Gaussian policy head on."""
     d = dict(ALG_DEFAULTS)
     unknown = set(overrides) - set(d)
     if unknown:
         raise KeyError(f"unknown algorithm argument(s): {sorted(unknown)}")
+    d.update(ALG_YAML.get(alg, {}))
     d.update(overrides)
     d.update(agent_num=int(agent_num), obs_size=int(obs_size), action_dim=int(action_dim),
              action_scale=float(action_scale), action_bias=float(action_bias))
     a = SimpleNamespace(**d)
+    if alg == "maac":
+        _maac_args_ok(a)
+        return a
     if not a.continuous or a.gaussian_policy or a.mixer or a.episodic or a.agent_type != "rnn":
         raise NotImplementedError("the DDPG-family learners here cover continuous, non-Gaussian, recurrent, "
                                   "transition-update training (args/alg_args/maddpg.yaml, iddpg.yaml)")
     return a
+
+
+def _maac_args_ok(a) -> None:
+    """what MAACNet builds: continuous actions, the Gaussian recurrent agent, one action per agent, at least two agents (with one the
+    reference's th.stack([]) over the other agents' keys raises: critics/maac_critic.py:127-128), transition updates, no mixer"""
+    if not a.continuous:
+        raise NotImplementedError("MAAC: continuous=False (discrete actions) is not built")
+    if a.agent_type != "rnn":
+        raise NotImplementedError(f"MAAC: agent_type={a.agent_type!r} is not built (only 'rnn': agents/rnn_agent_gaussian.py)")
+    if not a.gaussian_policy:
+        raise NotImplementedError("MAAC: gaussian_policy=False is not built (models/maac.py always constructs the Gaussian agent)")
+    if a.action_dim != 1:
+        raise NotImplementedError(f"MAAC: action_dim={a.action_dim} is not built (one action per agent)")
+    if a.agent_num < 2:
+        raise ValueError(f"MAAC: agent_num={a.agent_num}: the attention critic attends over the OTHER agents, it needs at least 2")
+    if a.mixer or a.episodic:
+        raise NotImplementedError("MAAC: mixer / episodic training is not built")
+    if int(a.attend_heads) < 1 or a.hid_size % int(a.attend_heads):
+        raise ValueError(f"MAAC: attend_heads={a.attend_heads} must divide hid_size={a.hid_size}")
 
 
 def _activation(name: str):
@@ -1251,9 +1279,299 @@ class COMANet(DDPGNet):
         return wmean(-advantages * log_prob), (means, log_stds)
 
 
+# ---- MAAC (models/maac.py, critics/maac_critic.py, agents/rnn_agent_gaussian.py) ---------------------------------------------------
+def attention_loop_reference(sel: torch.Tensor, key: torch.Tensor, val: torch.Tensor, H: int):
+    """critics/maac_critic.py:120-136 restated literally: per head and per agent, the keys / values of the OTHER agents stacked and
+    permuted to [b, d, n - 1], softmax over the last dimension.  (out [b, n, hid], logit_sq [n, H] = the sum of the squared unscaled
+    logits.)  What the batched route and the kernels are tested against; never on a training path."""
+    b, n, hid = sel.shape
+    d = hid // H
+    outs, lsq = [[] for _ in range(n)], sel.new_zeros(n, H)
+    for h in range(H):
+        cols = slice(h * d, (h + 1) * d)
+        for i in range(n):
+            keys = [key[:, j, cols] for j in range(n) if j != i]
+            values = [val[:, j, cols] for j in range(n) if j != i]
+            logits = torch.matmul(sel[:, i, cols].reshape(b, 1, -1), torch.stack(keys).permute(1, 2, 0))          # [b, 1, n - 1]
+            weights = F.softmax(logits / math.sqrt(d), dim=2)
+            outs[i].append((torch.stack(values).permute(1, 2, 0) * weights).sum(dim=2))
+            lsq[i, h] = (logits ** 2).sum()
+    return torch.stack([torch.cat(o, 1) for o in outs], 1), lsq
+
+
+def attention_core_torch(sel: torch.Tensor, key: torch.Tensor, val: torch.Tensor, H: int):
+    """the same as ONE masked softmax over [b, H, n, n] (the diagonal — an agent's own key — masked out): two batched products, no loop
+    over heads or agents.  The CPU route, and the GPU route where the kernels do not apply."""
+    b, n, hid = sel.shape
+    d = hid // H
+    q, k, v = (t.reshape(b, n, H, d).transpose(1, 2) for t in (sel, key, val))                 # [b, H, n, d]
+    logits = q @ k.transpose(-1, -2)                                                           # [b, H, n, n]
+    own = torch.eye(n, dtype=torch.bool, device=sel.device)
+    p = F.softmax((logits / math.sqrt(d)).masked_fill(own, float("-inf")), dim=-1)
+    out = (p @ v).transpose(1, 2).reshape(b, n, hid)
+    return out, logits.masked_fill(own, 0.0).square().sum(dim=(0, 3)).t()                      # [n, H]
+
+
+class _AttentionCore(torch.autograd.Function):
+    """(out, logit_sq) of attention_core_torch as one HIP launch forward and one backward (libmapdn_hip.so: mapdn_attention_*,
+    csrc/critic_attn.hip): a workgroup holds one sample's three [n, 64] operands and its [H, n, n] scores in LDS; the backward recomputes
+    the probabilities, so only the operands are saved."""
+    launches = 0           # how often the forward kernel was reached (tests count the routes)
+
+    @staticmethod
+    def forward(ctx, sel, key, val, H):
+        from . import _lib
+        lib = _lib.load()
+        s, k, v = sel.contiguous(), key.contiguous(), val.contiguous()
+        B, n, dev = s.shape[0], s.shape[1], s.device
+        out = torch.empty_like(s)
+        lsq = torch.empty(n, H, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            scratch = torch.empty(max(1, lib.mapdn_attention_scratch_floats(B, n, H)), dtype=torch.float32, device=dev)
+            _lib.check(lib.mapdn_attention_forward(s.data_ptr(), k.data_ptr(), v.data_ptr(), B, n, H, out.data_ptr(), lsq.data_ptr(),
+                                                   scratch.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        _AttentionCore.launches += 1
+        ctx.save_for_backward(s, k, v)
+        ctx.H = H
+        return out, lsq
+
+    @staticmethod
+    def backward(ctx, dout, dlsq):
+        from . import _lib
+        lib = _lib.load()
+        s, k, v = ctx.saved_tensors
+        B, n, dev = s.shape[0], s.shape[1], s.device
+        do, dl = dout.contiguous(), dlsq.contiguous()
+        ds, dk, dv = torch.empty_like(s), torch.empty_like(s), torch.empty_like(s)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mapdn_attention_backward(do.data_ptr(), dl.data_ptr(), s.data_ptr(), k.data_ptr(), v.data_ptr(), B, n, ctx.H,
+                                                    ds.data_ptr(), dk.data_ptr(), dv.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return ds, dk, dv, None
+
+
+ATTN_MAX_N = 48            # csrc/critic_attn.hip AT_MAX_N (mapdn_attention_max_agents()): one sample's operands and scores must fit a CU's LDS
+
+
+def attention_ok(sel: torch.Tensor, H: int) -> bool:
+    """the attention kernels cover fp32 on the GPU, hidden size 64, 2 <= n <= ATTN_MAX_N agents, 1 / 2 / 4 heads; MAPDN_FUSED_ATTN=0
+    switches them off (the batched PyTorch route remains)"""
+    return (sel.is_cuda and sel.dtype == torch.float32 and sel.dim() == 3 and sel.shape[-1] == 64 and 2 <= sel.shape[1] <= ATTN_MAX_N
+            and H in (1, 2, 4) and sel.shape[0] >= 1 and sel.shape[0] * sel.shape[1] * 64 < 2 ** 31 and os.environ.get("MAPDN_FUSED_ATTN", "1") != "0")
+
+
+def attention_core(sel: torch.Tensor, key: torch.Tensor, val: torch.Tensor, H: int):
+    if attention_ok(sel, H) and key.dtype == torch.float32 and val.dtype == torch.float32:
+        return _AttentionCore.apply(sel, key, val, H)
+    return attention_core_torch(sel, key, val, H)
+
+
+class GaussianRNNAgent(nn.Module):
+    """fc1 -> LayerNorm -> act -> GRUCell -> (mean, log_std) with log_std squashed by tanh into [LOG_STD_MIN, LOG_STD_MAX]
+    (agents/rnn_agent_gaussian.py:6-41).  PyTorch modules (the fused LayerNorm of RNNAgent where it applies): the one-launch policy
+    kernels have a single output head and are not extended to two."""
+
+    def __init__(self, input_shape: int, args):
+        super().__init__()
+        self.hid_size = args.hid_size
+        self.fc1 = nn.Linear(input_shape, args.hid_size)
+        if args.layernorm:
+            self.layernorm = nn.LayerNorm(args.hid_size)
+        self.rnn = nn.GRUCell(args.hid_size, args.hid_size)
+        self.mean = nn.Linear(args.hid_size, args.action_dim)
+        self.log_std = nn.Linear(args.hid_size, args.action_dim)
+        self.use_ln = bool(args.layernorm)
+        self.act = _activation(args.hid_activation)
+        self.lo, self.hi = float(args.LOG_STD_MIN), float(args.LOG_STD_MAX)
+
+    def trunk(self, x: torch.Tensor, hidden: torch.Tensor):
+        """x: pre-activation of fc1, [rows, hid]"""
+        x = layernorm_act(self.layernorm, self.act, x) if self.use_ln else self.act(x)
+        h = gru_cell_tall(self.rnn, x, hidden.reshape(-1, self.hid_size))
+        log_std = self.lo + 0.5 * (self.hi - self.lo) * (torch.tanh(tall_linear(self.log_std, h)) + 1)
+        return tall_linear(self.mean, h), log_std, h
+
+    def forward(self, inputs, hidden):
+        return self.trunk(self.fc1(inputs), hidden)
+
+
+def _named_sequential(**mods) -> nn.Sequential:
+    seq = nn.Sequential()
+    for k, m in mods.items():
+        if m is not None:
+            seq.add_module(k, m)
+    return seq
+
+
+class AttentionCritic(nn.Module):
+    """critics/maac_critic.py:8-161 for continuous actions, with the reference's module tree (critic_encoders.{i}.enc_fc1,
+    critics.{i}.critic_fc1 / critic_fc2, biases.{i}.bias_fc1 / bias_fc2, state_encoders.{i}.s_enc_fc1, key_extractors.{h},
+    selector_extractors.{h}, value_extractors.{h}.0; enc_bn / s_enc_bn under norm_in), so that its state_dict is the reference's.
+    forward: [b, n, o], [b, n, a] -> (q - bias [b, n], regulariser [n]).  The per-agent encoders, critics and biases run batched over
+    their stacked parameters; the attention over the other agents is attention_core (HIP kernels, or one masked softmax)."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.hidden_dim, self.attend_heads, self.nagents = args.hid_size, int(args.attend_heads), args.agent_num
+        assert self.hidden_dim % self.attend_heads == 0
+        sdim, adim, hid = args.obs_size, args.action_dim, args.hid_size
+        bn = (lambda k: nn.BatchNorm1d(k, affine=False)) if args.norm_in else (lambda k: None)
+        self.norm_in = bool(args.norm_in)
+        self.critic_encoders, self.critics, self.biases, self.state_encoders = nn.ModuleList(), nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
+        for _ in range(self.nagents):
+            self.critic_encoders.append(_named_sequential(enc_bn=bn(sdim + adim), enc_fc1=nn.Linear(sdim + adim, hid), enc_nl=nn.LeakyReLU()))
+            self.critics.append(_named_sequential(critic_fc1=nn.Linear(2 * hid, hid), critic_nl=nn.LeakyReLU(), critic_fc2=nn.Linear(hid, 1)))
+            self.biases.append(_named_sequential(bias_fc1=nn.Linear(hid, hid), bias_nl=nn.LeakyReLU(), bias_fc2=nn.Linear(hid, 1)))
+            self.state_encoders.append(_named_sequential(s_enc_bn=bn(sdim), s_enc_fc1=nn.Linear(sdim, hid), s_enc_nl=nn.LeakyReLU()))
+        d = hid // self.attend_heads
+        self.key_extractors, self.selector_extractors, self.value_extractors = nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
+        for _ in range(self.attend_heads):
+            self.key_extractors.append(nn.Linear(hid, d, bias=False))
+            self.selector_extractors.append(nn.Linear(hid, d, bias=False))
+            self.value_extractors.append(nn.Sequential(nn.Linear(hid, d), nn.LeakyReLU()))
+
+    @staticmethod
+    def _per_agent(x: torch.Tensor, layers) -> torch.Tensor:
+        """layers[i](x[:, i]) for every agent i as one batched product over the stacked weights: [b, n, in] -> [b, n, out]"""
+        w = torch.stack([m.weight for m in layers])                                        # [n, out, in]
+        return torch.einsum("bni,noi->bno", x, w) + torch.stack([m.bias for m in layers])
+
+    def forward(self, obs: torch.Tensor, act: torch.Tensor):
+        b, n, H = obs.shape[0], self.nagents, self.attend_heads
+        sa = torch.cat((obs, act), dim=-1)
+        s_in = obs
+        if self.norm_in:                                                                    # plain per-agent BatchNorm1d(affine=False) modules
+            sa = torch.stack([enc.enc_bn(sa[:, i]) for i, enc in enumerate(self.critic_encoders)], 1)
+            s_in = torch.stack([enc.s_enc_bn(obs[:, i]) for i, enc in enumerate(self.state_encoders)], 1)
+        sa_enc = F.leaky_relu(self._per_agent(sa, [e.enc_fc1 for e in self.critic_encoders]))          # [b, n, hid]
+        s_enc = F.leaky_relu(self._per_agent(s_in, [e.s_enc_fc1 for e in self.state_encoders]))
+        # head h's extractor fills columns h d .. (h + 1) d: the H extractors of a kind are one [hid, hid] product
+        key = F.linear(sa_enc, torch.cat([m.weight for m in self.key_extractors], 0))
+        val = F.leaky_relu(F.linear(sa_enc, torch.cat([m[0].weight for m in self.value_extractors], 0),
+                                    torch.cat([m[0].bias for m in self.value_extractors], 0)))
+        sel = F.linear(s_enc, torch.cat([m.weight for m in self.selector_extractors], 0))
+        other, logit_sq = attention_core(sel, key, val, H)                                  # [b, n, hid], [n, H]
+        x = F.leaky_relu(self._per_agent(torch.cat((sa_enc, other), -1), [c.critic_fc1 for c in self.critics]))
+        q = self._per_agent(x, [c.critic_fc2 for c in self.critics]).squeeze(-1)            # [b, n]
+        y = F.leaky_relu(self._per_agent(s_enc, [c.bias_fc1 for c in self.biases]))
+        bias = self._per_agent(y, [c.bias_fc2 for c in self.biases]).squeeze(-1)
+        reg = 1e-3 * logit_sq.sum(1) / float(b * (n - 1))                                   # 1e-3 sum over heads of mean(logit^2): maac_critic.py:156-157
+        return q - bias, reg
+
+
+class MAACNet(DDPGNet):
+    """`MAAC(Model)` (models/maac.py:10-121): Gaussian recurrent agents, ONE attention critic for all agents, the soft actor-critic loss.
+    Target handling, reward BatchNorm, initialisation and the Gaussian branch of select_action are DDPGNet's.  Off-policy: the replay ring
+    is kept between update rounds (models/model.py:53-56 clears it for COMA, IAC, IPPO and MAPPO only)."""
+    ALGS = ("maac",)
+
+    def __init__(self, args, alg: str = "maac", target_net: Optional["MAACNet"] = None):
+        nn.Module.__init__(self)
+        if alg not in self.ALGS:
+            raise KeyError(alg)
+        _maac_args_ok(args)
+        self.args, self.alg = args, alg
+        self.n_, self.obs_dim, self.act_dim, self.hid_dim = args.agent_num, args.obs_size, args.action_dim, args.hid_size
+        self._fused_fits = None
+        ids = self.n_ if args.agent_id else 0
+        self.batchnorm = nn.BatchNorm1d(self.n_)                   # rewards AND advantages (maac.py:18, 112-113; model.py:317-318)
+        self.__dict__["_adv_batchnorm"] = self.batchnorm
+        self.value_dicts = nn.ModuleList([AttentionCritic(args)])                                          # maac.py:40-41
+        self.policy_dicts = nn.ModuleList([GaussianRNNAgent(self.obs_dim + ids, args) for _ in range(1 if args.shared_params else self.n_)])
+        self.apply(self._init_weights)
+        if target_net is not None:
+            self.target_net = target_net
+            self.reload_params_to_target()
+
+    def policy(self, obs: torch.Tensor, last_hid: torch.Tensor, means_grad_only: bool = False):
+        """models/model.py:101-139 with gaussian_policy: obs [b, n, o], last_hid [b, n, h] -> means, log_stds [b, n, a], hiddens [b, n, h]"""
+        b, n, o = obs.shape[0], self.n_, self.obs_dim
+        if self.args.shared_params:
+            ag = self.policy_dicts[0]
+            w = ag.fc1.weight
+            if _tall_ok(obs, b * n, w):
+                x = _TallLinear.apply(obs.reshape(b * n, o), w[:, :o], ag.fc1.bias).view(b, n, -1)
+            else:
+                x = F.linear(obs, w[:, :o], ag.fc1.bias)
+            if self.args.agent_id:
+                x = x + w[:, o:].t().unsqueeze(0)                        # one-hot id i selects column o + i
+            m, ls, h = ag.trunk(x.reshape(b * n, -1), last_hid)
+            return m.view(b, n, -1), ls.view(b, n, -1), h.view(b, n, -1)
+        ms, lss, hs = [], [], []
+        for i, ag in enumerate(self.policy_dicts):
+            w = ag.fc1.weight
+            x = F.linear(obs[:, i], w[:, :o], ag.fc1.bias)
+            if self.args.agent_id:
+                x = x + w[:, o + i]
+            m, ls, h = ag.trunk(x, last_hid[:, i])
+            ms.append(m); lss.append(ls); hs.append(h)
+        return torch.stack(ms, 1), torch.stack(lss, 1), torch.stack(hs, 1)
+
+    def value(self, obs: torch.Tensor, act: torch.Tensor, own_action_only: bool = False) -> torch.Tensor:
+        """maac.py:47-66: [b + 1, n] — rows 0 .. b - 1 the values, row b the per-agent attention regulariser"""
+        q, reg = self.value_dicts[0](obs, act)
+        return torch.cat((q, reg.unsqueeze(0)), 0)
+
+    def get_actions(self, state, status, exploration, actions_avail, target=False, last_hid=None, means_grad_only=False, clip=False, noise=None):
+        """maac.py:68-92: DDPGNet.get_actions with the log-probability masked and summed over the action dimension: [b, n]"""
+        actions, restore, log_prob, out, hid = super().get_actions(state, status, exploration, actions_avail, target, last_hid, means_grad_only, clip, noise)
+        if log_prob is not None:
+            log_prob = ((1.0 - (actions_avail == 0).to(log_prob.dtype)) * log_prob).sum(dim=-1)
+        return actions, restore, log_prob, out, hid
+
+    def get_loss(self, batch: Batch, want=("policy", "value")):
+        """maac.py:94-121.  Two draws per call, in the reference's order: the actions at `state` from the behaviour policy, then the next
+        actions at `next_state` from the target policy; batch["noise"] / batch["next_noise"] [bs, n, 1] replace them.  A loss not in
+        `want` is None; of its forward passes only those are kept that change state the reference's call changes (the draws, and the
+        running statistics of `batchnorm` / the norm_in BatchNorms, which see every value() call while training)."""
+        n, a = self.n_, self.args
+        state, actions, next_state = batch["state"], batch["action"], batch["next_state"]
+        avail, last_hid, hid = batch["action_avail"], batch["last_hid"], batch["hid"]
+        bs = state.shape[0]
+        rewards = self.normalise_reward(batch["reward"].float())
+        done = batch["done"].float().view(-1, 1)
+        valid = batch.get("valid")
+        wmean = (lambda t: t.mean()) if valid is None else \
+            (lambda t: (t * valid.float().view(-1, 1)).sum() / (valid.float().sum().clamp(min=1.0) * t.shape[1]))
+        want_p, want_v = "policy" in want, "value" in want
+        stats = self.training and (a.norm_in or a.normalize_advantages)      # value() calls that move running statistics cannot be skipped
+        _, actions_pol, log_prob, action_out, _ = self.get_actions(state, "train", True, avail, False, last_hid, noise=batch.get("noise"))
+        if want_v or (stats and a.norm_in):
+            with torch.no_grad():
+                _, next_actions, _, _, _ = self.get_actions(next_state, "train", True, avail, True, hid, noise=batch.get("next_noise"))
+        elif batch.get("next_noise") is None:
+            torch.randn_like(actions_pol)                                    # the call's second draw, so that the generator goes the reference's way
+        policy_loss = value_loss = None
+        values_pol = None
+        if want_p or stats:
+            with torch.set_grad_enabled(want_p and torch.is_grad_enabled()):
+                values_pol = self.value(state, actions_pol)[:bs]             # (every agent's action carries gradient: maac.py:99 detaches nothing)
+        if want_v or want_p:
+            with torch.set_grad_enabled(want_v and torch.is_grad_enabled()):
+                compose = self.value(state, actions.detach())
+            values, attn_reg = compose[:bs], compose[bs]
+        if want_v or (stats and a.norm_in):
+            with torch.no_grad():
+                net = self.target_net if a.target else self
+                next_values = net.value(next_state, next_actions)[:bs].view(-1, n)
+        if values_pol is not None:
+            advantages = values_pol
+            if a.normalize_advantages:
+                advantages = self._adv_batchnorm.to(advantages.device)(advantages)
+        if want_p:
+            if a.soft:
+                pl = log_prob / a.reward_scale - advantages
+            else:
+                pl = -advantages.detach() * log_prob
+            policy_loss = wmean(pl + attn_reg)                               # the regulariser goes to the POLICY loss only (maac.py:118)
+        if want_v:
+            returns = rewards + a.gamma * (1 - done) * next_values - a.soft * log_prob / a.reward_scale       # log_prob NOT detached (maac.py:109)
+            value_loss = wmean((returns - values).pow(2))
+        return policy_loss, value_loss, (action_out if want_p else None)
+
+
 def net_class(alg: str):
     """the module class of an algorithm name (models/model_registry.py:14-25); KeyError for a name that is not built"""
-    for c in (DDPGNet, COMANet):
+    for c in (DDPGNet, COMANet, MAACNet):
         if alg in c.ALGS:
             return c
     raise KeyError(alg)
@@ -1431,6 +1749,8 @@ class PGTrainer:
         the K = n action term and the twin head are formed per epoch (DDPGNet._matd3_next_values)."""
         rb, net, a = self.replay_buffer, self.behaviour_net, self.args
         if not isinstance(rb, TransReplayBuffer) or os.environ.get("MAPDN_CACHE_NEXT_ACTIONS", "1") == "0" or len(rb) == 0:
+            return False
+        if net.alg == "maac":              # MAAC's target values the next actions DRAWN in every get_loss call (maac.py:98-102): nothing is cached
             return False
         st = rb.store
         if not all(k in st for k in ("next_state", "action_avail", "hid", "action")):

@@ -38,7 +38,7 @@ def run_episode(job):
     rng = np.random.default_rng(ep)
     pol = None
     if kind == "ckpt":
-        args = make_alg_args(n, o, 1, SCALE[case], 0.0)
+        args = make_alg_args(n, o, 1, SCALE[case], 0.0, alg=meta["alg"])
         Net = net_class(meta["alg"])
         pol = Net(args, meta["alg"], Net(args, meta["alg"]))      # behaviour net + its target, as PGTrainer builds it
         pol.load_state_dict(torch.load(path, map_location="cpu")["model_state_dict"])
