@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Seeded IDDPG / MADDPG / MATD3 / COMA / MAAC training on the batched GPU env with periodic checkpoints — the evidence run that the learner
+"""Seeded IDDPG / MADDPG / MATD3 / COMA / MAAC / SQDDPG training on the batched GPU env with periodic checkpoints — the evidence run that the learner
 learns.  Checkpoints (`model.pt` layout, train.py:119) are evaluated afterwards on the CPU ORACLE env
 (tools/eval_checkpoints_on_oracle.py), i.e. outside the product.
 
@@ -25,7 +25,7 @@ SCALE = {"case33": 0.8, "case141": 0.6, "case322": 0.8}
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="case33")
-    ap.add_argument("--alg", default="iddpg", choices=["maddpg", "iddpg", "matd3", "coma", "maac"])
+    ap.add_argument("--alg", default="iddpg", choices=["maddpg", "iddpg", "matd3", "coma", "maac", "sqddpg"])
     ap.add_argument("--envs", type=int, default=256)
     ap.add_argument("--episodes", type=int, default=300)
     ap.add_argument("--ckpt-every", type=int, default=25)

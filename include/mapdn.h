@@ -511,6 +511,37 @@ int mapdn_attention_backward(const float* dout, const float* dlogit_sq, const fl
 int64_t mapdn_attention_scratch_floats(int64_t B, int32_t n, int32_t H);
 int32_t mapdn_attention_max_agents(void);
 
+/* SQDDPG's Shapley coalition critic (models/sqddpg.py:37-106) behind its first layer, rows formed in the kernel (csrc/critic_shap.hip).
+ * For sample b, coalition draw s and agent i, with pos[b][s][i] the position of agent i in the draw's order and gc = argsort(pos):
+ *   x[b][s][i] = base[b] + id_cols[i] + P[b][s][pos_i],   P[b][s][p] = sum_{q <= p} act[b][gc[q]] act_cols[q],
+ *   v[b][s][i] = head(x[b][s][i])  (LayerNorm -> ReLU -> fc2 -> ReLU -> fc3, as mapdn_critic_head_forward),  phi[b][i] = mean_s v[b][s][i].
+ * base [b][64] (the observation columns of fc1 applied to all observations, plus its bias), id_cols / act_cols [n][64] (the agent-id and
+ * action columns of fc1, transposed), act [b][n] f32, pos [b][S][n] INT32 (a draw of torch.multinomial, narrowed by the caller).
+ * _forward: v [b][S][n] indexed by agent; phi [b][n] or NULL.
+ * _backward (recomputes the forward): dv [b][S][n] (a caller that holds dphi passes dphi / S expanded over s).
+ *   param_grads = 1: dbase [b][64]; grads [4416 + 2 n 64] = the trunk's gradients in the layout of mapdn_critic_head_backward, then
+ *     d id_cols [n][64], then d act_cols [n][64]; scratch: mapdn_critic_shapley_scratch_floats(b, S, n) floats (one partial per
+ *     workgroup, summed in a fixed order: deterministic, no atomics); dact [b][n] or NULL.
+ *   param_grads = 0: dact [b][n] only (dact[b][i] = sum_s dx[b][s][i] . act_cols[pos_i]: only the own slot carries a gradient);
+ *     dbase, grads, scratch may be NULL.
+ * _geometry: mode 0 forward, 1 backward with param_grads, 2 backward without; cus = 0: the current device's CU count.  Reports the launch
+ *   (threads, workgroups, LDS bytes) and, whatever the shape, the LDS budget per CU (163840) and the largest n that fits it.
+ * Refused with MAPDN_E_INVALID before any launch: a null pointer (other than the optional ones) or one that is not aligned (16 bytes for
+ * base, id_cols, act_cols, dbase and the trunk's vectors, 4 bytes otherwise); b < 1, S < 1, n < 1; n above the reported maximum;
+ * b S n >= 2^31; a pos in HOST memory with a row that is not a permutation of 0 .. n - 1 (pinned memory is checked and then read by the
+ * kernel; pageable host memory is refused).  For pos in device memory a permutation per row is a precondition: the kernels clamp its
+ * values into [0, n), so a broken one gives wrong numbers but no access outside the buffers. */
+int mapdn_critic_shapley_forward(const float* base, const float* id_cols, const float* act_cols, const float* act, const int32_t* pos,
+                                 int64_t b, int32_t S, int32_t n, const float* gamma, const float* beta, float eps, const float* w2,
+                                 const float* b2, const float* w3, const float* b3, float* v, float* phi, void* stream);
+int mapdn_critic_shapley_backward(const float* dv, const float* base, const float* id_cols, const float* act_cols, const float* act,
+                                  const int32_t* pos, int64_t b, int32_t S, int32_t n, const float* gamma, const float* beta, float eps,
+                                  const float* w2, const float* b2, const float* w3, const float* b3, float* dbase, float* grads,
+                                  float* scratch, float* dact, int32_t param_grads, void* stream);
+int64_t mapdn_critic_shapley_scratch_floats(int64_t b, int32_t S, int32_t n);
+int mapdn_critic_shapley_geometry(int64_t b, int32_t S, int32_t n, int32_t mode, int32_t cus, int32_t* threads, int32_t* blocks,
+                                  int32_t* lds_bytes, int32_t* lds_budget, int32_t* max_n);
+
 /* The glue of one batched rollout step (models/model.py:197-262) as three launches instead of ~45 one-line PyTorch kernels
  * (csrc/rollout.hip).  Device pointers, contiguous.
  * mapdn_explore_actions: action = tanh(mean + std * eps) (utilities/util.py:57-66; no tanh when tanh_bound == 0), action_pol =

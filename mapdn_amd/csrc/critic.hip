@@ -560,3 +560,4 @@ extern "C" int mapdn_critic_head_mse(const float* ret, const float* wrow, const 
 #include "critic_twin.hip"      // MATD3: both heads of the twin critic on one tile (k_twin_*)
 #include "critic_cf.hip"        // COMA: the counterfactual baseline, S sampled heads on one tile (k_cf_*)
 #include "critic_attn.hip"      // MAAC: the attention core over the n rows of a sample (k_attn_*)
+#include "critic_shap.hip"      // SQDDPG: the Shapley coalition critic, rows formed from a prefix sum over positions (k_shap_*)
