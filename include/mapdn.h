@@ -547,7 +547,8 @@ int mapdn_critic_shapley_geometry(int64_t b, int32_t S, int32_t n, int32_t mode,
  * mapdn_explore_actions: action = tanh(mean + std * eps) (utilities/util.py:57-66; no tanh when tanh_bound == 0), action_pol =
  *   (avail != 0) * action (maddpg.py:92-93; avail / action_pol may be NULL), actual = translate_action(action) = 0.5 (clamp(action, -1,
  *   1) + 1) (high - low) + low with low / high = bias -/+ scale (utilities/util.py:123-132); f32, the PyTorch chain's operations in
- *   its order, bit-identical.
+ *   its order, bit-identical — NaN included: the clamp hands a NaN on as torch.clamp does, so a NaN mean gives a NaN action, a NaN
+ *   action_pol (also where avail == 0: 0 * NaN) and a NaN actual: the env is handed the NaN, as the reference's is.
  * mapdn_rollout_stats: sums[0..10] += sum over live envs of info[e][k], sums[11] += of reward[e], sums[12] += live envs; then
  *   alive_out[e] = alive[e] & !done[e] (models/model.py:243-248, 225; alive_out may be alive); info [n_envs][11], reward [n_envs] f64; alive / done one byte per env.
  * mapdn_copy_segments: dst[i][0 .. nbytes[i]) = src[i][...] for up to 48 segments in one launch (the fields of a transition into

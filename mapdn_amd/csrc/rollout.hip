@@ -32,7 +32,8 @@ k_explore(const float* __restrict__ mean, const float* __restrict__ eps, const f
     const float yp = avail ? (avail[i] == 0.0f ? 0.0f : 1.0f) * y : y;
     if (action_pol) action_pol[i] = yp;
     // translate_action (util.py:123-132) of the stored action: clamp to [-1, 1], 0.5 (cp + 1) (high - low) + low
-    const float cp = fminf(fmaxf(y, -1.0f), 1.0f);
+    // (two compares, not fminf(fmaxf()): those drop a NaN and return the bound, torch.clamp hands it on — a NaN mean must reach the env)
+    const float cp = y < -1.0f ? -1.0f : (y > 1.0f ? 1.0f : y);
     const float t1 = cp + 1.0f;
     const float t2 = 0.5f * t1;
     const float t3 = t2 * half_range2;
