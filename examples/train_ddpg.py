@@ -33,7 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="case322")
-    ap.add_argument("--alg", default="maddpg", choices=["maddpg", "iddpg", "matd3", "coma", "maac", "sqddpg"])
+    ap.add_argument("--alg", default="maddpg", choices=["maddpg", "iddpg", "matd3", "coma", "maac", "sqddpg", "mappo", "ippo"])
     ap.add_argument("--envs", type=int, default=8192, help="envs per GPU")
     ap.add_argument("--episodes", type=int, default=3)
     ap.add_argument("--max-steps", type=int, default=240)

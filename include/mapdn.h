@@ -559,6 +559,35 @@ int mapdn_rollout_stats(const double* info, const double* reward, const uint8_t*
                         int32_t n_envs, void* stream);
 int mapdn_copy_segments(const void* const* src, void* const* dst, const int64_t* nbytes, int32_t n_segments, void* stream);
 
+/* The PPO half of MAPPO / IPPO's update (learning_algorithms/ppo.py:39-70; csrc/ppo.hip).  Device pointers, contiguous f32: per-agent
+ * tensors [rows][n], done / last_step / valid [rows]; rows >= 1, n >= 1, rows * n <= 2^40, no NULL pointer unless said so; anything
+ * else is MAPDN_E_INVALID and nothing is launched.
+ * mapdn_ppo_gae: adv[i] = delta[i] + gamma lambda mask[i] adv[i + stride] (0 beyond the last row), delta[i] = reward[i] + gamma
+ *   next_value[i] mask[i] - value[i], mask[i] = 1 - done[i] where last_step[i] != 0 and 1 elsewhere (ppo.py:46-54, which is stride 1;
+ *   a timeout row — last_step without done — does not cut the chain, nor does a done without last_step).  stride >= 1: row i's
+ *   successor is row i + stride, so rows in (step, env) order with stride = the env count are one chain per env; chains may differ
+ *   in length by one (rows % stride != 0); stride > rows gives chains of one row.  gamma and gamma * lambda are rounded to f32 as
+ *   PyTorch rounds a Python scalar that meets an f32 tensor; the f32 operations are the reference's, in its order, uncontracted.
+ * mapdn_ppo_loss_blocks: the number of floats `partial` must hold for a loss over rows * n = elems elements on the current device
+ *   (one per workgroup of the launch); 0 for elems < 1.
+ * mapdn_ppo_policy_loss: loss[0] = -scale[0] sum_e w[e] min(rho A, clamp(rho, 1 - eps_clip, 1 + eps_clip) A), w[e] = valid[row(e)]
+ *   (valid NULL: 1), rho = exp(m lp - m old_log_prob), lp = the log-density of action under N(mean, exp(log_std)), m = (avail != 0)
+ *   (avail NULL: 1), A = adv (ppo.py:30-33, 39, 62-64); dmean[e] = d loss[0] / d mean[e] as autograd gives it: torch.min halves the
+ *   gradient where its operands are equal, clamp passes it on its bounds.  scale [1]: 1 / (max(sum valid, 1) n), the mean's divisor.
+ * mapdn_ppo_value_loss: loss[0] = coef scale[0] sum_e w[e] max((v - R)^2, (v_old + clamp(v - v_old, -eps_clip, eps_clip) - R)^2),
+ *   R = reward + gamma (1 - done) v_next (ppo.py:56, 67-70); dv[e] = d loss[0] / d v[e], ties as above.
+ * Either loss: one streaming launch that writes the gradient and one partial sum per workgroup (wave-64 shuffles, then LDS), and a
+ * one-workgroup pass that adds the partials in a fixed order — no floating-point atomics, the same input gives the same bits. */
+int mapdn_ppo_gae(const float* reward, const float* value, const float* next_value, const float* done, const float* last_step, float* adv,
+                  int64_t rows, int32_t n, int64_t stride, double gamma, double lambda, void* stream);
+int mapdn_ppo_loss_blocks(int64_t elems);
+int mapdn_ppo_policy_loss(const float* action, const float* mean, const float* log_std, const float* avail, const float* old_log_prob,
+                          const float* adv, const float* valid, const float* scale, double eps_clip, float* loss, float* dmean,
+                          float* partial, int64_t rows, int32_t n, void* stream);
+int mapdn_ppo_value_loss(const float* v, const float* v_old, const float* reward, const float* v_next, const float* done,
+                         const float* valid, const float* scale, double gamma, double eps_clip, double coef, float* loss, float* dv,
+                         float* partial, int64_t rows, int32_t n, void* stream);
+
 /* Calibration aid for the HBM counters (tools/calibrate_traffic.py): copies rows x Bp x 16 bytes from src to dst (device pointers) with
  * the solver's own global access pattern — raw-buffer 16-byte loads / stores of env-minor pair rows, 256 contiguous bytes per
  * 16-lane worker (pattern 0) — or with whole waves on one row (pattern 1), so that rocprofv3's FETCH_SIZE / WRITE_SIZE can be read

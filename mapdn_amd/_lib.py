@@ -41,6 +41,7 @@ EXPORTS = (
     "mapdn_critic_head_counterfactual",
     "mapdn_attention_forward", "mapdn_attention_backward", "mapdn_attention_scratch_floats", "mapdn_attention_max_agents",
     "mapdn_critic_shapley_forward", "mapdn_critic_shapley_backward", "mapdn_critic_shapley_scratch_floats", "mapdn_critic_shapley_geometry",
+    "mapdn_ppo_gae", "mapdn_ppo_loss_blocks", "mapdn_ppo_policy_loss", "mapdn_ppo_value_loss",
 )
 
 _pd = C.POINTER(C.c_double)
@@ -247,6 +248,10 @@ def load():
     lib.mapdn_critic_shapley_scratch_floats.argtypes = [C.c_int64, C.c_int32, C.c_int32]
     lib.mapdn_critic_shapley_scratch_floats.restype = C.c_int64
     lib.mapdn_critic_shapley_geometry.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _pi, _pi, _pi, _pi, _pi]
+    lib.mapdn_ppo_gae.argtypes = [vp] * 6 + [C.c_int64, C.c_int32, C.c_int64, C.c_double, C.c_double, vp]
+    lib.mapdn_ppo_loss_blocks.argtypes = [C.c_int64]
+    lib.mapdn_ppo_policy_loss.argtypes = [vp] * 8 + [C.c_double, vp, vp, vp, C.c_int64, C.c_int32, vp]
+    lib.mapdn_ppo_value_loss.argtypes = [vp] * 7 + [C.c_double] * 3 + [vp, vp, vp, C.c_int64, C.c_int32, vp]
     lib.mapdn_critic_head_backward_dot.argtypes = [vp, vp, vp, C.c_int32, vp, vp, C.c_float] + [vp] * 6 + [C.c_int64, vp]
     lib.mapdn_dense_solve.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp]
     lib.mapdn_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int32), vp]

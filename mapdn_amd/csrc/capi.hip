@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "ppo.hip"            // MAPPO / IPPO: the strided GAE and the clipped losses (k_ppo_*), compiled inside this unit; entry points below
 #include "nr_inst_list.hpp"
 #include "colstats.hpp"
 #include "plan.hpp"
@@ -1207,5 +1208,38 @@ int mapdn_droop_actions(mapdn_handle* h, const mapdn_droop_config* cfg, double* 
   HIPCHK(h, hipSetDevice(h->device));
   return droop_run(h, c, actions, vm_pu, iterations, status, (hipStream_t)stream);
 } MAPDN_CATCH(h)
+
+// ---- the PPO half of MAPPO / IPPO's update (csrc/ppo.hip): argument checks here, nothing is launched on a refusal
+static bool ppo_shape_ok(int64_t rows, int32_t n) { return rows >= 1 && n >= 1 && rows <= ((int64_t)1 << 40) / n; }
+
+int mapdn_ppo_gae(const float* reward, const float* value, const float* next_value, const float* done, const float* last_step, float* adv,
+                  int64_t rows, int32_t n, int64_t stride, double gamma, double lambda, void* stream) try {
+  if (!reward || !value || !next_value || !done || !last_step || !adv || !ppo_shape_ok(rows, n) || stride < 1) return MAPDN_E_INVALID;
+  // ppo.py:52-53: gamma and gamma * lambda_ are Python doubles; PyTorch rounds each to f32 where it meets the f32 tensor
+  return launch_ppo_gae(reward, value, next_value, done, last_step, adv, rows, n, stride, (float)gamma, (float)(gamma * lambda), (hipStream_t)stream);
+} MAPDN_CATCH(nullptr)
+
+int mapdn_ppo_loss_blocks(int64_t elems) try {
+  return elems < 1 ? 0 : ppo_loss_blocks(elems);
+} MAPDN_CATCH(nullptr)
+
+int mapdn_ppo_policy_loss(const float* action, const float* mean, const float* log_std, const float* avail, const float* old_log_prob,
+                          const float* adv, const float* valid, const float* scale, double eps_clip, float* loss, float* dmean,
+                          float* partial, int64_t rows, int32_t n, void* stream) try {
+  if (!action || !mean || !log_std || !old_log_prob || !adv || !scale || !loss || !dmean || !partial || !ppo_shape_ok(rows, n) || !(eps_clip >= 0.0))
+    return MAPDN_E_INVALID;
+  // ppo.py:63: 1 - eps_clip and 1 + eps_clip are formed in double, then rounded to f32 by clamp
+  return launch_ppo_policy_loss(action, mean, log_std, avail, old_log_prob, adv, valid, scale, (float)(1.0 - eps_clip), (float)(1.0 + eps_clip), loss,
+                                dmean, partial, rows, n, (hipStream_t)stream);
+} MAPDN_CATCH(nullptr)
+
+int mapdn_ppo_value_loss(const float* v, const float* v_old, const float* reward, const float* v_next, const float* done,
+                         const float* valid, const float* scale, double gamma, double eps_clip, double coef, float* loss, float* dv,
+                         float* partial, int64_t rows, int32_t n, void* stream) try {
+  if (!v || !v_old || !reward || !v_next || !done || !scale || !loss || !dv || !partial || !ppo_shape_ok(rows, n) || !(eps_clip >= 0.0))
+    return MAPDN_E_INVALID;
+  return launch_ppo_value_loss(v, v_old, reward, v_next, done, valid, scale, (float)gamma, (float)eps_clip, (float)coef, loss, dv, partial, rows, n,
+                               (hipStream_t)stream);
+} MAPDN_CATCH(nullptr)
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-"""End-to-end MADDPG / IDDPG / MATD3 / COMA / MAAC / SQDDPG loop on the batched GPU env (BASELINE.json configs[4]; SURVEY 8(f) rows 1-3 wired together): rollout of B envs
+"""End-to-end MADDPG / IDDPG / MATD3 / COMA / MAAC / SQDDPG / MAPPO / IPPO loop on the batched GPU env (BASELINE.json configs[4]; SURVEY 8(f) rows 1-3 wired together): rollout of B envs
 per GPU through the HIP hot path, GPU-resident replay, DDPG updates.  One function, used by examples/train_ddpg.py (the CLI) and by
 bench.py's `e2e` block (so that a driver run records the loop the env feeds, not only the env).
 

@@ -1,4 +1,4 @@
-"""MADDPG / IDDPG / MATD3 / COMA / MAAC / SQDDPG learners for the batched env (BASELINE.json configs[4]).
+"""MADDPG / IDDPG / MATD3 / COMA / MAAC / SQDDPG / MAPPO / IPPO learners for the batched env (BASELINE.json configs[4]).
 
 What is learned, and every quirk of how, follows the reference (file:line cited at each piece):
 `models/maddpg.py`, `models/iddpg.py`, `models/matd3.py`, `models/coma.py`, `learning_algorithms/ddpg.py`, `models/model.py`,
@@ -23,7 +23,11 @@ Only the configuration the DDPG family trains with exists: continuous actions, d
 attention critic whose attention over the other agents is one HIP launch each way, csrc/critic_attn.hip), reached through
 make_alg_args(..., alg="maac") — and SQDDPG's (models/sqddpg.py: the deterministic agents with a critic valued on sampled coalition
 orders, whose b x sample_size x n rows are formed inside the kernels of csrc/critic_shap.hip from a prefix sum over positions), reached
-through make_alg_args(..., alg="sqddpg").  Anything else raises.
+through make_alg_args(..., alg="sqddpg") — and MAPPO's / IPPO's (models/mappo.py, models/ippo.py, learning_algorithms/ppo.py: the deterministic
+agents with a state-value critic, generalised advantage estimation and the clipped surrogate / clipped value losses; the GAE recurrence over
+strided chains and both losses with their gradients are the launches of csrc/ppo.hip), reached through make_alg_args(..., alg="mappo" | "ippo").
+Two of the reference's quirks there are kept and stated at PPONet: the GAE chain is cut only by a row that is BOTH done and last_step, and
+the ratio's old log-probability is the stored action (models/model.py:309) unless ppo_old_log_prob="stored".  Anything else raises.
 """
 from __future__ import annotations
 
@@ -52,9 +56,16 @@ ALG_DEFAULTS = dict(
     policy_update_epochs=1, value_update_epochs=10, mixer_update_epochs=None, reward_normalisation=True,
     eval_freq=20, num_eval_episodes=10, sample_size=10,
     attend_heads=1, norm_in=False, soft=True, reward_scale=100,      # args/alg_args/maac.yaml (read by MAAC only)
+    lambda_=0.95, eps_clip=0.6, value_loss_coef=2.0,                 # args/alg_args/mappo.yaml == ippo.yaml (read by MAPPO / IPPO only)
+    ppo_old_log_prob="reference",    # not a reference key: "reference" = the ratio's old log-probability is the stored ACTION, as
+                                     # Model.unpack_data fills it (models/model.py:309); "stored" = the log-probability recorded at rollout time
 )
 ALG_YAML = {"maac": dict(gaussian_policy=True, action_enforcebound=True),      # what an algorithm's yaml sets beyond the defaults above
-            "sqddpg": dict(sample_size=10, action_enforcebound=True)}          # args/alg_args/sqddpg.yaml
+            "sqddpg": dict(sample_size=10, action_enforcebound=True),          # args/alg_args/sqddpg.yaml
+            "mappo": dict(policy_update_epochs=10, value_update_epochs=10, lambda_=0.95, eps_clip=0.6, value_loss_coef=2.0, reward_normalisation=True,
+                          normalize_advantages=True, gaussian_policy=False, action_enforcebound=True, behaviour_update_freq=240,
+                          target_update_freq=480)}                             # args/alg_args/mappo.yaml
+ALG_YAML["ippo"] = dict(ALG_YAML["mappo"])                                     # args/alg_args/ippo.yaml: the same values
 
 Batch = Dict[str, torch.Tensor]
 
@@ -62,7 +73,8 @@ Batch = Dict[str, torch.Tensor]
 def make_alg_args(agent_num: int, obs_size: int, action_dim: int = 1, action_scale: float = 0.8,
                   action_bias: float = 0.0, alg: Optional[str] = None, **overrides) -> SimpleNamespace:
     """The `args` namedtuple train.py:64-67 assembles, as a namespace.  alg: the algorithm whose yaml is merged over the defaults before the
-    overrides (train.py:60-62) — needed for "maac" alone, whose yaml switches the Gaussian policy head on."""
+    overrides (train.py:60-62) — needed for "maac", whose yaml switches the Gaussian policy head on, and for "mappo" / "ippo", whose
+    yaml sets the update schedule, the clip range, lambda_ and normalize_advantages."""
     d = dict(ALG_DEFAULTS)
     unknown = set(overrides) - set(d)
     if unknown:
@@ -77,6 +89,9 @@ def make_alg_args(agent_num: int, obs_size: int, action_dim: int = 1, action_sca
         return a
     if alg == "sqddpg":
         _sqddpg_args_ok(a)
+        return a
+    if alg in ("mappo", "ippo"):
+        _ppo_args_ok(a)
         return a
     if not a.continuous or a.gaussian_policy or a.mixer or a.episodic or a.agent_type != "rnn":
         raise NotImplementedError("the DDPG-family learners here cover continuous, non-Gaussian, recurrent, "
@@ -120,6 +135,25 @@ def _sqddpg_args_ok(a) -> None:
         raise NotImplementedError(f"SQDDPG: agent_type={a.agent_type!r} is not built (only 'rnn')")
     if int(a.sample_size) < 1:
         raise ValueError(f"SQDDPG: sample_size={a.sample_size} must be at least 1")
+
+
+def _ppo_args_ok(a) -> None:
+    """what PPONet builds: continuous actions, the deterministic recurrent agent (fixed std), one action per agent, transition updates,
+    no mixer"""
+    if not a.continuous:
+        raise NotImplementedError("MAPPO/IPPO: continuous=False (discrete actions) is not built")
+    if a.gaussian_policy:
+        raise NotImplementedError("MAPPO/IPPO: gaussian_policy=True is not built (args/alg_args/mappo.yaml, ippo.yaml set it False)")
+    if a.action_dim != 1:
+        raise NotImplementedError(f"MAPPO/IPPO: action_dim={a.action_dim} is not built (one action per agent)")
+    if a.mixer:
+        raise NotImplementedError("MAPPO/IPPO: mixer=True is not built")
+    if a.episodic:
+        raise NotImplementedError("MAPPO/IPPO: episodic=True is not built (transition updates only)")
+    if a.agent_type != "rnn":
+        raise NotImplementedError(f"MAPPO/IPPO: agent_type={a.agent_type!r} is not built (only 'rnn')")
+    if a.ppo_old_log_prob not in ("reference", "stored"):
+        raise ValueError(f"MAPPO/IPPO: ppo_old_log_prob={a.ppo_old_log_prob!r} must be 'reference' or 'stored'")
 
 
 def _activation(name: str):
@@ -1118,7 +1152,12 @@ class DDPGNet(nn.Module):
         equals the one-rank update on the concatenated batch and the running statistics stay identical on every replica."""
         if not self.args.reward_normalisation:
             return reward
-        bn, red = self.batchnorm, self.__dict__.get("_dp_all_reduce")
+        return self._union_batchnorm(self.batchnorm, reward)
+
+    def _union_batchnorm(self, bn: nn.BatchNorm1d, reward: torch.Tensor) -> torch.Tensor:
+        """bn(x) for x [batch, n]; in training mode under data-parallel training with the statistics of the union of the ranks' batches
+        (see normalise_reward).  MAPPO / IPPO's advantage BatchNorm goes through it as well."""
+        red = self.__dict__.get("_dp_all_reduce")
         if red is None or not bn.training:
             return bn(reward)
         x = reward.double()
@@ -1824,9 +1863,286 @@ class SQDDPGNet(DDPGNet):
         return policy_loss, value_loss, (action_out if want_p else None)
 
 
+# ---- MAPPO / IPPO (models/mappo.py, models/ippo.py, learning_algorithms/ppo.py) ---------------------------------------------------------
+_LOG_SQRT_2PI = math.log(math.sqrt(2 * math.pi))
+PPO_MAX_ELEMS = 1 << 40                    # csrc/capi.hip ppo_shape_ok: rows * n at most
+
+
+def ppo_fused_ok(*tensors) -> bool:
+    """the PPO kernels (csrc/ppo.hip: the strided GAE, the two clipped losses) cover fp32 tensors on the GPU with at most 2^40 elements;
+    MAPDN_FUSED_PPO=0 switches them off (the vectorised PyTorch forms below remain, which are also the CPU route).  tensors: every tensor
+    the launch would read (None for an optional one that is absent); the first is a per-agent [rows, n] one."""
+    return (os.environ.get("MAPDN_FUSED_PPO", "1") != "0" and all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in tensors)
+            and tensors[0].dim() == 2 and 1 <= tensors[0].numel() <= PPO_MAX_ELEMS)
+
+
+def ppo_gae_torch(reward, value, next_value, done, last_step, stride: int, gamma: float, lambda_: float) -> torch.Tensor:
+    """ppo.py:46-54 over chains of `stride`: row i's successor is row i + stride.  reward / value / next_value [rows, n], done / last_step
+    [rows] -> advantages [rows, n].  A loop over the ceil(rows / stride) chain STEPS on [stride, n] slices (newest first), never over
+    rows; stride 1 is the reference's loop, operation for operation."""
+    rows = reward.shape[0]
+    S = int(stride)
+    mask = torch.where(last_step != 0, 1.0 - done, torch.ones_like(done)).unsqueeze(-1)          # ppo.py:48-51
+    delta = reward + gamma * next_value * mask - value                                            # ppo.py:52
+    adv = torch.empty_like(delta)
+    last = torch.zeros_like(delta[:min(S, rows)])
+    for t in reversed(range(-(-rows // S))):
+        lo, hi = t * S, min((t + 1) * S, rows)
+        new = delta[lo:hi] + gamma * lambda_ * last[:hi - lo] * mask[lo:hi]                       # ppo.py:53
+        adv[lo:hi] = new
+        last = new if hi - lo == last.shape[0] else torch.cat((new, last[hi - lo:]))             # (the ragged end: the other chains start one step later)
+    return adv
+
+
+def ppo_gae(reward, value, next_value, done, last_step, stride: int, gamma: float, lambda_: float) -> torch.Tensor:
+    """the advantages of ppo_gae_torch, without autograd: ONE launch (mapdn_ppo_gae) where ppo_fused_ok, the chain-step loop otherwise"""
+    if stride < 1:
+        raise ValueError(f"GAE chain stride {stride} must be at least 1")
+    r, v, nv, d, ls = (t.detach() for t in (reward, value, next_value, done, last_step))
+    if not ppo_fused_ok(r, v, nv, d, ls):
+        with torch.no_grad():
+            return ppo_gae_torch(r, v, nv, d, ls, stride, gamma, lambda_)
+    from . import _lib
+    r, v, nv, d, ls = (t.contiguous() for t in (r, v, nv, d, ls))
+    rows, n = r.shape
+    adv = torch.empty_like(r)
+    with torch.cuda.device(r.device):
+        _lib.check(_lib.load().mapdn_ppo_gae(r.data_ptr(), v.data_ptr(), nv.data_ptr(), d.data_ptr(), ls.data_ptr(), adv.data_ptr(), rows, n, int(stride),
+                                             float(gamma), float(lambda_), torch.cuda.current_stream(r.device).cuda_stream))
+    ppo_gae.launches += 1
+    return adv
+
+
+ppo_gae.launches = 0            # how often the kernel was reached (tests count the routes)
+
+
+def _ppo_weights(valid: Optional[torch.Tensor], like: torch.Tensor):
+    """(valid as f32 [rows] or None, scale [1] = 1 / (the divisor of DDPGNet.get_loss's wmean)) for a per-agent tensor [rows, n]"""
+    rows, n = like.shape
+    if valid is None:
+        return None, like.new_full((1,), 1.0 / (rows * n))
+    vf = valid.float().view(-1).contiguous()
+    return vf, (1.0 / (vf.sum().clamp(min=1.0) * n)).reshape(1)
+
+
+class _PPOPolicyLoss(torch.autograd.Function):
+    """-wmean(min(rho A, clamp(rho, 1 -/+ eps) A)) of ppo.py:39, 62-64 and its gradient with respect to the policy means as ONE entry
+    call (mapdn_ppo_policy_loss: the streaming launch + the fixed-order pass over its per-workgroup partial sums).  backward scales the
+    stored gradient by the incoming one (1 for `loss.backward()`).  The log-std of the non-Gaussian agent is a constant: no gradient."""
+    launches = 0
+
+    @staticmethod
+    def forward(ctx, means, actions, log_stds, avail, old_log_prob, adv, valid, scale, eps_clip):
+        from . import _lib
+        lib = _lib.load()
+        rows, n = adv.shape
+        mu, ac, ls, ol, ad = (t.detach().reshape(rows, n).contiguous() for t in (means, actions, log_stds, old_log_prob, adv))
+        av = avail.detach().reshape(rows, n).contiguous() if avail is not None else None
+        dev = mu.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        dmean = torch.empty_like(mu)
+        with torch.cuda.device(dev):
+            partial = torch.empty(lib.mapdn_ppo_loss_blocks(rows * n), dtype=torch.float32, device=dev)
+            _lib.check(lib.mapdn_ppo_policy_loss(ac.data_ptr(), mu.data_ptr(), ls.data_ptr(), av.data_ptr() if av is not None else None, ol.data_ptr(),
+                                                 ad.data_ptr(), valid.data_ptr() if valid is not None else None, scale.data_ptr(), float(eps_clip),
+                                                 loss.data_ptr(), dmean.data_ptr(), partial.data_ptr(), rows, n, torch.cuda.current_stream(dev).cuda_stream))
+        _PPOPolicyLoss.launches += 1
+        ctx.save_for_backward(dmean)
+        ctx.shape = means.shape
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (dmean,) = ctx.saved_tensors
+        return ((dmean * g).view(ctx.shape),) + (None,) * 8
+
+
+class _PPOValueLoss(torch.autograd.Function):
+    """coef wmean(max((V - R)^2, (V_clip - R)^2)) of ppo.py:56, 67-70 and its gradient with respect to V as ONE entry call
+    (mapdn_ppo_value_loss), R = r + gamma (1 - done) V(next) formed inside; backward scales the stored gradient by the incoming one"""
+    launches = 0
+
+    @staticmethod
+    def forward(ctx, values, old_values, reward, next_values, done, valid, scale, gamma, eps_clip, coef):
+        from . import _lib
+        lib = _lib.load()
+        rows, n = old_values.shape
+        v, vo, r, vn = (t.detach().reshape(rows, n).contiguous() for t in (values, old_values, reward, next_values))
+        d = done.detach().reshape(rows).contiguous()
+        dev = v.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        dv = torch.empty_like(v)
+        with torch.cuda.device(dev):
+            partial = torch.empty(lib.mapdn_ppo_loss_blocks(rows * n), dtype=torch.float32, device=dev)
+            _lib.check(lib.mapdn_ppo_value_loss(v.data_ptr(), vo.data_ptr(), r.data_ptr(), vn.data_ptr(), d.data_ptr(),
+                                                valid.data_ptr() if valid is not None else None, scale.data_ptr(), float(gamma), float(eps_clip),
+                                                float(coef), loss.data_ptr(), dv.data_ptr(), partial.data_ptr(), rows, n,
+                                                torch.cuda.current_stream(dev).cuda_stream))
+        _PPOValueLoss.launches += 1
+        ctx.save_for_backward(dv)
+        ctx.shape = values.shape
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (dv,) = ctx.saved_tensors
+        return ((dv * g).view(ctx.shape),) + (None,) * 9
+
+
+def _wmean(valid):
+    return (lambda t: t.mean()) if valid is None else \
+        (lambda t: (t * valid.float().view(-1, 1)).sum() / (valid.float().sum().clamp(min=1.0) * t.shape[1]))
+
+
+def ppo_policy_loss_torch(means, actions, log_stds, avail, old_log_prob, adv, valid, eps_clip: float) -> torch.Tensor:
+    """ppo.py:30-33, 39, 62-64 as written (Normal(means, stds).log_prob of utilities/util.py:44-46 spelled out); [bs, n, 1] tensors, adv
+    [bs, n]; the means of the loss weighted by `valid` as in DDPGNet.get_loss"""
+    std = log_stds.exp()
+    log_prob = -((actions - means) ** 2) / (2 * std ** 2) - std.log() - _LOG_SQRT_2PI
+    mask = 1.0 if avail is None else 1.0 - (avail == 0).to(log_prob.dtype)
+    log_prob, old = (mask * log_prob).sum(dim=-1), (mask * old_log_prob).sum(dim=-1)
+    ratios = torch.exp(log_prob - old.detach())
+    adv = adv.detach()
+    return -_wmean(valid)(torch.min(ratios * adv, torch.clamp(ratios, 1 - eps_clip, 1 + eps_clip) * adv))
+
+
+def ppo_value_loss_torch(values, old_values, reward, next_values, done, valid, gamma: float, eps_clip: float, coef: float) -> torch.Tensor:
+    """ppo.py:56, 67-70 as written; [bs, n] tensors, done [bs]"""
+    returns = reward + gamma * (1 - done.view(-1, 1)) * next_values.detach()
+    clipped = old_values + torch.clamp(values - old_values, -eps_clip, eps_clip)
+    return coef * _wmean(valid)(torch.max((values - returns).pow(2), (clipped - returns).pow(2)))
+
+
+def ppo_policy_loss(means, actions, log_stds, avail, old_log_prob, adv, valid, eps_clip: float) -> torch.Tensor:
+    if not (ppo_fused_ok(adv, means, actions, log_stds, avail, old_log_prob) and means.shape[-1] == 1 and not log_stds.requires_grad):
+        return ppo_policy_loss_torch(means, actions, log_stds, avail, old_log_prob, adv, valid, eps_clip)
+    vf, scale = _ppo_weights(valid, adv)
+    return _PPOPolicyLoss.apply(means, actions, log_stds, avail, old_log_prob, adv, vf, scale, eps_clip)
+
+
+def ppo_value_loss(values, old_values, reward, next_values, done, valid, gamma: float, eps_clip: float, coef: float) -> torch.Tensor:
+    if not ppo_fused_ok(old_values, values, reward, next_values, done):
+        return ppo_value_loss_torch(values, old_values, reward, next_values, done, valid, gamma, eps_clip, coef)
+    vf, scale = _ppo_weights(valid, old_values)
+    return _PPOValueLoss.apply(values, old_values, reward, next_values, done, vf, scale, gamma, eps_clip, coef)
+
+
+class PPONet(DDPGNet):
+    """`MAPPO(Model)` (models/mappo.py:11) and `IPPO(Model)` (models/ippo.py:10) with the loss of `PPO` (learning_algorithms/ppo.py): the
+    deterministic recurrent agents (their fixed std makes them a Gaussian policy for the ratio), target handling and reward BatchNorm
+    are DDPGNet's; the critic is a state value V(s) — MAPPO's on [all obs | id], IPPO's on [own obs | id].  On-policy: PGTrainer empties
+    the replay ring after every update round (models/model.py:53-56), stores log_prob / value / next_value with every transition, and
+    sets `gae_stride` to its env count.
+
+    Two quirks of the reference are kept.  (1) The GAE mask (ppo.py:48-51) is 1 - done on a last_step row and 1 on every other row, so
+    a timeout (last_step without done) does not cut the chain, nor does a done without last_step.  (2) Model.unpack_data
+    (models/model.py:309) fills old_log_prob_a from batch.action, so the reference's ratio is exp(log_prob_new - action):
+    args.ppo_old_log_prob="reference" (the default; not a reference key) does the same, "stored" takes the log-probability recorded at
+    rollout time (batch["log_prob"]).  The target net is built, updated and saved, and never read by the loss (ppo.py:16).
+
+    Chain stride.  get_loss(batch, want, stride) treats row i + stride as row i's successor (default: the attribute `gae_stride`, 1
+    unless the trainer set it; 1 is the reference's row-by-row walk, literally).  The replay ring holds rows in (step, env) order and
+    every insertion adds one row per env, so with stride = the env count each residue class of a sampled window is one env's time
+    series wherever the window starts.  A window shorter than the stride gives chains of one row (advantage = delta): on-policy
+    training wants batch_size to be a multiple of the env count."""
+    ALGS = ("mappo", "ippo")
+
+    def __init__(self, args, alg: str = "mappo", target_net: Optional["PPONet"] = None):
+        nn.Module.__init__(self)
+        if alg not in self.ALGS:
+            raise KeyError(alg)
+        _ppo_args_ok(args)
+        self.args, self.alg = args, alg
+        self.n_, self.obs_dim, self.act_dim, self.hid_dim = args.agent_num, args.obs_size, args.action_dim, args.hid_size
+        self._fused_fits = None
+        n, o = self.n_, self.obs_dim
+        ids = n if args.agent_id else 0
+        self.batchnorm = nn.BatchNorm1d(n)                         # rewards only (model.py:317-318)
+        # advantages: PPO.batchnorm (ppo.py:11, 58-59) lives on a plain object — not part of the state_dict, never switched to eval
+        self.__dict__["_adv_batchnorm"] = nn.BatchNorm1d(n)
+        self.__dict__["gae_stride"] = 1
+        copies = 1 if args.shared_params else n
+        critic_in = (n * o if alg == "mappo" else o) + ids         # mappo.py:21-26, ippo.py:20-25: a V(s), no action columns
+        self.value_dicts = nn.ModuleList([MLPCritic(critic_in, 1, args) for _ in range(copies)])
+        self.policy_dicts = nn.ModuleList([RNNAgent(o + ids, args) for _ in range(copies)])
+        self.apply(self._init_weights)
+        if target_net is not None:
+            self.target_net = target_net
+            self.reload_params_to_target()
+
+    def value(self, obs: torch.Tensor, act: Optional[torch.Tensor] = None, own_action_only: bool = False) -> torch.Tensor:
+        """obs [b, n, o] -> V [b, n, 1]; `act` is ignored (mappo.py:36-65, ippo.py:35-59).  MAPPO's [b, n, n o] input is never built: the
+        first layer is W_obs·obs_all + b1 once per sample plus the agent's id column, and with the default critic on the GPU everything
+        behind it is the one-launch head on rows formed as base[b] + per_n[i]."""
+        b, n, o = obs.shape[0], self.n_, self.obs_dim
+        ids = n if self.args.agent_id else 0
+        if self.alg == "ippo":
+            if self.args.shared_params:
+                cr = self.value_dicts[0]
+                w = cr.fc1.weight
+                x = tall_linear_w(obs.reshape(b * n, o), w[:, :o], cr.fc1.bias)
+                if ids:
+                    x = (x.view(b, n, -1) + w[:, o:].t().unsqueeze(0)).reshape(b * n, -1)
+                return cr.trunk(x)[0].view(b, n, 1)
+            return torch.stack([cr.trunk(F.linear(obs[:, i], cr.fc1.weight[:, :o], cr.fc1.bias) + (cr.fc1.weight[:, o + i] if ids else 0.0))[0]
+                                for i, cr in enumerate(self.value_dicts)], 1)
+        obs_all = obs.reshape(b, n * o)
+        if self.args.shared_params:
+            cr = self.value_dicts[0]
+            w = cr.fc1.weight
+            base = tall_linear_w(obs_all, w[:, :n * o], cr.fc1.bias)                         # [b, h]: once per sample
+            if ids:
+                per_n = w[:, n * o:].t()                                                    # [n, h]: the id columns
+                if critic_head_ok(cr, base, b * n, n):
+                    return critic_head(cr, base, per_n).view(b, n, 1)
+                x = base.unsqueeze(1) + per_n.unsqueeze(0)
+            else:
+                x = base.unsqueeze(1).expand(b, n, -1)
+            return cr.trunk(x.reshape(b * n, -1))[0].view(b, n, 1)
+        return torch.stack([cr.trunk(F.linear(obs_all, cr.fc1.weight[:, :n * o], cr.fc1.bias) + (cr.fc1.weight[:, n * o + i] if ids else 0.0))[0]
+                            for i, cr in enumerate(self.value_dicts)], 1)
+
+    @torch.no_grad()
+    def advantages(self, batch: Batch, rewards: torch.Tensor, stride: Optional[int] = None) -> torch.Tensor:
+        """GAE on the STORED value / next_value (ppo.py:46-54) over chains of `stride`, through PPO.batchnorm with normalize_advantages
+        (ppo.py:58-59; the union of the ranks' batches under data-parallel training): [bs, n], no gradient"""
+        n, a = self.n_, self.args
+        S = int(self.__dict__.get("gae_stride", 1) if stride is None else stride)
+        adv = ppo_gae(rewards, batch["value"].float().view(-1, n), batch["next_value"].float().view(-1, n), batch["done"].float().view(-1),
+                      batch["last_step"].float().view(-1), S, a.gamma, a.lambda_)
+        if a.normalize_advantages:
+            adv = self._union_batchnorm(self._adv_batchnorm.to(adv.device), adv)
+        return adv.detach()
+
+    def get_loss(self, batch: Batch, want=("policy", "value"), stride: Optional[int] = None):
+        """ppo.py:16-71.  batch: the fields of DDPGNet.get_loss plus last_step [bs, 1], value / next_value [bs, n, 1] (what the behaviour
+        critic gave at rollout time) and, for ppo_old_log_prob="stored", log_prob [bs, n, 1].  stride: the GAE chain stride (see the
+        class).  The returns use FRESH behaviour-net values of next_state, the advantages the STORED ones; the target net is not read.
+        No random number is drawn.  Returns (policy_loss, value_loss, (means, log_stds)); a loss not in `want` is None and its forward
+        passes are skipped (the reward BatchNorm sees the rewards in every call, as the reference's does)."""
+        n, a = self.n_, self.args
+        rewards = self.normalise_reward(batch["reward"].float())
+        valid = batch.get("valid")
+        policy_loss = value_loss = action_out = None
+        if "policy" in want:
+            actions, avail = batch["action"], batch["action_avail"]
+            means, log_stds, _ = self.policy(batch["state"], batch["last_hid"], means_grad_only=True)
+            action_out = (means, log_stds)
+            adv = self.advantages(batch, rewards.detach(), stride)
+            old = actions if a.ppo_old_log_prob == "reference" else batch["log_prob"].float()       # models/model.py:309
+            policy_loss = ppo_policy_loss(means, actions, log_stds, avail, old, adv, valid, a.eps_clip)
+        if "value" in want:
+            values = self.value(batch["state"]).view(-1, n)
+            with torch.no_grad():
+                next_values = self.value(batch["next_state"]).view(-1, n)                           # ppo.py:41, 56: the behaviour net, now
+            value_loss = ppo_value_loss(values, batch["value"].float().view(-1, n), rewards.detach(), next_values, batch["done"].float().view(-1),
+                                        valid, a.gamma, a.eps_clip, a.value_loss_coef)
+        return policy_loss, value_loss, action_out
+
+
 def net_class(alg: str):
     """the module class of an algorithm name (models/model_registry.py:14-25); KeyError for a name that is not built"""
-    for c in (DDPGNet, COMANet, MAACNet, SQDDPGNet):
+    for c in (DDPGNet, COMANet, MAACNet, SQDDPGNet, PPONet):
         if alg in c.ALGS:
             return c
     raise KeyError(alg)
@@ -1868,6 +2184,12 @@ class PGTrainer:
                 self._collective(self._dist.all_reduce, t)
                 self.collectives["all_reduce_reward_stats"] += 1
             self.behaviour_net.__dict__["_dp_all_reduce"] = _bn_reduce
+        self.on_policy = alg in ("coma", "mappo", "ippo")         # models/model.py:53-56: the ring is emptied after every update round
+        self.ppo = isinstance(self.behaviour_net, PPONet)
+        if self.ppo and env is not None:
+            # rows enter the ring in (step, env) order, n_envs per insertion: row i + n_envs is the same env one step later, wherever a
+            # sampled window starts — the GAE chain stride (PPONet)
+            self.behaviour_net.__dict__["gae_stride"] = int(env.n_envs)
         if self._dist is not None:                               # identical replicas to start from
             for t in self.behaviour_net.state_dict().values():
                 self._collective(self._dist.broadcast, t, src=0)
@@ -2009,6 +2331,8 @@ class PGTrainer:
             return False
         if net.alg == "sqddpg":            # SQDDPG's target is valued on coalitions DRAWN in every get_loss call (sqddpg.py:145): nothing is cached
             return False
+        if self.ppo:                       # MAPPO / IPPO read no target net and no next action (ppo.py:16-71): nothing to cache
+            return False
         st = rb.store
         if not all(k in st for k in ("next_state", "action_avail", "hid", "action")):
             return False
@@ -2081,7 +2405,7 @@ class PGTrainer:
                     self.replay_buffer.store.pop("next_obs_term_cached", None)
             for _ in range(a.policy_update_epochs):
                 self.policy_replay_process(stat)
-            if self.behaviour_net.alg == "coma":                 # on-policy: the ring is emptied after every update round (model.py:53-56)
+            if self.on_policy:                                   # COMA, MAPPO, IPPO: the ring is emptied after every update round (model.py:53-56)
                 self.replay_buffer.clear()
         if a.target and self.steps % a.target_update_freq == 0:
             with self._phase("target_update"):
@@ -2094,7 +2418,8 @@ class PGTrainer:
         prefix = "mean_train_" if train else "mean_test_"
         avail = env.get_avail_actions().to(dv)
 
-        fused_explore = (train and self.device.type == "cuda" and a.action_dim == 1 and a.continuous and not a.gaussian_policy
+        # (MAPPO / IPPO store the log-probability of the taken action, which the one-launch exploration sample does not produce)
+        fused_explore = (train and self.device.type == "cuda" and a.action_dim == 1 and a.continuous and not a.gaussian_policy and not self.ppo
                          and os.environ.get("MAPDN_FUSED_ROLLOUT", "1") != "0")
         if fused_explore:
             from . import _lib
@@ -2118,10 +2443,10 @@ class PGTrainer:
                                                          actual.data_ptr(), means.numel(), torch.cuda.current_stream(dv).cuda_stream))
                 return action, hid, dict(action_pol=action_pol, last_hid=last_hid, hid=hid, actual=actual)
             if train:
-                action, action_pol, _, _, hid = net.get_actions(obs, "train", True, avail, False, last_hid)
+                action, action_pol, log_prob, _, hid = net.get_actions(obs, "train", True, avail, False, last_hid)
             else:
-                action, action_pol, _, _, hid = net.get_actions(obs, "test", False, avail, False, last_hid)
-            return action, hid, dict(action_pol=action_pol, last_hid=last_hid, hid=hid)
+                action, action_pol, log_prob, _, hid = net.get_actions(obs, "test", False, avail, False, last_hid)
+            return action, hid, dict(action_pol=action_pol, last_hid=last_hid, hid=hid, log_prob=log_prob)
 
         def on_step(t, obs, action, reward, done, info, next_obs, alive, aux):
             action_pol, last_hid, hid = aux["action_pol"], aux["last_hid"], aux["hid"]
@@ -2129,6 +2454,9 @@ class PGTrainer:
                          next_state=next_obs, done=done.view(B, 1).float(),
                          last_step=(done | (t == a.max_steps - 1)).view(B, 1).float(), action_avail=avail,
                          last_hid=last_hid, hid=hid, valid=alive.clone())
+            if self.ppo:                                        # models/model.py:212-222: what the behaviour net gave BEFORE this step's update
+                with torch.no_grad():
+                    trans.update(log_prob=aux["log_prob"], value=net.value(obs), next_value=net.value(next_obs))
             self.transition_update(trans, stat)
             self.steps += 1
 
