@@ -640,6 +640,40 @@ typedef struct mapdn_droop_config {
 int mapdn_droop_actions(mapdn_handle* h, const mapdn_droop_config* cfg, double* actions, double* vm_pu, int32_t* iterations,
                         uint8_t* status, void* stream);
 
+/* ---- Optimal power flow: the reference's second traditional baseline (the traditional_control scripts: runopf on the loss objective with
+ * the PV inverters' reactive power as the controls), as a reduced-space SQP on the handle's own power flow.
+ * Per env, on the env's current state (the loads and PV the next mapdn_step solves with, noise applied):
+ *     minimise   sum_k Re(V_k conj((Ybus V)_k))            (the total active loss)
+ *     over       a in [-1, 1]^ns,  q_j = sqrt(s_max_j^2 - p_j^2) a_j
+ *     subject to v_lower <= |V_k(a)| <= v_upper at every non-slack bus.
+ * A field left 0 takes its default (so an all-zero struct, or NULL, is the default configuration). */
+typedef struct mapdn_opf_config {
+  double v_lower, v_upper;          /* voltage bounds (p.u.): the env's (mapdn_env_config); need 0 < v_lower < v_upper              */
+  double v_tol;                     /* a point is feasible when its violation is <= v_tol: 5e-6 (MATPOWER's opf.violation); > 0     */
+  double step_tol;                  /* stop when |d|inf < step_tol (and feasible): 1e-6; > 0                                        */
+  int32_t max_iter;                 /* power flows per env at most: 50; 1 ... 1000                                                  */
+  int32_t max_backtrack;            /* halvings of the step in a row when the trial point's power flow fails: 8; 1 ... 60          */
+} mapdn_opf_config;
+
+/* a = 0, then for i = 1 ... max_iter: power flow at a; S = d|V|/da, g = dloss/da and the Gauss-Newton Hessian H from the converged V
+ * (exact sensitivities: the Jacobian's block LU on the tree); d = argmin g'd + d'Hd/2 s.t. -1 - a <= d <= 1 - a, v_lower <= |V| + S d
+ * <= v_upper; stop when |d|inf < step_tol and the violation is <= v_tol, else a <- clip(a + d).  A trial point whose power flow fails
+ * is retried at a + d/2, a + d/4, ...
+ *   actions    f64 [B, ns]: a of the last solved power flow (step() takes it unclipped)
+ *   vm_pu      f64 [B, nb] or NULL: |V| of that power flow (NaN when none solved)
+ *   loss_mw    f64 [B]: the objective there, MW;  violation f64 [B]: max(|V| - v_upper, v_lower - |V|, 0) over the non-slack buses, p.u.
+ *              (both NaN when none solved)
+ *   iterations i32 [B]: power flows solved
+ *   status     u8 [B]: 0 converged and feasible, 1 max_iter reached (or the last QP hit its iteration cap): the last solved point with
+ *              its violation, 2 a power flow failed even after backtracking (actions = the last a that solved, 0 if the first failed),
+ *              3 not solved (terminated / frozen / waiting for its auto-reset restart; a = 0)
+ * Device pointers on `stream`.  Not a step-path call (it polls the count of envs still iterating; the workspace is allocated on the
+ * first call).  The obs, state, results, returns, counters and the next mapdn_step are what they would have been without the call.
+ * MAPDN_E_INVALID, on host-only handles too, for a config outside the ranges above and for what the tree sweeps do not cover:
+ * meshed nets and handles on another solver than the tree solver, voltage-dependent (ZIP) loads, fused buses, more than 64 sgens. */
+int mapdn_opf_actions(mapdn_handle* h, const mapdn_opf_config* cfg, double* actions, double* vm_pu, double* loss_mw, double* violation,
+                      int32_t* iterations, uint8_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,7 +36,7 @@ EXPORTS = (
     "mapdn_critic_head_forward", "mapdn_critic_head_scratch_floats", "mapdn_critic_head_backward", "mapdn_critic_head_backward_dot", "mapdn_critic_head_mse", "mapdn_get_profile_stats",
     "mapdn_explore_actions", "mapdn_rollout_stats", "mapdn_copy_segments",
     "mapdn_policy_forward_train", "mapdn_policy_backward", "mapdn_policy_backward_scratch_floats", "mapdn_get_dc_angles",
-    "mapdn_get_nr_kernel", "mapdn_droop_actions", "mapdn_policy_forward_geometry", "mapdn_critic_head_backward_geometry",
+    "mapdn_get_nr_kernel", "mapdn_droop_actions", "mapdn_opf_actions", "mapdn_policy_forward_geometry", "mapdn_critic_head_backward_geometry",
     "mapdn_critic_twin_forward", "mapdn_critic_twin_scratch_floats", "mapdn_critic_twin_geometry", "mapdn_critic_twin_mse",
     "mapdn_critic_head_counterfactual",
     "mapdn_attention_forward", "mapdn_attention_backward", "mapdn_attention_scratch_floats", "mapdn_attention_max_agents",
@@ -113,6 +113,32 @@ def make_droop_config(cfg=None) -> CDroopConfig:
         if unknown:
             raise KeyError(f"unknown droop config keys {sorted(unknown)}")
     for name, typ in CDroopConfig._fields_:
+        v = get(name, None)
+        if v is not None:
+            setattr(c, name, int(v) if typ is C.c_int32 else float(v))
+    return c
+
+
+class COPFConfig(C.Structure):
+    """mapdn_opf_config: a field left 0 takes its default; v_lower / v_upper the env's (include/mapdn.h)"""
+    _fields_ = [("v_lower", C.c_double), ("v_upper", C.c_double), ("v_tol", C.c_double), ("step_tol", C.c_double),
+                ("max_iter", C.c_int32), ("max_backtrack", C.c_int32)]
+
+
+OPF_STATUS = ("converged", "max_iter", "pf_failed", "not_solved")      # mapdn_opf_actions status codes 0 .. 3
+
+
+def make_opf_config(cfg=None) -> COPFConfig:
+    """COPFConfig from None (the defaults), a dict or an object with the same attribute names (baselines.OPFConfig)"""
+    c = COPFConfig()
+    if cfg is None:
+        return c
+    get = cfg.get if isinstance(cfg, dict) else (lambda k, _d=None: getattr(cfg, k, _d))
+    if isinstance(cfg, dict):
+        unknown = set(cfg) - {f for f, _ in COPFConfig._fields_}
+        if unknown:
+            raise KeyError(f"unknown opf config keys {sorted(unknown)}")
+    for name, typ in COPFConfig._fields_:
         v = get(name, None)
         if v is not None:
             setattr(c, name, int(v) if typ is C.c_int32 else float(v))
@@ -258,6 +284,7 @@ def load():
     lib.mapdn_nr_timing.argtypes = [vp, C.c_int32]
     lib.mapdn_nr_time_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.mapdn_droop_actions.argtypes = [vp, C.POINTER(CDroopConfig), vp, vp, vp, vp, vp]
+    lib.mapdn_opf_actions.argtypes = [vp, C.POINTER(COPFConfig), vp, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("mapdn_last_error", "mapdn_destroy", "mapdn_build_info"):
             getattr(lib, name).restype = C.c_int

@@ -1,10 +1,12 @@
-"""Traditional baselines of the MAPDN paper next to the MARL learners: droop control and no control.
+"""Traditional baselines of the MAPDN paper next to the MARL learners: droop control, optimal power flow and no control.
 
-The reference ships them as MATLAB scripts (traditional_control/pf_droop_matpower_all.m, run "pf" = no control).  Here they act on
+The reference ships them as MATLAB scripts (traditional_control/*.m: the droop loop, runopf, run "pf" = no control).  Here they act on
 the batched env:
 
 ``DroopConfig``     the droop script's parameters (breakpoints va < vb <= vc < vd, damping, max_iter, v_tol, reactive_ratio)
 ``DroopControl``    the droop controller: per env step, VoltageControlBatch.droop_actions (the fixed-point loop runs on the GPU)
+``OPFConfig``       the OPF's parameters (voltage bounds, v_tol, step_tol, max_iter, max_backtrack; None / 0 = the default)
+``OPFControl``      the OPF baseline: per env step, VoltageControlBatch.opf_actions (a reduced-space SQP on the GPU)
 ``NoControl``       a = 0 (the script's "pf" run)
 ``BaselineTester``  PGTester's `run` / `batch_run` with a baseline in place of the policy: the same record and `mean_test_*`
                     formats, so the paper's comparison table and the plotting scripts take baseline results unchanged.
@@ -48,6 +50,37 @@ class DroopControl:
         a, it, st = env.droop_actions(self.config)
         if self.history is not None:
             self.history.append((it.clone(), st.clone()))
+        return a
+
+
+@dataclass
+class OPFConfig:
+    """mapdn_opf_config (include/mapdn.h): 0 = the default; v_lower / v_upper default to the env's own bounds"""
+    v_lower: float = 0.0
+    v_upper: float = 0.0
+    v_tol: float = 5e-6
+    step_tol: float = 1e-6
+    max_iter: int = 50
+    max_backtrack: int = 8
+
+    def as_dict(self):
+        return asdict(self)
+
+
+class OPFControl:
+    """The OPF baseline on a VoltageControlBatch.  `history` (when kept) collects the (loss_mw, violation, iterations, status)
+    tensors of every call."""
+
+    name = "opf"
+
+    def __init__(self, config: OPFConfig | None = None, keep_history: bool = False):
+        self.config = config or OPFConfig()
+        self.history = [] if keep_history else None
+
+    def actions(self, env):
+        a, loss, viol, it, st = env.opf_actions(self.config)
+        if self.history is not None:
+            self.history.append((loss.clone(), viol.clone(), it.clone(), st.clone()))
         return a
 
 

@@ -175,4 +175,28 @@ struct DroopState {
 };
 void launch_droop_update(const Dev& d, const DroopState& s, int iter, hipStream_t st);
 
+// ---- OPF baseline (opf.hip, opf.hpp; mapdn_opf_actions).  Per-env status (opf.hpp OPF_*) as in include/mapdn.h; RUNNING only between launches.
+struct OpfState {
+  double v_lower, v_upper, v_tol, step_tol;
+  int32_t max_iter, max_backtrack;
+  // topology tables (by node position): parent, children in the canonical order of the sweeps (CSR), the node of every sgen's bus
+  // (n: the slack), the Y / M constants (opf.hpp OY_*), the slack's own term of the loss, the Vout row of |V| of every bus
+  const int32_t *par, *cptr, *cidx, *sg_node;
+  const double* yt; double loss_slack;
+  const int32_t* vm_row;
+  // workspace of the linearisation, env-minor: the block-LU factors [n][OPF_FAC], M V [n][2], dV and M dV [n][ns][2], S [n][ns],
+  // H [ns][ns], g [ns]; of the QP: d [ns], y [ns + n], scratch (opf_qp_work)
+  double *fac, *mv, *X, *W, *S, *H, *g, *qd, *qy, *qw;
+  double *a, *a_sol;                 // [ns][Bp]: the action of the next solve, the action of the last converged solve
+  double *t, *loss, *viol, *loss_out, *viol_out;   // [Bp]: step length; loss (p.u.) and violation of the last solve / of a_sol
+  int32_t *iters, *nback;                           // [Bp] solves so far, failed solves in a row
+  uint8_t *status, *act, *lin, *qp_capped;          // [Bp]; act: the solver's active flags of the OPF solves; lin: linearised by the last launch
+  const int32_t* nr_iters; const uint8_t* nr_conv;  // [Bp] Dev::iters / conv of those launches
+  int32_t* n_active;                 // [max_iter + 1] envs still iterating after update i
+  double* vm_out;                    // [B][nbo] env-major, or nullptr
+};
+void launch_opf_update(const Dev& d, const OpfState& s, int iter, hipStream_t st);
+void launch_opf_linearise(const Dev& d, const OpfState& s, hipStream_t st);
+void launch_opf_qp(const Dev& d, const OpfState& s, hipStream_t st);
+
 }  // namespace mapdn

@@ -361,6 +361,27 @@ class VoltageControlBatch:
                                                      it.data_ptr(), st.data_ptr(), self._stream()), self._h)
         return (act, it, st, vm) if vm_pu else (act, it, st)
 
+    def opf_actions(self, config=None, vm_pu=False):
+        """The paper's OPF baseline on the current state of every env (mapdn_opf_actions, include/mapdn.h): the actions that minimise
+        the total active loss subject to v_lower <= |V| <= v_upper at every non-slack bus, by a reduced-space SQP whose power flows
+        are the env's own.  config: None (the defaults), a baselines.OPFConfig or a dict of its fields.  Returns (actions float64
+        [B, n_sgen], loss_mw float64 [B], violation float64 [B] p.u., iterations int32 [B] power flows solved, status uint8 [B]:
+        0 converged and feasible, 1 max_iter or a QP cap reached, 2 a power flow failed even after backtracking, 3 not solved — done /
+        waiting for its restart), and vm_pu float64 [B, n_bus] when vm_pu=True.  Radial nets on the tree solver with constant-power
+        loads, no fused buses and at most 64 sgens; anything else raises.  The env's state and its next step() are not affected."""
+        cc = _lib.make_opf_config(config)
+        B, dv, f64 = self.n_envs, self.device, torch.float64
+        act = torch.empty(B, self.n_sgen, dtype=f64, device=dv)
+        loss = torch.empty(B, dtype=f64, device=dv)
+        viol = torch.empty(B, dtype=f64, device=dv)
+        it = torch.empty(B, dtype=torch.int32, device=dv)
+        st = torch.empty(B, dtype=torch.uint8, device=dv)
+        vm = torch.empty(B, self.n_bus, dtype=f64, device=dv) if vm_pu else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mapdn_opf_actions(self._h, _lib.C.byref(cc), act.data_ptr(), vm.data_ptr() if vm_pu else None,
+                                                   loss.data_ptr(), viol.data_ptr(), it.data_ptr(), st.data_ptr(), self._stream()), self._h)
+        return (act, loss, viol, it, st, vm) if vm_pu else (act, loss, viol, it, st)
+
     def ybus_dense(self):
         """Ybus over the ELECTRICAL nodes (n_nodes x n_nodes; == buses unless closed bus-bus switches fuse some: include/mapdn.h)"""
         nn = self.geometry()["n_nodes"]
@@ -566,6 +587,12 @@ class VoltageControl(MultiAgentEnv):
         out = self._b.droop_actions(config, vm_pu=vm_pu)
         a, it, st = out[0][0].cpu().numpy(), int(out[1][0].item()), int(out[2][0].item())
         return (a, it, st, out[3][0].cpu().numpy()) if vm_pu else (a, it, st)
+
+    def opf_action(self, config=None, vm_pu=False):
+        """VoltageControlBatch.opf_actions for this one env, as numpy: (action [n_sgen], loss_mw, violation, iterations, status[, vm_pu])"""
+        out = self._b.opf_actions(config, vm_pu=vm_pu)
+        r = (out[0][0].cpu().numpy(), float(out[1][0].item()), float(out[2][0].item()), int(out[3][0].item()), int(out[4][0].item()))
+        return r + (out[5][0].cpu().numpy(),) if vm_pu else r
 
     def _obs_list(self, obs):
         o = obs[0].double().cpu().numpy()
