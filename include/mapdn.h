@@ -674,6 +674,27 @@ typedef struct mapdn_opf_config {
 int mapdn_opf_actions(mapdn_handle* h, const mapdn_opf_config* cfg, double* actions, double* vm_pu, double* loss_mw, double* violation,
                       int32_t* iterations, uint8_t* status, void* stream);
 
+/* Diagnostic entry for the kernel tests of the OPF baseline (tests/test_opf_kernels_gpu.py): ONE linearisation and ONE QP at the caller's
+ * set-points, by the launches of mapdn_opf_actions' first iteration and nothing else — the start launch, which here begins from `a`
+ * (clipped to [-1, 1]) instead of 0 and writes the Sbus of that a; one power flow in MODE_SOLVE with the OPF's own active set;
+ * k_opf_linearise; k_opf_qp from zero multipliers — and then the workspace as those launches left it.  Device pointers on `stream`:
+ *   a          f64 [B, ns] in: the set-points;  ns: the row length of a, must be the handle's number of sgens
+ * and, each may be NULL, env-major, by NODE k = 0 .. n - 1 (the elimination position; bus_of_pos of mapdn_get_flat_factors maps it to its
+ * bus, n = n_bus - 1, the slack is no node):
+ *   v_re, v_im, vm f64 [B, n]: the converged V and the |V| the kernels read;   S f64 [B, n, ns] = d|V_k| / da_j;   g f64 [B, ns] = dloss / da (p.u.);   H f64 [B, ns, ns]
+ *   loss_mw    f64 [B] (MW) and violation f64 [B] (p.u., against the config's bounds) at that V
+ *   d          f64 [B, ns] the QP's step;   y f64 [B, ns + n] its multipliers: the box rows, then one row per node (> 0: upper bound)
+ *   linearised u8 [B]: 1 when the env was solved (not terminated / frozen / waiting for its restart), its power flow converged and it was
+ *              linearised; 0 otherwise: then d and y are 0, and V, S, g, H, loss_mw and violation are unspecified (workspace of an
+ *              earlier call)
+ *   qp_capped  u8 [B]: 1 when the QP hit its iteration cap (d is then its least-violation compromise)
+ * Like mapdn_opf_actions: the obs, state, results, returns, counters and the next mapdn_step are what they would have been without the
+ * call, also after mapdn_solve_only; the refusals of mapdn_opf_actions' config and nets (checked on host-only handles too), and
+ * MAPDN_E_INVALID for a == NULL or an ns that is not the handle's; nothing is launched on a refusal. */
+int mapdn_opf_probe(mapdn_handle* h, const mapdn_opf_config* cfg, const double* a, int32_t ns, double* v_re, double* v_im, double* vm, double* S,
+                    double* g, double* H, double* loss_mw, double* violation, double* d, double* y, uint8_t* linearised,
+                    uint8_t* qp_capped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

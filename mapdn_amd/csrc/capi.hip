@@ -98,6 +98,8 @@ struct mapdn_handle {
   // OPF baseline (mapdn_opf_actions): likewise
   OpfState opf{};
   bool opf_ready = false;
+  double* opf_probe_a = nullptr;                 // mapdn_opf_probe: its set-points env-minor [ns][Bp], and the rows of its exports
+  const int32_t* opf_probe_rows = nullptr;       // identity rows | the Re V, the Im V, the |V| row of every node
 };
 
 static std::string g_create_err;
@@ -1341,6 +1343,68 @@ int mapdn_opf_actions(mapdn_handle* h, const mapdn_opf_config* cfg, double* acti
   if (!h->was_reset) { h->err = "opf_actions before reset"; return MAPDN_E_STATE; }
   HIPCHK(h, hipSetDevice(h->device));
   return opf_run(h, c, actions, vm_pu, loss_mw, violation, iterations, status, (hipStream_t)stream);
+} MAPDN_CATCH(h)
+
+// One linearisation and one QP at the caller's set-points, for the kernel tests: the launches of opf_run's first iteration (the start
+// launch — which here begins from a instead of 0 and writes the Sbus of that a —, the solve, k_opf_linearise, k_opf_qp; no k_opf_update
+// after them), then the workspace as it stands, env-major.  Writes what opf_run writes.
+int mapdn_opf_probe(mapdn_handle* h, const mapdn_opf_config* cfg, const double* a, int32_t ns, double* v_re, double* v_im, double* vm, double* S,
+                    double* g, double* H, double* loss_mw, double* violation, double* d, double* y, uint8_t* linearised,
+                    uint8_t* qp_capped, void* stream) try {
+  if (!h) return MAPDN_E_INVALID;
+  mapdn_opf_config c;
+  if (const char* why = opf_resolve(h, cfg, c)) return api_fail(h, MAPDN_E_INVALID, why);
+  if (!a) return api_fail(h, MAPDN_E_INVALID, "opf_probe: a is NULL");
+  if (ns != h->plan.ns) return api_fail(h, MAPDN_E_INVALID, "opf_probe: ns must be the handle's number of sgens");
+  NEEDDEV(h);
+  if (!h->was_reset) { h->err = "opf_probe before reset"; return MAPDN_E_STATE; }
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (const int rc = opf_prepare(h)) return rc;
+  const Dev& dv = h->d;
+  const int n = dv.n;
+  const int io = std::max(std::max(n * ns, ns * ns), ns + n);      // identity rows for the widest export
+  if (!h->opf_probe_a) { if (const int rc = dalloc(h, &h->opf_probe_a, (size_t)ns * dv.Bp)) return rc; }
+  if (!h->opf_probe_rows) {
+    std::vector<int32_t> rows((size_t)io + 3 * (size_t)n);
+    for (int i = 0; i < io; ++i) rows[(size_t)i] = i;
+    for (int k = 0; k < n; ++k) {
+      rows[(size_t)io + k] = (int32_t)dv.r_vout + VOF * k + VO_E; rows[(size_t)io + n + k] = (int32_t)dv.r_vout + VOF * k + VO_F;
+      rows[(size_t)io + 2 * n + k] = (int32_t)dv.r_vout + VOF * k + VO_VM;
+    }
+    if (const int rc = dupload(h, &h->opf_probe_rows, rows)) return rc;
+  }
+  const int32_t* iota = h->opf_probe_rows;
+  const int32_t* erow = iota + io;
+  OpfState s = h->opf;
+  s.v_lower = c.v_lower; s.v_upper = c.v_upper; s.v_tol = c.v_tol; s.step_tol = c.step_tol;
+  s.max_iter = c.max_iter; s.max_backtrack = c.max_backtrack; s.vm_out = nullptr; s.a0 = h->opf_probe_a;
+  launch_to_envminor(dv, a, h->opf_probe_a, ns, st);
+  HIPCHK(h, hipMemsetAsync(s.n_active, 0, sizeof(int32_t), st));
+  if (h->sbus_stale) {                           // as opf_run
+    HIPCHK(h, hipMemsetAsync(s.a, 0, (size_t)dv.ns * dv.Bp * sizeof(double), st));
+    launch_inject(dv, MODE_SOLVE, nullptr, MAPDN_F64, dv.cur_pl, dv.cur_ql, dv.cur_pv, s.a, 0, st);
+  }
+  launch_opf_update(dv, s, 0, st);
+  Dev dd = dv;
+  dd.active = s.act; dd.iters = const_cast<int32_t*>(s.nr_iters); dd.conv = const_cast<uint8_t*>(s.nr_conv);
+  nr_launch(h, MODE_SOLVE, nullptr, nullptr, nullptr, st, nullptr, 0, &dd);
+  launch_opf_linearise(dd, s, st);
+  launch_opf_qp(dd, s, st);
+  if (v_re) transpose_out(h, dv.nrbuf, 1.0, erow, v_re, n, st);
+  if (v_im) transpose_out(h, dv.nrbuf, 1.0, erow + n, v_im, n, st);
+  if (vm) transpose_out(h, dv.nrbuf, 1.0, erow + 2 * n, vm, n, st);
+  if (S) transpose_out(h, s.S, 1.0, iota, S, n * ns, st);
+  if (g) transpose_out(h, s.g, 1.0, iota, g, ns, st);
+  if (H) transpose_out(h, s.H, 1.0, iota, H, ns * ns, st);
+  if (loss_mw) transpose_out(h, s.loss, dv.sn, iota, loss_mw, 1, st);
+  if (violation) transpose_out(h, s.viol, 1.0, iota, violation, 1, st);
+  if (d) transpose_out(h, s.qd, 1.0, iota, d, ns, st);
+  if (y) transpose_out(h, s.qy, 1.0, iota, y, ns + n, st);
+  if (linearised) launch_copy_u8(s.lin, linearised, dv.B, st);
+  if (qp_capped) launch_copy_u8(s.qp_capped, qp_capped, dv.B, st);
+  HIPCHK(h, hipGetLastError());
+  return MAPDN_OK;
 } MAPDN_CATCH(h)
 
 // ---- the PPO half of MAPPO / IPPO's update (csrc/ppo.hip): argument checks here, nothing is launched on a refusal

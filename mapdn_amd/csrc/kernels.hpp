@@ -188,6 +188,7 @@ struct OpfState {
   // H [ns][ns], g [ns]; of the QP: d [ns], y [ns + n], scratch (opf_qp_work)
   double *fac, *mv, *X, *W, *S, *H, *g, *qd, *qy, *qw;
   double *a, *a_sol;                 // [ns][Bp]: the action of the next solve, the action of the last converged solve
+  const double* a0;                  // [ns][Bp] the set-points the start launch begins from (clipped to [-1, 1]: mapdn_opf_probe), or nullptr: a = 0
   double *t, *loss, *viol, *loss_out, *viol_out;   // [Bp]: step length; loss (p.u.) and violation of the last solve / of a_sol
   int32_t *iters, *nback;                           // [Bp] solves so far, failed solves in a row
   uint8_t *status, *act, *lin, *qp_capped;          // [Bp]; act: the solver's active flags of the OPF solves; lin: linearised by the last launch

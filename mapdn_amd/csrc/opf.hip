@@ -155,7 +155,8 @@ __global__ void __launch_bounds__(64) k_opf_qp(Dev d, OpfState s) {
   if (tm.sl == 0) s.qp_capped[e] = (uint8_t)out.capped;
 }
 
-// iter == 0: start — a = 0, status 3 for the envs that step() would not solve, the Sbus of the first solve (as k_droop_update does).
+// iter == 0: start — a = 0 (or the caller's set-points s.a0, clipped: the probe), status 3 for the envs that step() would not solve,
+// the Sbus of the first solve (as k_droop_update does).
 // iter = i > 0: after the i-th solve and its QP, opf_decide (opf.hpp) — the solve failed: halve t (at most max_backtrack times in a
 // row) and retry from the last solved a, or stop with status 2;  it converged: record a, |V|, loss and violation, stop with status 0
 // when |d|inf < step_tol, the violation is <= v_tol and the QP did not hit its cap, with status 1 at max_iter or at the least-violation
@@ -171,7 +172,11 @@ __global__ void __launch_bounds__(DL * DS) k_opf_update(Dev d, OpfState s, int i
   if (iter == 0) {
     const bool run = valid && d.done[e] == 0;
     if (valid) {
-      for (int j = sl; j < d.ns; j += DS) { const size_t o = (size_t)j * S + e; s.a[o] = 0.0; s.a_sol[o] = 0.0; s.qd[o] = 0.0; }
+      for (int j = sl; j < d.ns; j += DS) {
+        const size_t o = (size_t)j * S + e;
+        const double a0 = s.a0 ? opf_trial(s.a0[o], 0.0, 0.0) : 0.0;
+        s.a[o] = a0; s.a_sol[o] = a0; s.qd[o] = 0.0;
+      }
       for (int r = sl; r < d.ns + d.n; r += DS) s.qy[(size_t)r * S + e] = 0.0;
       if (sl == 0) {
         s.iters[e] = 0; s.nback[e] = 0; s.t[e] = 1.0; s.lin[e] = 0; s.qp_capped[e] = 0;

@@ -382,6 +382,31 @@ class VoltageControlBatch:
                                                    loss.data_ptr(), viol.data_ptr(), it.data_ptr(), st.data_ptr(), self._stream()), self._h)
         return (act, loss, viol, it, st, vm) if vm_pu else (act, loss, viol, it, st)
 
+    def opf_probe(self, a, config=None):
+        """Diagnostic (mapdn_opf_probe, include/mapdn.h): one linearisation and one QP of the OPF baseline at the set-points a [B, n_sgen]
+        in [-1, 1], by the launches of opf_actions' first iteration.  Returns a dict of tensors by NODE (elimination position; `bus_of_node`
+        [n] maps it to its bus): v (complex128 [B, n]), vm [B, n], S [B, n, ns], g [B, ns], H [B, ns, ns], loss_mw [B], violation [B], d [B, ns],
+        y [B, ns + n], linearised and qp_capped (bool [B]).  Rows of envs that were not linearised hold d = y = 0 and are unspecified
+        otherwise.  The env's state and its next step() are not affected."""
+        cc = _lib.make_opf_config(config)
+        B, dv, f64, ns = self.n_envs, self.device, torch.float64, self.n_sgen
+        a = torch.as_tensor(a, dtype=f64, device=dv).contiguous()
+        assert a.shape == (B, ns)
+        bop = np.zeros(self.n_bus, np.int32)
+        fac = np.zeros((self.n_bus - 1) * 12)
+        _lib.check(self._lib.mapdn_get_flat_factors(self._h, _lib._p(fac, _lib._pd), _lib._p(bop, _lib._pi)), self._h)
+        n = self.n_bus - 1
+        new = lambda *shape, dtype=f64: torch.zeros(*shape, dtype=dtype, device=dv)
+        out = dict(v_re=new(B, n), v_im=new(B, n), vm=new(B, n), S=new(B, n, ns), g=new(B, ns), H=new(B, ns, ns), loss_mw=new(B), violation=new(B),
+                   d=new(B, ns), y=new(B, ns + n), linearised=new(B, dtype=torch.uint8), qp_capped=new(B, dtype=torch.uint8))
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mapdn_opf_probe(self._h, _lib.C.byref(cc), a.data_ptr(), ns, *[t.data_ptr() for t in out.values()],
+                                                 self._stream()), self._h)
+        out["v"] = torch.complex(out.pop("v_re"), out.pop("v_im"))
+        out["linearised"], out["qp_capped"] = out["linearised"].bool(), out["qp_capped"].bool()
+        out["bus_of_node"] = torch.as_tensor(bop[:n].astype(np.int64))
+        return out
+
     def ybus_dense(self):
         """Ybus over the ELECTRICAL nodes (n_nodes x n_nodes; == buses unless closed bus-bus switches fuse some: include/mapdn.h)"""
         nn = self.geometry()["n_nodes"]

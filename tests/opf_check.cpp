@@ -3,6 +3,9 @@
 //         -> x[n][ns][2] = (dtheta, u = d|V| / |V|) of J X = E by the tree elimination
 //   qp:   1, n, ns, vl, vu | g[ns] | H[ns][ns] | S[n][ns] | v[n] | a[ns]
 //         -> d[ns] | y[ns + n] | newton, capped, kkt | stationarity, violation, complementarity (opf_qp_kkt at (d, y))
+//   linearise: 4, n, ns, nc | as tree | vm[n] | loss_slack
+//         -> S[n][ns] | g[ns] | H[ns][ns] | loss: the elimination of opf.hpp, then k_opf_linearise's sums (M V, dV, W = M dV, g, H, the
+//            loss) restated for the host in the kernel's order — what float64 without pivoting gives on that net at that V
 //   decide: 3, step_tol, v_tol, max_iter, max_backtrack | rows of (iter, solved, nback, t, dn, viol, prev_viol, capped)
 //         -> rows of (run, status, nback, t) by opf_decide
 //   qp by a team: 2, lanes, then as qp — the same routine shared by `lanes` threads, as the sub-lanes of the kernel share it
@@ -81,6 +84,81 @@ int main(int argc, char** argv) {
     for (int k = 0; k < n; ++k) opf_elim_step(k, n, par.data(), cptr.data(), cidx.data(), yt, e, f, F, &P, &Q);
     out.assign((size_t)n * ns * 2, 0.0);
     for (int j = 0; j < ns; ++j) opf_solve_column(sg[j], w[j], n, par.data(), F, OpfVec{out.data() + (size_t)j * 2, 1}, (size_t)ns * 2);
+  } else if (mode == 4) {
+    const int n = (int)in[o++], ns = (int)in[o++], nc = (int)in[o++];
+    if (in.size() != (size_t)4 + n + (n + 1) + nc + (size_t)n * OPF_YT + 2 * n + 2 * ns + n + 1) return 4;
+    std::vector<int32_t> par(n), cptr(n + 1), cidx(nc), sg(ns);
+    for (int& p : par) p = (int)in[o++];
+    for (int& p : cptr) p = (int)in[o++];
+    for (int& p : cidx) p = (int)in[o++];
+    const double* yt = &in[o]; o += (size_t)n * OPF_YT;
+    const double* E = &in[o]; o += n;
+    const double* F = &in[o]; o += n;
+    for (int& p : sg) p = (int)in[o++];
+    const double* w = &in[o]; o += ns;
+    const double* VM = &in[o]; o += n;
+    const double loss_slack = in[o];
+    std::vector<double> fac((size_t)n * OPF_FAC), mv((size_t)n * 2), X((size_t)n * ns * 2), W((size_t)n * ns * 2);
+    OpfVec Fc{fac.data(), 1}, e{const_cast<double*>(E), 1}, f{const_cast<double*>(F), 1};
+    const size_t xs = (size_t)ns * 2;
+    for (int k = 0; k < n; ++k) {
+      const double* y = yt + (size_t)k * OPF_YT;
+      double mr = y[OY_KK] * E[k] + y[OY_MSV], mi = y[OY_KK] * F[k] + y[OY_MSV + 1];
+      const int p = par[k];
+      if (p < n) { mr += y[OY_MKP] * E[p] - y[OY_MKP + 1] * F[p]; mi += y[OY_MKP] * F[p] + y[OY_MKP + 1] * E[p]; }
+      for (int i = cptr[k]; i < cptr[k + 1]; ++i) {
+        const int c = cidx[i];
+        const double* yc = yt + (size_t)c * OPF_YT;
+        mr += yc[OY_MKP] * E[c] + yc[OY_MKP + 1] * F[c]; mi += yc[OY_MKP] * F[c] - yc[OY_MKP + 1] * E[c];
+      }
+      mv[(size_t)k * 2] = mr; mv[(size_t)k * 2 + 1] = mi;
+    }
+    double P, Q;
+    for (int k = 0; k < n; ++k) opf_elim_step(k, n, par.data(), cptr.data(), cidx.data(), yt, e, f, Fc, &P, &Q);
+    double loss = loss_slack;
+    for (int k = 0; k < n; ++k) {
+      const double* y = yt + (size_t)k * OPF_YT;
+      loss += E[k] * mv[(size_t)k * 2] + F[k] * mv[(size_t)k * 2 + 1] + (y[OY_MSV] * E[k] + y[OY_MSV + 1] * F[k]);
+    }
+    out.assign((size_t)n * ns + ns + (size_t)ns * ns + 1, 0.0);
+    double *S = out.data(), *g = S + (size_t)n * ns, *H = g + ns;
+    for (int j = 0; j < ns; ++j) {
+      double* x = X.data() + (size_t)j * 2; double* wv = W.data() + (size_t)j * 2;
+      opf_solve_column(sg[j], w[j], n, par.data(), Fc, OpfVec{x, 1}, xs);
+      for (int k = 0; k < n; ++k) {
+        const double th = x[(size_t)k * xs], u = x[(size_t)k * xs + 1];
+        S[(size_t)k * ns + j] = u * VM[k];
+        x[(size_t)k * xs] = u * E[k] - th * F[k]; x[(size_t)k * xs + 1] = u * F[k] + th * E[k];
+      }
+      double gj = 0.0;
+      for (int k = 0; k < n; ++k) {
+        const double* y = yt + (size_t)k * OPF_YT;
+        const double de = x[(size_t)k * xs], df = x[(size_t)k * xs + 1];
+        double wr = y[OY_KK] * de, wi = y[OY_KK] * df;
+        const int pk = par[k];
+        if (pk < n) {
+          const double pe = x[(size_t)pk * xs], pf = x[(size_t)pk * xs + 1];
+          wr += y[OY_MKP] * pe - y[OY_MKP + 1] * pf; wi += y[OY_MKP] * pf + y[OY_MKP + 1] * pe;
+        }
+        for (int i = cptr[k]; i < cptr[k + 1]; ++i) {
+          const int c = cidx[i];
+          const double* yc = yt + (size_t)c * OPF_YT;
+          const double ce = x[(size_t)c * xs], cf = x[(size_t)c * xs + 1];
+          wr += yc[OY_MKP] * ce + yc[OY_MKP + 1] * cf; wi += yc[OY_MKP] * cf - yc[OY_MKP + 1] * ce;
+        }
+        wv[(size_t)k * xs] = wr; wv[(size_t)k * xs + 1] = wi;
+        gj += de * mv[(size_t)k * 2] + df * mv[(size_t)k * 2 + 1];
+      }
+      g[j] = 2.0 * gj;
+    }
+    for (int j = 0; j < ns; ++j)
+      for (int i = 0; i <= j; ++i) {
+        const double* x = X.data() + (size_t)i * 2; const double* wv = W.data() + (size_t)j * 2;
+        double h = 0.0;
+        for (int k = 0; k < n; ++k) h += x[(size_t)k * xs] * wv[(size_t)k * xs] + x[(size_t)k * xs + 1] * wv[(size_t)k * xs + 1];
+        H[(size_t)i * ns + j] = H[(size_t)j * ns + i] = 2.0 * h;
+      }
+    out.back() = loss;
   } else if (mode == 1 || mode == 2) {
     const int lanes = mode == 2 ? (int)in[o++] : 1;
     if (lanes < 1 || lanes > 64) return 4;

@@ -93,12 +93,18 @@ def qp_kkt(g, H, A, lo, hi, d, y):
     return float(np.abs(r).max()), float(viol.max()), float(comp.max())
 
 
-def qp_solve(g, H, S, lo_box, hi_box, lo_row, hi_row, y0=None) -> QPResult:
+def qp_solve(g, H, S, lo_box, hi_box, lo_row, hi_row, y0=None, expanded=False) -> QPResult:
     """Augmented Lagrangian on every row of A = [I; S] with a semismooth Newton inner solve, as opf_qp_solve (csrc/opf.hpp):
       phi(d) = g'd + d'Hd / 2 + sum_r psi(c_r),  c = A d,  psi = (rho / 2) dist^2 of (c_r + y_r / rho) to [lo_r, hi_r]
     Newton: (H + rho A_P' A_P + ridge) p = -grad phi over the penalised rows P, backtracking on phi; then y <- the AL multiplier.
     y0: the multipliers of the previous SQP iteration's QP (the loop passes them unless that QP hit its cap).
-    Stops on the KKT residual of the QP: stationarity <= eps scale_g, violation <= eps, complementarity <= eps scale_g."""
+    Stops on the KKT residual of the QP: stationarity <= eps scale_g, violation <= eps, complementarity <= eps scale_g.
+    expanded: the backtracking compares phi along p as opf_qp_solve forms it — the quadratic expanded in t around d, c(t) = c + t A p —
+    and not phi recomputed at d + t p.  The two are the same function, but the recomputed one carries the rounding of the whole
+    objective, ~1e-16 |phi|, which near the optimum exceeds the decrease the Armijo test asks for: the search then halves t thirty
+    times and the QP crawls (case33, a daytime row at a = 0.9 x random: 444 Newton steps and the cap, where the routine and the
+    expanded form take 26 and 25).  The kernel tests (tests/test_opf_kernels_gpu.py) compare with expanded=True.  The SQP loop below
+    keeps the recomputed form: the iterates stored in tests/golden/opf_golden.npz were made with it."""
     ns = g.shape[0]
     A = np.vstack([np.eye(ns), S])
     lo, hi = np.concatenate([lo_box, lo_row]), np.concatenate([hi_box, hi_row])
@@ -132,9 +138,19 @@ def qp_solve(g, H, S, lo_box, hi_box, lo_row, hi_row, y0=None) -> QPResult:
             K = K + np.eye(ns) * (QP_RIDGE * max(float(np.diag(K).max()), 1e-300))
             p = np.linalg.solve(K, -grad)
             newton += 1
-            f0, slope, t = phi(d, y), float(grad @ p), 1.0
+            slope, t = float(grad @ p), 1.0
+            if expanded:
+                Ap, Hd, Hp = A @ p, H @ d, H @ p
+                gd, gp, dHd, dHp, pHp = float(g @ d), float(g @ p), float(d @ Hd), float(p @ Hd), float(p @ Hp)
+
+                def along(tt):
+                    zt = mult(c + tt * Ap, y)
+                    return gd + tt * gp + 0.5 * (dHd + 2.0 * tt * dHp + tt * tt * pHp) + float(np.sum((zt * zt - y * y) / (2.0 * rho_r)))
+            else:
+                along = lambda tt: phi(d + tt * p, y)
+            f0 = along(0.0)
             for _ in range(30):
-                if phi(d + t * p, y) <= f0 + 1e-4 * t * slope:
+                if along(t) <= f0 + 1e-4 * t * slope:
                     break
                 t *= 0.5
             d = d + t * p

@@ -239,8 +239,10 @@ def test_qp_routine_against_the_stored_qp_optima(host_opf, case):
 
 
 def test_update_decision_replays_the_restated_loop(host_opf, cases):
-    """opf_decide / k_opf_update's branches, failed power flows included, which no honest input reaches on the GPU: the restated loop
-    runs with a power flow that is made to fail at chosen calls, records what it saw before every decision, and opf_decide, replayed
+    """opf_decide / k_opf_update's branches, failed power flows included.  Honest inputs that reach the retry and status 2 on the GPU
+    exist only near voltage collapse (found by the search of tests/golden/make_opf_backtrack.py and run by
+    tests/test_opf_kernels_gpu.py); the other failure paths (at the first solve, at max_iter, after several retries) are replayed here: the
+    restated loop runs with a power flow that is made to fail at chosen calls, records what it saw before every decision, and opf_decide, replayed
     on those records, takes the same path (retry with half the step, at most max_backtrack times in a row; status 2 at the first
     solve, after too many failures and at max_iter; status 1 at max_iter) and ends where the loop ends."""
     net, prof, smax = cases["case33"]
@@ -289,6 +291,7 @@ def test_header_and_export_present(lib):
     hdr = open(os.path.join(ROOT, "include", "mapdn.h")).read()
     assert "mapdn_opf_actions(" in hdr and "typedef struct mapdn_opf_config" in hdr
     assert "mapdn_opf_actions" in _lib.EXPORTS and hasattr(lib, "mapdn_opf_actions")
+    assert "mapdn_opf_probe(" in hdr and "mapdn_opf_probe" in _lib.EXPORTS and hasattr(lib, "mapdn_opf_probe")
     assert os.path.exists(os.path.join(ROOT, "mapdn_amd", "csrc", "opf.hpp")) and os.path.exists(os.path.join(ROOT, "mapdn_amd", "csrc", "opf.hip"))
 
 
@@ -311,6 +314,160 @@ def test_config_refusals_on_host_only_handle(lib):
         assert "null buffer" in lib.mapdn_last_error(h).decode()
     finally:
         lib.mapdn_destroy(h)
+
+
+def probe(lib, h, cfg, a, ns):
+    """mapdn_opf_probe with no output asked for"""
+    return lib.mapdn_opf_probe(h, C.byref(cfg) if cfg is not None else None, a, ns, *([None] * 13))
+
+
+def test_probe_refusals_on_host_only_handle(lib):
+    """mapdn_opf_probe refuses what mapdn_opf_actions refuses, with the same words, then a NULL a and a wrong ns by name, and only then
+    notices that the handle has no device: nothing was launched"""
+    net, _ = make_case("case33")
+    h, keep = host_handle(lib, net)
+    one = C.c_void_p(1)
+    try:
+        for bad in BAD:
+            assert probe(lib, h, _lib.make_opf_config(bad), one, net.n_sgen) == -1, bad
+            assert lib.mapdn_last_error(h).decode().startswith("opf:"), bad
+        for ok in (None, _lib.make_opf_config(dict(v_lower=0.94, v_upper=1.06, max_iter=1000, max_backtrack=60))):
+            assert probe(lib, h, ok, None, net.n_sgen) == -1 and "opf_probe: a is NULL" in lib.mapdn_last_error(h).decode()
+            for ns in (0, -1, net.n_sgen - 1, net.n_sgen + 1, 65):
+                assert probe(lib, h, ok, one, ns) == -1 and "opf_probe: ns" in lib.mapdn_last_error(h).decode(), ns
+            assert probe(lib, h, ok, one, net.n_sgen) == -4                # MAPDN_E_STATE: host-only
+        assert lib.mapdn_opf_probe(None, None, one, net.n_sgen, *([None] * 13)) == -1
+    finally:
+        lib.mapdn_destroy(h)
+
+
+@pytest.mark.parametrize("which,word", [("meshed", "meshed"), ("zip", "ZIP"), ("fused", "fused"), ("sgens", "64 sgens")])
+def test_probe_named_refusals_on_host_only_handle(lib, which, word):
+    net, _ = make_case("case33")
+    if which == "meshed":
+        net = case33_meshed(net, 5)
+    elif which == "zip":
+        net = km.make_net("case33_zip")[0]
+    elif which == "fused":
+        net = add_fused_buses(net, [3, 7])
+    else:
+        net = _many_sgens(make_case("case322")[0])
+    h, keep = host_handle(lib, net)
+    try:
+        rc = probe(lib, h, None, C.c_void_p(1), net.n_sgen)
+        msg = lib.mapdn_last_error(h).decode()
+        assert rc == -1 and msg.startswith("opf:") and word in msg, (which, rc, msg)
+    finally:
+        lib.mapdn_destroy(h)
+
+
+# ---- the nets and the bars of tests/test_opf_kernels_gpu.py ------------------------------------------------------------------------------
+def test_special_net_carries_what_it_claims(lib):
+    """the special net of the kernel matrix: an unsymmetric Ybus (the phase shifter), iron losses, a shunt, sgen scalings, an sgen on the
+    slack bus, and in the handle's elimination order a junction with four children whose chain child k - 1 is not its lowest-numbered
+    one; and on it the restated g, which the GPU test holds the kernel's to, against central differences of the oracle's loss.
+    Observed max error relative to |g|inf at envs 0 / 2 / 16:  h = 1e-2: 1.1e-5 / 2.1e-6 / 2.0e-6,  1e-3: 1.1e-7 / 2.8e-8 / 4.7e-8,
+    1e-4: 3.8e-7 / 1.7e-7 / 1.3e-7: truncation (~0.1 h^2) and round-off cross near h = 1e-3, as in
+    test_gradient_against_central_differences, whose h = 1e-3 and bound 1e-6 serve here too."""
+    from tests import opf_kernel_cases as K
+    net, prof, rows, a, smax = K.state("special")
+    Y = make_ybus(net)[0].toarray()
+    assert np.abs(Y - Y.T).max() > 1e-3 * np.abs(Y).max() and net.br_shift_deg[0] == 3.0 and net.br_g_pu[0] != 0
+    assert net.shunt_bus.shape[0] == 1 and (net.sgen_scaling != 1).all() and net.sgen_bus[-1] == net.ext_grid_bus
+    assert 0 not in (int(net.br_from_bus[0]), int(net.br_to_bus[0]))       # an inner branch
+    h, keep = host_handle(lib, net)
+    try:
+        n = net.n_bus - 1
+        nr, sched, par = C.c_int32(), np.zeros(4 * n + 8, np.int32), np.zeros(n + 1, np.int32)
+        assert lib.mapdn_get_schedule(h, 1, C.byref(nr), _lib._p(sched, _lib._pi), _lib._p(par, _lib._pi)) == 0
+        fac, bop = np.zeros(n * 12), np.zeros(n + 1, np.int32)
+        assert lib.mapdn_get_flat_factors(h, _lib._p(fac, _lib._pd), _lib._p(bop, _lib._pi)) == 0
+    finally:
+        lib.mapdn_destroy(h)
+    kids = [[c for c in range(n) if par[c] == k] for k in range(n)]
+    four = [k for k in range(n) if len(kids[k]) == 4]
+    assert four and all(k - 1 in kids[k] and min(kids[k]) < k - 1 for k in four), kids
+    assert int(bop[four[0]]) == K.special_hub()
+    ybus = make_ybus(net)[0]
+    eye = np.eye(net.n_sgen)
+    for e in (0, 2, 16):
+        t = rows[e]
+        lim = R.limits(prof.pv[t], smax)
+        f = lambda x: R.loss_pu(ybus, runpp_restated(net, prof.load_p[t], prof.load_q[t], prof.pv[t], lim * x).V)
+        g = R.linearise(net, runpp_restated(net, prof.load_p[t], prof.load_q[t], prof.pv[t], lim * a[e]).V, lim).g
+        for hh in (1e-2, 1e-3, 1e-4):
+            fd = np.array([(f(a[e] + hh * eye[j]) - f(a[e] - hh * eye[j])) / (2.0 * hh) for j in range(net.n_sgen)])
+            err = float(np.abs(fd - g).max() / np.abs(g).max())
+            print("special env", e, "h", hh, "relative error", err)
+            assert hh != 1e-3 or err <= 1e-6, (e, err)
+        assert g[-1] == 0 and fd[-1] == 0                                 # the slack sgen moves nothing
+
+
+def _kernel_cases():
+    from tests import opf_kernel_cases as K
+    return list(K.BATCHES)
+
+
+@pytest.mark.parametrize("case", _kernel_cases())
+def test_e64_constants_are_what_the_float64_reference_gives(case):
+    """tests/test_opf_kernels_gpu.py holds k_opf_linearise to 16 x E64, E64 the error of opf_ref.linearise against the extended-precision
+    reference.  Recomputed here: every constant within a factor 2 either way (another LAPACK rounds otherwise), so that none is inflated."""
+    from tests import opf_kernel_cases as K
+    now = K.e64(case)
+    print(case, {q: f"{v:.2e}" for q, v in now.items()})
+    for q in K.QUANTITIES:
+        assert 0.5 * K.E64[case][q] <= now[q] <= 2.0 * K.E64[case][q], (case, q, now[q], K.E64[case][q])
+
+
+# the error of the host build of opf.hpp (opf_check mode 4: its elimination and k_opf_linearise's sums in the kernel's order, float64,
+# g++ -O2, no fused multiply-add) against the extended-precision reference at the oracle's V of the reference envs, per case and
+# quantity, as measured when the test was written: what the arithmetic of the kernel is good for on each net, apart from the GPU
+HOST_ERR = dict(
+    tiny=dict(S=1.2e-14, g=2.8e-14, H=1.0e-14, loss=2.2e-13),
+    small15=dict(S=6.6e-15, g=2.2e-13, H=9.7e-15, loss=7.9e-13),
+    small16=dict(S=2.4e-14, g=4.3e-13, H=1.6e-14, loss=1.1e-12),
+    small17=dict(S=1.6e-14, g=1.1e-12, H=1.9e-14, loss=6.7e-13),
+    wide33=dict(S=9.3e-14, g=6.1e-13, H=7.4e-14, loss=4.1e-12),
+    wide48=dict(S=4.9e-14, g=1.6e-13, H=4.2e-14, loss=1.3e-12),
+    wide49=dict(S=3.6e-14, g=5.1e-13, H=3.1e-14, loss=3.7e-12),
+    wide64=dict(S=1.2e-13, g=4.0e-12, H=1.2e-13, loss=4.2e-12),
+    case33=dict(S=2.6e-14, g=4.6e-13, H=2.3e-14, loss=3.6e-12),
+    case141=dict(S=2.6e-13, g=2.7e-12, H=2.2e-13, loss=6.7e-12),
+    special=dict(S=2.0e-14, g=8.4e-13, H=3.8e-14, loss=4.2e-12),
+)
+
+
+@pytest.mark.parametrize("case", _kernel_cases())
+def test_host_build_of_the_linearisation_meets_the_kernel_bars(host_opf, case):
+    """the kernel's arithmetic on the host against the extended-precision reference, under the bar the GPU test sets the kernel"""
+    from tests import opf_kernel_cases as K
+    net, prof, rows, a, smax = K.state(case)
+    ybus = make_ybus(net)[0]
+    Y = ybus.toarray()
+    slack, vroot = int(net.ext_grid_bus), net.ext_grid_vm_pu
+    bus_of_pos, par, cptr, cidx, yt = tree_tables(Y, slack, vroot)
+    n, ns = net.n_bus - 1, net.n_sgen
+    pos = {b: i for i, b in enumerate(bus_of_pos)}
+    sg = [pos.get(int(b), n) for b in net.sgen_bus]                      # (n: an sgen on the slack bus)
+    per_env = []
+    for e in K.ref_envs(len(rows)):
+        t = rows[e]
+        lim = R.limits(prof.pv[t], smax)
+        res = runpp_restated(net, prof.load_p[t], prof.load_q[t], prof.pv[t], lim * a[e])
+        assert res.converged
+        Vp = res.V[bus_of_pos]
+        w = lim * net.sgen_scaling / net.sn_mva
+        out = host_opf(np.concatenate([[4, n, ns, len(cidx)], par, cptr, cidx, yt.ravel(), Vp.real, Vp.imag, sg, w, np.abs(Vp),
+                                       [Y[slack, slack].real * vroot * vroot]]))
+        S = np.zeros((net.n_bus, ns))
+        S[bus_of_pos] = out[:n * ns].reshape(n, ns)
+        got = dict(S=S, g=out[n * ns:n * ns + ns], H=out[n * ns + ns:-1].reshape(ns, ns), loss=out[-1],
+                   violation=R.violation_of(np.abs(res.V), net, *K.V_BAND))
+        per_env.append(K.errors(net, res.V, lim, got))
+    worst = K.worst(per_env)
+    print(f"    {case}=dict(" + ", ".join(f"{q}={v:.1e}" for q, v in worst.items() if q != "violation") + "),")
+    for q in ("S", "g", "H", "loss"):
+        assert worst[q] <= K.bar(case, q), (case, q, worst[q], K.bar(case, q))
 
 
 def _many_sgens(net, ns=65):

@@ -207,7 +207,8 @@ def test_stopped_envs_get_status_3():
 
 
 def test_widest_feeder_runs():
-    """case322: 38 sgens, three columns per sub-lane"""
+    """case322: 38 sgens, three columns per sub-lane.  Finiteness and statuses only: widths like this one and beyond (33, 48, 49 and 64
+    sgens) are held against an extended-precision reference, S, g and H entry by entry, in tests/test_opf_kernels_gpu.py."""
     net, prof = km.make_net("case322")
     env = VoltageControlBatch(net, prof, dict(ARGS), n_envs=16, device=DEV, obs_dtype=torch.float64)
     try:
