@@ -278,6 +278,47 @@ int mapdn_get_results(mapdn_handle* h, double* vm_pu, double* va_degree, double*
 /* current load table values f64 [B, nl] (net.load.p_mw / q_mvar) */
 int mapdn_get_loads(mapdn_handle* h, double* load_p, double* load_q, void* stream);
 
+/* ---- res_line / res_trafo: the branch tables the reference reads from pandapower after every runpp — res_line.loading_percent,
+ * i_from_ka, i_to_ka (environments/var_voltage_control/pf_res_plot.py:142-150) and res_trafo.loading_percent, i_hv_ka, i_lv_ka
+ * (pf_res_plot.py:161-163) — restated from pandapower 2.7.0 results_branch.py (_get_line_results, _get_trafo_results with
+ * trafo_loading="current") [PP-recalled].  With Sf = Vf conj(yff Vf + yft Vt), St = Vt conj(ytf Vf + ytt Vt) in per unit (the pi constants of
+ * makeYbus): p_from_mw + j q_from_mvar = Sf sn_mva, p_to_mw + j q_to_mvar = St sn_mva; pl_mw / ql_mvar = Re / Im (Sf + St) sn_mva in the
+ * four-term form of the res_line.pl_mw that mapdn_get_results reports; i_from_ka = |Sf| sn_mva / (sqrt(3) |Vf| bus_vn_kv[from]), i_to_ka
+ * likewise, i_ka their maximum (|S| == 0 gives 0); loading_percent = 100 i_ka / (max_i_ka df parallel) of a line and
+ * 100 sqrt(3) max(i_hv_ka vn_hv_kv, i_lv_ka vn_lv_kv) / br_rating_mva of a per-unit pi branch (a transformer: from = hv, to = lv).
+ * An out-of-service line reports 0 in every column; a branch without a rating reports loading_percent = NaN.
+ *
+ * Ratings: HOST arrays, any of them NULL, copied and uploaded once (synchronous; on a host-only handle only validated).
+ * line_max_i_ka, line_df [n_line] = net.line.max_i_ka, net.line.df (NULL df: 1; net.line.parallel is the netspec's); br_vn_hv_kv,
+ * br_vn_lv_kv [n_branch_pu] = the transformer's nameplate voltages; br_rating_mva [n_branch_pu] = its sn_mva x parallel x df.  A NULL
+ * line_max_i_ka leaves every line unrated, a NULL among the three br_ columns every pi branch; a NaN in line_max_i_ka / br_rating_mva
+ * leaves that row unrated (pandapower's missing value).  Any other entry that is not finite and > 0 is MAPDN_E_INVALID, named by
+ * column and row.  A call replaces the ratings of the call before. */
+int mapdn_set_branch_ratings(mapdn_handle* h, const double* line_max_i_ka, const double* line_df,
+                             const double* br_vn_hv_kv, const double* br_vn_lv_kv, const double* br_rating_mva);
+
+typedef struct mapdn_branch_out {            /* device f64, any pointer NULL */
+  double *p_from_mw, *q_from_mvar, *p_to_mw, *q_to_mvar, *pl_mw, *ql_mvar,
+         *i_from_ka, *i_to_ka, *i_ka, *loading_percent;
+} mapdn_branch_out;
+
+/* The two tables for every env in one launch (k_branch_results), only the columns whose pointer is not NULL; `line` / `trafo` may be NULL.
+ * vm_pu, va_degree: device f64 [B, n_bus] by bus — what mapdn_get_results and mapdn_solve_only write — and the tables are computed at
+ * those voltages: env state is neither read nor touched (fused buses: the caller's own rows of the two ends are read).  Both NULL: the
+ * env's current vm / va (MAPDN_E_STATE before mapdn_reset); exactly one NULL: MAPDN_E_INVALID.  Enqueues only. */
+int mapdn_get_branch_results(mapdn_handle* h, const double* vm_pu, const double* va_degree,
+                             const mapdn_branch_out* line,   /* [B, n_line]      */
+                             const mapdn_branch_out* trafo,  /* [B, n_branch_pu], from = hv, to = lv */
+                             void* stream);
+
+/* Per env, over the rated in-service branches at the env's current state, lines numbered 0 .. n_line - 1 and pi branches from n_line:
+ * max_loading f64 [B] = the largest loading_percent, worst_branch i32 [B] = the lowest index that attains it (-1, with max_loading = NaN
+ * and n_overloaded = 0, when nothing is rated), n_overloaded i32 [B] = the count of loading_percent > limit_percent.  One launch
+ * (k_loading_summary) from the voltages; the bits do not depend on the batch size.  Device pointers; MAPDN_E_STATE before mapdn_reset. */
+int mapdn_get_loading_summary(mapdn_handle* h, double limit_percent,
+                              double* max_loading /*[B]*/, int32_t* worst_branch /*[B]*/,
+                              int32_t* n_overloaded /*[B]*/, void* stream);
+
 /* `start` of voltage_control_env.py:445 for every env: device int64 [B] */
 int mapdn_get_start_rows(mapdn_handle* h, int64_t* start_rows, void* stream);
 

@@ -42,6 +42,7 @@ EXPORTS = (
     "mapdn_attention_forward", "mapdn_attention_backward", "mapdn_attention_scratch_floats", "mapdn_attention_max_agents",
     "mapdn_critic_shapley_forward", "mapdn_critic_shapley_backward", "mapdn_critic_shapley_scratch_floats", "mapdn_critic_shapley_geometry",
     "mapdn_ppo_gae", "mapdn_ppo_loss_blocks", "mapdn_ppo_policy_loss", "mapdn_ppo_value_loss",
+    "mapdn_set_branch_ratings", "mapdn_get_branch_results", "mapdn_get_loading_summary",
 )
 
 _pd = C.POINTER(C.c_double)
@@ -149,6 +150,14 @@ class CDims(C.Structure):
     _fields_ = [(k, C.c_int32) for k in (
         "n_envs", "n_bus", "n_line", "n_load", "n_sgen", "n_agents", "n_actions", "obs_size", "state_size",
         "n_info", "is_radial", "max_zone_size")]
+
+
+BRANCH_COLUMNS = ("p_from_mw", "q_from_mvar", "p_to_mw", "q_to_mvar", "pl_mw", "ql_mvar", "i_from_ka", "i_to_ka", "i_ka", "loading_percent")
+
+
+class CBranchOut(C.Structure):
+    """mapdn_branch_out: device pointers of the requested columns of res_line / res_trafo, NULL for the others"""
+    _fields_ = [(k, C.c_void_p) for k in BRANCH_COLUMNS]
 
 
 class MapdnError(RuntimeError):
@@ -286,6 +295,9 @@ def load():
     lib.mapdn_droop_actions.argtypes = [vp, C.POINTER(CDroopConfig), vp, vp, vp, vp, vp]
     lib.mapdn_opf_actions.argtypes = [vp, C.POINTER(COPFConfig), vp, vp, vp, vp, vp, vp, vp]
     lib.mapdn_opf_probe.argtypes = [vp, C.POINTER(COPFConfig), vp, C.c_int32] + [vp] * 13
+    lib.mapdn_set_branch_ratings.argtypes = [vp, _pd, _pd, _pd, _pd, _pd]
+    lib.mapdn_get_branch_results.argtypes = [vp, vp, vp, C.POINTER(CBranchOut), C.POINTER(CBranchOut), vp]
+    lib.mapdn_get_loading_summary.argtypes = [vp, C.c_double, vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("mapdn_last_error", "mapdn_destroy", "mapdn_build_info"):
             getattr(lib, name).restype = C.c_int

@@ -18,7 +18,7 @@ from dataclasses import asdict, dataclass
 import torch
 
 from ._lib import INFO_KEYS
-from .tester import RECORD_KEYS, PGTester
+from .tester import RECORD_KEYS, PGTester, loading_stats
 
 
 @dataclass
@@ -98,17 +98,18 @@ class BaselineTester:
     policy: `run(day, hour, quarter)` records one env's trajectory from a noise-free start, `batch_run(num_episodes)` returns
     {'mean_test_<info key>': (mean, 2 std)} over all steps of all episodes — the same steps, resets and noise as PGTester."""
 
-    def __init__(self, args, controller, env):
+    def __init__(self, args, controller, env, record_loading: bool = False, loading_limit_percent: float = 100.0):
         self.args, self.controller, self.env = args, controller, env
+        self.record_loading, self.loading_limit_percent = bool(record_loading), float(loading_limit_percent)   # as PGTester's
 
-    _snapshot = PGTester._snapshot
+    _snapshot, _new_record, _loading_sample = PGTester._snapshot, PGTester._new_record, PGTester._loading_sample
     save_record = staticmethod(PGTester.save_record)
     print_info = staticmethod(PGTester.print_info)
 
     def run(self, day, hour, quarter, env_index: int = 0):
         env = self.env
         env.manual_reset(day, hour, quarter)
-        record = {k: [] for k in RECORD_KEYS}
+        record = self._new_record()
         self._snapshot(record, env_index)
         for t in range(self.args.max_steps):
             _, done, _ = env.step(self.controller.actions(env), add_noise=False)
@@ -120,7 +121,7 @@ class BaselineTester:
     def batch_run(self, num_episodes: int = 100):
         env = self.env
         rounds = max(1, -(-int(num_episodes) // env.n_envs))
-        samples = []
+        samples, loading = [], []
         for _ in range(rounds):
             env.reset()
             alive = torch.ones(env.n_envs, dtype=torch.bool, device=env.device)
@@ -128,8 +129,14 @@ class BaselineTester:
             for t in range(self.args.max_steps):
                 _, done, info = env.step(self.controller.actions(env), add_noise=False)
                 infos.append(info.clone()); masks.append(alive.clone())
+                if self.record_loading:
+                    mx, over = self._loading_sample()
+                    loading.append((mx[alive], over[alive]))
                 alive = alive & ~done.bool()
             samples.append(torch.stack(infos)[torch.stack(masks)])
         allv = torch.cat(samples).double()
         mean, std = allv.mean(0).tolist(), allv.std(0, unbiased=False).tolist()
-        return {"mean_test_" + k: (m, 2.0 * s) for k, m, s in zip(INFO_KEYS, mean, std)}
+        stat = {"mean_test_" + k: (m, 2.0 * s) for k, m, s in zip(INFO_KEYS, mean, std)}
+        if self.record_loading:
+            stat.update(loading_stats(loading))
+        return stat

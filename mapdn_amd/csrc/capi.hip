@@ -12,6 +12,7 @@
 
 #include "kernels.hpp"
 #include "ppo.hip"            // MAPPO / IPPO: the strided GAE and the clipped losses (k_ppo_*), compiled inside this unit; entry points below
+#include "branch.hip"         // res_line / res_trafo: k_branch_results, k_loading_summary, compiled inside this unit like ppo.hip; entry points below
 #include "nr_inst_list.hpp"
 #include "colstats.hpp"
 #include "opf.hpp"
@@ -98,6 +99,10 @@ struct mapdn_handle {
   // OPF baseline (mapdn_opf_actions): likewise
   OpfState opf{};
   bool opf_ready = false;
+  // res_line / res_trafo (mapdn_get_branch_results, mapdn_get_loading_summary): the plan's branch records with the ratings of
+  // mapdn_set_branch_ratings folded in, and their device copy
+  std::vector<BranchRec> branches;
+  BranchRec* branches_dev = nullptr;
   double* opf_probe_a = nullptr;                 // mapdn_opf_probe: its set-points env-minor [ns][Bp], and the rows of its exports
   const int32_t* opf_probe_rows = nullptr;       // identity rows | the Re V, the Im V, the |V| row of every node
 };
@@ -623,6 +628,7 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
   std::memset(&h->d, 0, sizeof(h->d));
   h->d.B = B; h->d.Bp = (B + 63) / 64 * 64;
   if ((rc = settle_general_solver(h))) return rc;
+  h->branches = h->plan.branches;
   if (device == -1) {                                            // plan only (CPU tests): no device work
     h->host_only = true;
     return h->solver == 0 ? settle_tree_geometry(h, h->d.Bp, 256) : MAPDN_OK;   // (an MI355X has 256 CUs)
@@ -632,6 +638,7 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
   if (device < 0 || device >= ndev) { h->err = "device index out of range"; return MAPDN_E_HIP; }
   HIPCHK(h, hipSetDevice(device));
   if ((rc = upload_topology(h)) || (rc = setup_pv_buses(h)) || (rc = setup_env_state(h)) || (rc = setup_gather_tables(h))) return rc;
+  if ((rc = dupload(h, &h->branches_dev, h->branches))) return rc;
   return h->solver == 2 ? setup_dense(h) : h->solver == 1 ? setup_sparse(h) : setup_tree(h);
 }
 
@@ -879,6 +886,86 @@ int mapdn_get_loads(mapdn_handle* h, double* load_p, double* load_q, void* strea
   hipStream_t st = (hipStream_t)stream;
   if (load_p) transpose_out(h, h->d.cur_pl, 1.0, h->iota_idx, load_p, h->d.nl, st);
   if (load_q) transpose_out(h, h->d.cur_ql, 1.0, h->iota_idx, load_q, h->d.nl, st);
+  HIPCHK(h, hipGetLastError());
+  return MAPDN_OK;
+} MAPDN_CATCH(h)
+
+// ---- res_line / res_trafo ------------------------------------------------------------------------------------------------------------
+int mapdn_set_branch_ratings(mapdn_handle* h, const double* line_max_i_ka, const double* line_df, const double* br_vn_hv_kv,
+                             const double* br_vn_lv_kv, const double* br_rating_mva) try {
+  if (!h) return MAPDN_E_INVALID;
+  const int n_line = h->plan.n_line, n_tr = (int)h->plan.branches.size() - n_line;
+  // NaN in a RATING column (max_i_ka, rating_mva) leaves that row unrated, as a missing value does in pandapower; anything else that is
+  // not a finite positive number is refused, by column and row
+  auto check = [&](const double* v, int n, const char* what, bool nan_ok) {
+    for (int i = 0; v && i < n; ++i) {
+      if (nan_ok && v[i] != v[i]) continue;
+      if (!(v[i] > 0.0) || !std::isfinite(v[i])) {
+        h->err = std::string("set_branch_ratings: ") + what + "[" + std::to_string(i) + "] = " + std::to_string(v[i]) + " must be finite and > 0";
+        return false;
+      }
+    }
+    return true;
+  };
+  if (!check(line_max_i_ka, n_line, "line_max_i_ka", true) || !check(line_df, n_line, "line_df", false) ||
+      !check(br_vn_hv_kv, n_tr, "br_vn_hv_kv", false) || !check(br_vn_lv_kv, n_tr, "br_vn_lv_kv", false) ||
+      !check(br_rating_mva, n_tr, "br_rating_mva", true))
+    return MAPDN_E_INVALID;
+  std::vector<BranchRec> br(h->plan.branches);                   // (unrated: rate = NaN)
+  for (int l = 0; line_max_i_ka && l < n_line; ++l)
+    br[l].rate = line_max_i_ka[l] * (line_df ? line_df[l] : 1.0) * br[l].parallel;
+  for (int k = 0; br_rating_mva && br_vn_hv_kv && br_vn_lv_kv && k < n_tr; ++k) {
+    BranchRec& r = br[n_line + k];
+    r.rate = br_rating_mva[k]; r.tv_f = br_vn_hv_kv[k]; r.tv_t = br_vn_lv_kv[k];
+  }
+  if (!h->host_only) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!br.empty()) HIPCHK(h, hipMemcpy(h->branches_dev, br.data(), br.size() * sizeof(BranchRec), hipMemcpyHostToDevice));
+  }
+  h->branches.swap(br);
+  return MAPDN_OK;
+} MAPDN_CATCH(h)
+
+int mapdn_get_branch_results(mapdn_handle* h, const double* vm_pu, const double* va_degree, const mapdn_branch_out* line,
+                             const mapdn_branch_out* trafo, void* stream) try {
+  if (!h) return MAPDN_E_INVALID;
+  if ((vm_pu == nullptr) != (va_degree == nullptr)) { h->err = "get_branch_results: vm_pu and va_degree go together (both, or both NULL for the env's state)"; return MAPDN_E_INVALID; }
+  if (!vm_pu && !h->was_reset) { h->err = "get_branch_results before reset"; return MAPDN_E_STATE; }
+  NEEDDEV(h);
+  HIPCHK(h, hipSetDevice(h->device));
+  const Dev& d = h->d;
+  BranchArgs a{};
+  a.rec = h->branches_dev; a.n_line = d.n_line; a.n_trafo = (int32_t)h->branches.size() - d.n_line; a.B = d.B; a.sn = d.sn;
+  if (vm_pu) { a.vm = vm_pu; a.va = va_degree; a.sb = 1; a.se = d.nbo; a.ang = M_PI / 180.0; }
+  else { a.vm = d.vm; a.va = d.va; a.sb = d.Bp; a.se = 1; a.ang = 1.0; }
+  const mapdn_branch_out* tab[2] = {line, trafo};
+  bool any[2] = {false, false};
+  for (int t = 0; t < 2; ++t) {
+    if (!tab[t]) continue;
+    double* const cols[BC_N] = {tab[t]->p_from_mw, tab[t]->q_from_mvar, tab[t]->p_to_mw, tab[t]->q_to_mvar, tab[t]->pl_mw, tab[t]->ql_mvar,
+                                tab[t]->i_from_ka, tab[t]->i_to_ka, tab[t]->i_ka, tab[t]->loading_percent};
+    for (int c = 0; c < BC_N; ++c) { a.out[t][c] = cols[c]; any[t] = any[t] || cols[c]; }
+  }
+  a.line_tiles = any[0] ? (a.n_line + BR_TILE - 1) / BR_TILE : 0;
+  a.trafo_tiles = any[1] ? (a.n_trafo + BR_TILE - 1) / BR_TILE : 0;
+  launch_branch_results(a, d.Bp, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return MAPDN_OK;
+} MAPDN_CATCH(h)
+
+int mapdn_get_loading_summary(mapdn_handle* h, double limit_percent, double* max_loading, int32_t* worst_branch, int32_t* n_overloaded,
+                              void* stream) try {
+  if (!h) return MAPDN_E_INVALID;
+  if (!h->was_reset) { h->err = "get_loading_summary before reset"; return MAPDN_E_STATE; }
+  if (!max_loading || !worst_branch || !n_overloaded) { h->err = "get_loading_summary: null buffer"; return MAPDN_E_INVALID; }
+  if (limit_percent != limit_percent) { h->err = "get_loading_summary: limit_percent is NaN"; return MAPDN_E_INVALID; }
+  NEEDDEV(h);
+  HIPCHK(h, hipSetDevice(h->device));
+  const Dev& d = h->d;
+  LoadingArgs a{};
+  a.rec = h->branches_dev; a.n_branch = (int32_t)h->branches.size(); a.B = d.B; a.Bp = d.Bp; a.vm = d.vm; a.va = d.va; a.sn = d.sn;
+  a.limit = limit_percent; a.max_loading = max_loading; a.worst = worst_branch; a.n_over = n_overloaded;
+  launch_loading_summary(a, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return MAPDN_OK;
 } MAPDN_CATCH(h)

@@ -200,4 +200,25 @@ void launch_opf_update(const Dev& d, const OpfState& s, int iter, hipStream_t st
 void launch_opf_linearise(const Dev& d, const OpfState& s, hipStream_t st);
 void launch_opf_qp(const Dev& d, const OpfState& s, hipStream_t st);
 
+// ---- res_line / res_trafo (branch.hip, branch.hpp; mapdn_get_branch_results, mapdn_get_loading_summary).  Their own small argument
+// blocks: Dev stays what every other launch takes.
+enum { BR_TILE = 16, LS_WAVES = 8 };
+struct BranchArgs {
+  const BranchRec* rec;              // [n_line + n_trafo]: net.line rows, then the per-unit pi branches
+  int32_t n_line, n_trafo, B;
+  int32_t line_tiles, trafo_tiles;   // tiles of BR_TILE branches of each table (0: no column of the table is asked for)
+  const double *vm, *va;             // |V| and angle of original bus b, env e at [b * sb + e * se]: env state (sb = Bp, se = 1, rad) or the
+  int64_t sb, se;                    // caller's [B, n_bus] arrays (sb = 1, se = n_bus, degrees)
+  double ang, sn;                    // angle unit -> rad (1 or pi / 180), sn_mva
+  double* out[2][BC_N];              // columns of mapdn_branch_out (BC_*) of the line and the trafo table, [B, n] each or nullptr
+};
+struct LoadingArgs {
+  const BranchRec* rec; int32_t n_branch, B, Bp;
+  const double *vm, *va;             // env state [n_bus][Bp], va in rad
+  double sn, limit;
+  double* max_loading; int32_t* worst; int32_t* n_over;   // [B]
+};
+void launch_branch_results(const BranchArgs& a, int Bp, hipStream_t st);
+void launch_loading_summary(const LoadingArgs& a, hipStream_t st);
+
 }  // namespace mapdn

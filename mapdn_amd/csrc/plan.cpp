@@ -387,6 +387,21 @@ static int build_plan_nodes(const mapdn_netspec& net, const mapdn_netspec& net_o
     L.c[0] = b.yff.real(); L.c[1] = b.ytt.real(); L.c[2] = b.yft.real() + b.ytf.real(); L.c[3] = b.yft.imag() - b.ytf.imag();
   }
 
+  // ---- res_line / res_trafo constants (branch.hpp): every pi branch by the caller's own bus ids, ratings set later -------------
+  P.branches.assign((size_t)net.n_line + net.n_branch_pu, BranchRec{});
+  auto put_branch = [&](BranchRec& r, const PiBranch& b, int fo, int to, bool live, bool trafo) {
+    r.f = fo; r.t = to; r.live = live ? 1 : 0; r.trafo = trafo ? 1 : 0;
+    const cplx y[4] = {b.yff, b.yft, b.ytf, b.ytt};
+    for (int i = 0; i < 4; ++i) { r.y[2 * i] = live ? y[i].real() : 0.0; r.y[2 * i + 1] = live ? y[i].imag() : 0.0; }
+    r.vn_f = net_o.bus_vn_kv[fo]; r.vn_t = net_o.bus_vn_kv[to];
+    r.rate = NAN; r.tv_f = r.tv_t = 1.0; r.parallel = 1.0;
+  };
+  for (int l = 0; l < net.n_line; ++l)
+    put_branch(P.branches[l], line_pi[l], net_o.line_from_bus[l], net_o.line_to_bus[l], net.line_in_service[l] != 0, false);
+  for (int l = 0; l < net.n_line; ++l) P.branches[l].parallel = (double)net.line_parallel[l];
+  for (int k = 0; k < net.n_branch_pu; ++k)
+    put_branch(P.branches[net.n_line + k], pi_from_pu(net, k), net_o.br_from_bus[k], net_o.br_to_bus[k], true, true);
+
   // ---- element CSR by position ------------------------------------------------------------------
   auto csr = [&](int n_el, const int32_t* el_bus, std::vector<int32_t>& ptr, std::vector<int32_t>& idx) {
     ptr.assign(nb + 1, 0); idx.assign(n_el, 0);

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/mapdn.h"
+#include "branch.hpp"
 
 namespace mapdn {
 
@@ -151,6 +152,7 @@ struct Plan {
   std::vector<double> gy_dc;                    // aligned with gy_col: Bbus entries (the general sparse solver assembles them)
 
   std::vector<LineFlow> lines;                  // [n_line]
+  std::vector<BranchRec> branches;              // [n_line + n_branch_pu] res_line / res_trafo constants by ORIGINAL bus id, unrated (branch.hpp)
   // element -> bus CSR by position (0..nb-1, root last)
   std::vector<int32_t> load_ptr, load_idx, sgen_ptr, sgen_idx;
   std::vector<double> shunt_p, shunt_q;         // [nb] by position, MW/MVAr at 1 p.u.

@@ -76,6 +76,13 @@ def _col(df, name, default):
     return np.where(np.isnan(v), float(default), v)
 
 
+def _rating(v):
+    """a thermal rating column: NaN (= unrated, loading_percent NaN) wherever the table holds no finite positive number"""
+    v = np.asarray(v, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isfinite(v) & (v > 0.0), v, np.nan)
+
+
 def trafo_to_pi(trafo, bus_vn_kv: np.ndarray, net_sn_mva: float, calculate_voltage_angles: bool = False):
     """pandapower 2.7.0 build_branch._calc_branch_values_from_trafo_df with runpp's defaults (trafo_model="t",
     no tap-dependent impedance), restated [PP-recalled; SURVEY.md Appendix A.2]: two-winding transformers ->
@@ -91,6 +98,7 @@ def trafo_to_pi(trafo, bus_vn_kv: np.ndarray, net_sn_mva: float, calculate_volta
       _wye_delta (T -> pi)          za = (r + jx) / 2; zc = -1j / y; zs = za^2 + 2 za zc; (r + jx) = zs / zc; y = -2j / (zs / za)
     The ppc branch then has BR_B = y (= b - 1j*g), TAP = ratio, SHIFT = shift_degree when voltage angles are calculated
     (runpp calculate_voltage_angles="auto": only if a line touches a bus above 70 kV), else 0.
+    Also returned: the ratings of res_trafo.loading_percent (NetSpec.br_vn_hv_kv, br_vn_lv_kv, br_rating_mva).
     Out-of-service transformers are dropped.  Phase-shifting / cross regulators (tap_step_degree != 0, tap_phase_shifter)
     and tap-dependent impedance are refused."""
     t = trafo.sort_index()
@@ -100,7 +108,7 @@ def trafo_to_pi(trafo, bus_vn_kv: np.ndarray, net_sn_mva: float, calculate_volta
     if n == 0:
         z = np.zeros(0)
         return dict(br_from_bus=np.zeros(0, np.int32), br_to_bus=np.zeros(0, np.int32), br_r_pu=z, br_x_pu=z, br_b_pu=z,
-                    br_g_pu=z, br_ratio=z, br_shift_deg=z)
+                    br_g_pu=z, br_ratio=z, br_shift_deg=z, br_vn_hv_kv=z, br_vn_lv_kv=z, br_rating_mva=z)
     if "tap_phase_shifter" in t and t["tap_phase_shifter"].fillna(False).to_numpy(bool).any():
         raise NotImplementedError("transformers with tap_phase_shifter=True are not converted")
     if np.any(_col(t, "tap_step_degree", 0.0) != 0.0):
@@ -138,8 +146,11 @@ def trafo_to_pi(trafo, bus_vn_kv: np.ndarray, net_sn_mva: float, calculate_volta
     zab = zs / zc
     r, x, y = r.copy(), x.copy(), y.copy()
     r[nz], x[nz], y[nz] = zab.real, zab.imag, -2j / (zs / za)
+    # res_trafo.loading_percent (results_branch._get_trafo_results, trafo_loading="current") reads the nameplate voltages and
+    # sn_mva x parallel x df [PP-recalled]
     return dict(br_from_bus=hv.astype(np.int32), br_to_bus=lv.astype(np.int32), br_r_pu=r, br_x_pu=x, br_b_pu=y.real,
-                br_g_pu=-y.imag, br_ratio=ratio, br_shift_deg=shift)
+                br_g_pu=-y.imag, br_ratio=ratio, br_shift_deg=shift, br_vn_hv_kv=t["vn_hv_kv"].to_numpy(np.float64).copy(),
+                br_vn_lv_kv=vn_lv_kv, br_rating_mva=_rating(sn_t * parallel * _col(t, "df", 1.0)))
 
 
 def from_pandapower(net, hv_init: str = "refuse", zip_loads: str = "refuse") -> NetSpec:
@@ -274,6 +285,8 @@ def from_pandapower(net, hv_init: str = "refuse", zip_loads: str = "refuse") -> 
         load_scaling=_col(load, "scaling", 1.0) * on(load), sgen_scaling=_col(sgen, "scaling", 1.0) * on(sgen),
         ext_grid_bus=int(rb([net.ext_grid["bus"].iloc[0]])[0]), ext_grid_vm_pu=float(net.ext_grid["vm_pu"].iloc[0]),
         sn_mva=float(net.sn_mva), f_hz=float(net.f_hz))
+    if "max_i_ka" in line:                                       # res_line.loading_percent; a missing max_i_ka stays NaN (unrated)
+        kw.update(line_max_i_ka=_rating(line["max_i_ka"].to_numpy(dtype=np.float64, na_value=np.nan)), line_df=_col(line, "df", 1.0))
     if fused_alias is not None:
         kw["bus_alias"] = fused_alias
     if zip_cols:

@@ -109,6 +109,10 @@ class VoltageControlBatch:
         self.obs_size = self._obs_size1 * self.history          # :303-315 stacks `history` frames
         self.max_zone_size = dims.max_zone_size
         self.is_radial = bool(dims.is_radial)                   # False: meshed net, general-topology solver (k_nr_dense)
+        self.n_trafo = net.n_branch_pu                          # rows of res_trafo: the per-unit pi branches
+        rat = [getattr(net, k) for k in ("line_max_i_ka", "line_df", "br_vn_hv_kv", "br_vn_lv_kv", "br_rating_mva")]
+        if any(r.size for r in rat):                            # thermal ratings of res_line / res_trafo (none: loading_percent is NaN)
+            _lib.check(self._lib.mapdn_set_branch_ratings(self._h, *[_lib._p(r, _lib._pd) for r in rat]), self._h)
         p = profiles
         _lib.check(self._lib.mapdn_set_profiles(
             self._h, _lib._p(p.pv, _lib._pd), _lib._p(p.load_p, _lib._pd), _lib._p(p.load_q, _lib._pd),
@@ -321,6 +325,85 @@ class VoltageControlBatch:
         if b is None:
             b = self._obs[("res", k)] = torch.empty(self.n_envs, w, dtype=torch.float64, device=self.device)
         return b
+
+    # pandapower's column names of res_trafo for the columns of mapdn_branch_out (from = hv, to = lv)
+    _TRAFO_KEYS = ("p_hv_mw", "q_hv_mvar", "p_lv_mw", "q_lv_mvar", "pl_mw", "ql_mvar", "i_hv_ka", "i_lv_ka", None, "loading_percent")
+    _LINE_BUS_KEYS = ("vm_from_pu", "va_from_degree", "vm_to_pu", "va_to_degree")
+
+    def _branch_tables(self, line_keys, trafo_keys, vm_pu, va_degree):
+        """mapdn_get_branch_results: {column of mapdn_branch_out: tensor} of either table for the requested struct columns"""
+        B, dv, f64 = self.n_envs, self.device, torch.float64
+        if (vm_pu is None) != (va_degree is None):
+            raise ValueError("vm_pu and va_degree go together: both (e.g. from solve()), or neither for the env's current state")
+        volt = [None, None]
+        if vm_pu is not None:
+            volt = [torch.as_tensor(x, dtype=f64, device=dv).contiguous() for x in (vm_pu, va_degree)]
+            if volt[0].shape != (B, self.n_bus) or volt[1].shape != (B, self.n_bus):
+                raise ValueError(f"vm_pu / va_degree must be [{B}, {self.n_bus}]")
+        outs, structs = [], []
+        for keys, n in ((line_keys, self.n_line), (trafo_keys, self.n_trafo)):
+            o = {k: torch.empty(B, n, dtype=f64, device=dv) for k in keys}
+            s = _lib.CBranchOut()
+            for k, t in o.items():
+                setattr(s, k, t.data_ptr())
+            outs.append(o)
+            structs.append(s)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mapdn_get_branch_results(self._h, *[None if v is None else v.data_ptr() for v in volt],
+                                                          _lib.C.byref(structs[0]), _lib.C.byref(structs[1]), self._stream()), self._h)
+        return outs
+
+    def res_line(self, keys=None, vm_pu=None, va_degree=None):
+        """pandapower's res_line for the whole batch (pf_res_plot.py:142-150 reads loading_percent, i_from_ka, i_to_ka): a dict of
+        float64 [B, n_line] tensors under its column names — p_from_mw q_from_mvar p_to_mw q_to_mvar pl_mw ql_mvar i_from_ka i_to_ka i_ka
+        loading_percent (mapdn_get_branch_results, include/mapdn.h; only the requested ones are computed) and vm_from_pu va_from_degree
+        vm_to_pu va_to_degree (gathered from the bus voltages).  `keys`: a subset (default all).  vm_pu / va_degree [B, n_bus]: compute
+        the table at these voltages (e.g. what solve() returned) instead of the env's current state, which is then not read.
+        loading_percent is NaN for a line without max_i_ka (NetSpec.line_max_i_ka); an out-of-service line reports 0."""
+        keys = _lib.BRANCH_COLUMNS + self._LINE_BUS_KEYS if keys is None else tuple(keys)
+        unknown = set(keys) - set(_lib.BRANCH_COLUMNS) - set(self._LINE_BUS_KEYS)
+        if unknown:
+            raise KeyError(f"res_line has no column {sorted(unknown)}")
+        out = self._branch_tables([k for k in keys if k in _lib.BRANCH_COLUMNS], (), vm_pu, va_degree)[0]
+        if any(k in self._LINE_BUS_KEYS for k in keys):
+            if vm_pu is None:
+                r = self.results(("vm_pu", "va_degree"))
+                vm, va = r["vm_pu"], r["va_degree"]
+            else:
+                vm, va = (torch.as_tensor(x, dtype=torch.float64, device=self.device) for x in (vm_pu, va_degree))
+            f = torch.as_tensor(self.net.line_from_bus.astype(np.int64), device=self.device)
+            t = torch.as_tensor(self.net.line_to_bus.astype(np.int64), device=self.device)
+            bus = dict(vm_from_pu=(vm, f), va_from_degree=(va, f), vm_to_pu=(vm, t), va_to_degree=(va, t))
+            for k in keys:
+                if k in bus:
+                    out[k] = bus[k][0][:, bus[k][1]]
+        return {k: out[k] for k in keys}
+
+    def res_trafo(self, keys=None, vm_pu=None, va_degree=None):
+        """pandapower's res_trafo for the per-unit pi branches of the net (the transformers from_pandapower converted; pf_res_plot.py:161-163
+        reads loading_percent, i_hv_ka, i_lv_ka): a dict of float64 [B, n_branch_pu] tensors — p_hv_mw q_hv_mvar p_lv_mw q_lv_mvar pl_mw
+        ql_mvar i_hv_ka i_lv_ka loading_percent (br_from_bus is the hv side; trafo_loading="current").  Arguments as res_line."""
+        names = {k: c for k, c in zip(self._TRAFO_KEYS, _lib.BRANCH_COLUMNS) if k}
+        keys = tuple(names) if keys is None else tuple(keys)
+        unknown = set(keys) - set(names)
+        if unknown:
+            raise KeyError(f"res_trafo has no column {sorted(unknown)}")
+        out = self._branch_tables((), [names[k] for k in keys], vm_pu, va_degree)[1]
+        return {k: out[names[k]] for k in keys}
+
+    def loading_summary(self, limit_percent=100.0):
+        """(max_loading float64 [B], worst_branch int32 [B], n_overloaded int32 [B]) over the rated in-service branches at the env's
+        current state (mapdn_get_loading_summary): lines are numbered 0 .. n_line - 1, pi branches from n_line; worst_branch is the
+        lowest index that attains the maximum, -1 (max_loading NaN, n_overloaded 0) when nothing is rated; n_overloaded counts
+        loading_percent > limit_percent."""
+        B, dv = self.n_envs, self.device
+        mx = torch.empty(B, dtype=torch.float64, device=dv)
+        wb = torch.empty(B, dtype=torch.int32, device=dv)
+        no = torch.empty(B, dtype=torch.int32, device=dv)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mapdn_get_loading_summary(self._h, float(limit_percent), mx.data_ptr(), wb.data_ptr(), no.data_ptr(),
+                                                           self._stream()), self._h)
+        return mx, wb, no
 
     def loads(self):
         lp = torch.empty(self.n_envs, self.n_load, dtype=torch.float64, device=self.device)
@@ -675,6 +758,14 @@ class VoltageControl(MultiAgentEnv):
 
     def _get_res_line_loss(self):
         return self._res("pl_mw")
+
+    def _get_res_line_loading(self):
+        """res_line.loading_percent [n_line] (pf_res_plot.py:142-150); NaN for lines without a rating"""
+        return self._b.res_line(("loading_percent",))["loading_percent"][0].cpu().numpy()
+
+    def _get_res_trafo_loading(self):
+        """res_trafo.loading_percent [n_branch_pu] (pf_res_plot.py:161-163)"""
+        return self._b.res_trafo(("loading_percent",))["loading_percent"][0].cpu().numpy()
 
     def _get_sgen_active(self):
         return self._res("sgen_p")

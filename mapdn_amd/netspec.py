@@ -81,6 +81,15 @@ class NetSpec:
     # power, what every net without these columns is); data.from_pandapower(zip_loads="runpp") fills them.  DESIGN.md section 9.
     load_const_z: np.ndarray = field(default_factory=lambda: np.zeros(0))
     load_const_i: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    # thermal ratings behind res_line / res_trafo loading_percent (VoltageControlBatch.res_line / res_trafo / loading_summary; DESIGN.md
+    # section 17).  empty = unrated (loading_percent NaN), and they stay empty on the built-in cases.  line_max_i_ka = net.line.max_i_ka
+    # (NaN: that line is unrated), line_df = net.line.df (empty = 1); br_vn_hv_kv / br_vn_lv_kv = the transformer's nameplate voltages,
+    # br_rating_mva = its sn_mva x parallel x df (NaN: unrated); br_from_bus is the hv side.  data.from_pandapower fills them.
+    line_max_i_ka: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    line_df: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    br_vn_hv_kv: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    br_vn_lv_kv: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    br_rating_mva: np.ndarray = field(default_factory=lambda: np.zeros(0))
 
     def __post_init__(self):
         f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
@@ -107,6 +116,13 @@ class NetSpec:
                 raise ValueError(f"{k} must be a fraction in [0, 1] (const_*_percent / 100) for every load")
         if np.any(self.load_const_z + self.load_const_i > 1.0):
             raise ValueError("const_z_percent + const_i_percent need to be less or equal to 100%!")
+        for k, n in (("line_max_i_ka", np.shape(self.line_from_bus)[0]), ("line_df", np.shape(self.line_from_bus)[0]),
+                     ("br_vn_hv_kv", np.shape(self.br_from_bus)[0]), ("br_vn_lv_kv", np.shape(self.br_from_bus)[0]),
+                     ("br_rating_mva", np.shape(self.br_from_bus)[0])):
+            v = f64(getattr(self, k))
+            setattr(self, k, v)
+            if v.shape[0] and v.shape != (n,):
+                raise ValueError(f"{k} must be empty or have one entry per row ({n}), got shape {v.shape}")
         if np.shape(self.bus_alias)[0] == 0:
             self.bus_alias = np.arange(np.shape(self.bus_vn_kv)[0])
         for k in ("bus_zone", "line_from_bus", "line_to_bus", "line_parallel", "load_bus",

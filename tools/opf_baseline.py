@@ -13,6 +13,7 @@ OPFControl and with NoControl over N episodes of --steps steps and prints
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -47,15 +48,17 @@ class TimedOPF(OPFControl):
         return a
 
 
-def run_case(case, episodes, steps, seed, cfg, device, controllers=("opf", "no_control")):
+def run_case(case, episodes, steps, seed, cfg, device, controllers=("opf", "no_control"), loading=False, max_i_ka=None):
     net, prof = make_case(case)
+    if max_i_ka is not None:                                   # the built-in cases carry no ratings: one for every line
+        net = dataclasses.replace(net, line_max_i_ka=np.full(net.n_line, float(max_i_ka)))
     out = {}
     for ctrl in (TimedOPF(cfg), NoControl()):
         if ctrl.name not in controllers:
             continue
         env = VoltageControlBatch(net, prof, dict(ARGS, seed=seed), n_envs=episodes, device=device)
         try:
-            tester = BaselineTester(types.SimpleNamespace(max_steps=steps), ctrl, env)
+            tester = BaselineTester(types.SimpleNamespace(max_steps=steps), ctrl, env, record_loading=loading)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             stat = tester.batch_run(episodes)
@@ -66,6 +69,8 @@ def run_case(case, episodes, steps, seed, cfg, device, controllers=("opf", "no_c
         env_steps = episodes * steps
         r = dict(CR=stat["mean_test_totally_controllable_ratio"][0], QL=stat["mean_test_q_loss"][0],
                  PL=stat["mean_test_total_line_loss"][0], wall_s=wall, env_steps_per_s=env_steps / wall, stat=stat)
+        if loading:
+            r.update(max_loading_percent=stat["mean_test_max_loading_percent"][0], overloaded_steps_ratio=stat["mean_test_overloaded_steps_ratio"][0])
         flows = env_steps
         if isinstance(ctrl, OPFControl):
             it = torch.stack([h[2] for h in ctrl.history]).cpu().numpy()      # [steps, B]
@@ -92,12 +97,15 @@ def main():
     ap.add_argument("--max-iter", type=int, default=50)
     ap.add_argument("--controllers", nargs="+", default=["opf", "no_control"], choices=["opf", "no_control"])
     ap.add_argument("--json", default=None, help="write the results here")
+    ap.add_argument("--loading", action="store_true", help="also print the mean of the largest branch loading_percent per step and the "
+                    "share of steps with a branch above 100 %% (BaselineTester(record_loading=True); NaN on a net without ratings)")
+    ap.add_argument("--max-i-ka", type=float, default=None, help="with --loading: rate every line at this max_i_ka (the built-in cases carry no ratings)")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     cfg = OPFConfig(max_iter=a.max_iter)
     res = dict(config=cfg.as_dict(), episodes=a.episodes, steps=a.steps, seed=a.seed, cases={})
     for case in a.cases:
-        r = res["cases"][case] = run_case(case, a.episodes, a.steps, a.seed, cfg, a.device, a.controllers)
+        r = res["cases"][case] = run_case(case, a.episodes, a.steps, a.seed, cfg, a.device, a.controllers, a.loading, a.max_i_ka)
         for name, x in r.items():
             line = (f"{case:8s} {name:10s} CR {x['CR']:.4f}  QL {x['QL']:.4f}  PL {x['PL']:.4f}  | {x['wall_s']:.2f} s  "
                     f"{x['env_steps_per_s']:.3e} env-steps/s  {x['power_flows_per_s']:.3e} power flows/s")
@@ -105,6 +113,8 @@ def main():
                 line += (f"  | solves/step mean {x['solves_mean']:.2f} p99 {x['solves_p99']:.0f} max {x['solves_max']}  "
                          f"status 0 {100 * x['share_status0']:.2f} %  1 {100 * x['share_status1']:.2f} %  2 {100 * x['share_status2']:.2f} %  "
                          f"| {x['ms_per_call']:.1f} ms / call (first {x['ms_first_call']:.1f})")
+            if a.loading:
+                line += f"  | max loading {x['max_loading_percent']:.2f} %  overloaded steps {100 * x['overloaded_steps_ratio']:.2f} %"
             print(line, flush=True)
     if a.json:
         with open(a.json, "w") as f:
