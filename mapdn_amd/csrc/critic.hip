@@ -22,6 +22,13 @@
 // dW2 / dgamma / dbeta / db2 / dw3 / db3 (and, for formed rows, dper_n) are accumulated per wavefront over its contiguous range of
 // rows, summed across the wavefronts of a workgroup through LDS and across workgroups by a second small launch, both in a fixed
 // order: deterministic, no atomics.
+//
+// Where things live: rowtile.hpp has the lane-level helpers (reductions, LayerNorm statistics, wave_sync); headtile.hpp has the trunk on
+// one tile as steps (head_value forward; mm64_lds, dpre_step, dw2_step, ln_backward, formed_handover, head_partials backward).  This file
+// has the single head's kernels — how a row is read or formed, what dv is (given, or the fused value loss), where dx goes — the launch
+// shapes and the C entry points; critic_twin.hip, critic_cf.hip and critic_shap.hip, included at the end, put the same steps together
+// for MATD3, COMA and SQDDPG (k_twin_mse keeps its LayerNorm backward and critic_shap.hip its four MFMA products spelt out, for the
+// reasons given there).  critic_attn.hip (MAAC) shares only head_cus and k_head_reduce.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -30,6 +37,7 @@
 
 #include "../../include/mapdn.h"
 #include "rowtile.hpp"
+#include "headtile.hpp"
 
 namespace mapdn {
 
@@ -55,39 +63,16 @@ template <bool BC>
 __global__ void __launch_bounds__(256)
 k_head_fwd(HeadArgs p, float* __restrict__ v, long rows) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, j = lane & 15;
-  f4 wop[4][4], gam[4], bet[4], b2v[4], w3v[4];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) wop[nt][c] = *(const f4*)(p.w2 + (size_t)(16 * nt + j) * 64 + 16 * c + 4 * g);
-    gam[nt] = *(const f4*)(p.gamma + 16 * nt + 4 * g); bet[nt] = *(const f4*)(p.beta + 16 * nt + 4 * g);
-    b2v[nt] = *(const f4*)(p.b2 + 16 * nt + 4 * g); w3v[nt] = *(const f4*)(p.w3 + 16 * nt + 4 * g);
-  }
+  f4 wop[4][4];
+  load_w2_operand(p.w2, j, g, wop);
+  const HeadParams<false> par(p, g);
   const float b3 = p.b3[0];
   const long n_tiles = (rows + 15) >> 4;
   for (long T = (long)blockIdx.x * 4 + wave; T < n_tiles; T += (long)gridDim.x * 4) {
     const long row = T * 16 + j;
     f4 xa[4];
     load_row<BC>(p, row < rows ? row : rows - 1, g, xa);
-    ln_stats(xa, p.eps);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const f4 y = xa[c] * gam[c] + bet[c];
-      xa[c] = f4{relu_nan(y.x), relu_nan(y.y), relu_nan(y.z), relu_nan(y.w)};
-    }
-    f4 acc[4] = {f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}};
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wop[nt][c][q], xa[c][q], acc[nt], 0, 0, 0);
-    float dot = 0.0f;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dot = fmaf(relu_nan(acc[nt][r] + b2v[nt][r]), w3v[nt][r], dot);
-    dot = sum_g(dot);
+    const float dot = head_value(xa, p.eps, wop, par);
     if (g == 0 && row < rows) v[row] = dot + b3;
   }
 }
@@ -112,33 +97,14 @@ k_head_bwd(HeadArgs p, const float* __restrict__ dv, float* __restrict__ dx, con
   constexpr int NW = NT / 64, TILES = NT == 512 ? 1 : 2;
   constexpr bool SLIM = NT == 512;
   extern __shared__ float sm[];
-  f4* sW = (f4*)sm;                         // [4 nt][4 c][64]: W2[16 nt + j][16 c + 4 g + q]       A operand of pre^T = W2 xn^T
-  f4* sWT = sW + 1024;                      // [4 nt][4 c][64]: W2[16 c + 4 g + q][16 nt + j]       A operand of dxn^T = W2^T dpre^T
-  float* sP = (float*)(sWT + 1024);         // gamma | beta | b2 | w3 [4][64]
-  float* stage = sP + 256 + (size_t)(threadIdx.x >> 6) * TILES * 16 * HS;                // TILES 16 x HS tiles per wavefront
-  float* accn = sP + 256 + (size_t)NW * TILES * 16 * HS + (size_t)(threadIdx.x >> 6) * p.n * 64;   // [n][64] per wavefront (BC, MODE != 2)
+  const HeadLds L(sm);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, j = lane & 15;
-  if (tid < 64) { sP[tid] = p.gamma[tid]; sP[64 + tid] = p.beta[tid]; sP[128 + tid] = p.b2[tid]; sP[192 + tid] = p.w3[tid]; }
-  for (int i = tid; i < 1024; i += NT) {
-    const int l = i & 63, c = (i >> 6) & 3, nt = i >> 8, lj = l & 15, lg = l >> 4;
-    sW[i] = *(const f4*)(p.w2 + (size_t)(16 * nt + lj) * 64 + 16 * c + 4 * lg);
-    f4 t;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) t[q] = p.w2[(size_t)(16 * c + 4 * lg + q) * 64 + 16 * nt + lj];
-    sWT[i] = t;
-  }
+  float* stage = L.rest + (size_t)wave * TILES * 16 * HS;                                   // TILES 16 x HS tiles per wavefront
+  float* accn0 = L.rest + (size_t)NW * TILES * 16 * HS, *accn = accn0 + (size_t)wave * p.n * 64;   // [n][64] per wavefront (BC, MODE != 2)
+  L.fill(p, tid, NT);
   if (BC && MODE != 2) for (int i = lane; i < p.n * 64; i += 64) accn[i] = 0.0f;
-  f4 gam_[4], bet_[4], b2v_[4], w3v_[4];     // (dead in the SLIM build: the accessors below read LDS there)
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-    gam_[nt] = *(const f4*)(p.gamma + 16 * nt + 4 * g); bet_[nt] = *(const f4*)(p.beta + 16 * nt + 4 * g);
-    b2v_[nt] = *(const f4*)(p.b2 + 16 * nt + 4 * g); w3v_[nt] = *(const f4*)(p.w3 + 16 * nt + 4 * g);
-  }
+  const HeadParams<SLIM> par(p, g, L.sP);
   __syncthreads();
-  auto GAM = [&](int c) -> f4 { return SLIM ? *(const f4*)(sP + 16 * c + 4 * g) : gam_[c]; };
-  auto BET = [&](int c) -> f4 { return SLIM ? *(const f4*)(sP + 64 + 16 * c + 4 * g) : bet_[c]; };
-  auto B2V = [&](int c) -> f4 { return SLIM ? *(const f4*)(sP + 128 + 16 * c + 4 * g) : b2v_[c]; };
-  auto W3V = [&](int c) -> f4 { return SLIM ? *(const f4*)(sP + 192 + 16 * c + 4 * g) : w3v_[c]; };
 
   // this wavefront's range of rows [r0, r1)
   const long W = (long)gridDim.x * NW, w = (long)blockIdx.x * NW + wave;
@@ -146,17 +112,9 @@ k_head_bwd(HeadArgs p, const float* __restrict__ dv, float* __restrict__ dx, con
   if (BC) { const long G = rows / p.n; r0 = (G * w / W) * p.n; r1 = (G * (w + 1) / W) * p.n; }
   else { const long Tn = (rows + 15) >> 4; r0 = (Tn * w / W) * 16; r1 = (Tn * (w + 1) / W) * 16; if (r1 > rows) r1 = rows; }
 
-  f4 accW[4][4];                            // dW2[16 ntu + 4 g + r][16 ntk + j]
-  f4 ag[4], ab[4], aw3[4], ab2[4];          // column sums in A layout (this lane's row j only): dgamma, dbeta, dw3, db2
-  float ab3 = 0.0f, carry = 0.0f;           // db3; running sum of dx over the rows of the current group (lane = column)
-  float aloss = 0.0f;
+  HeadAcc A;
+  float carry = 0.0f;                       // running sum of dx over the rows of the current group (lane = column)
   const float b3 = MODE == 3 ? p.b3[0] : 0.0f, lscale = MODE == 3 ? scale[0] : 0.0f;
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-#pragma unroll
-    for (int b = 0; b < 4; ++b) accW[a][b] = f4{0, 0, 0, 0};
-    ag[a] = ab[a] = aw3[a] = ab2[a] = f4{0, 0, 0, 0};
-  }
 
   // the rows of the NEXT tile are requested while the current one is in the matrix cores (one wavefront per SIMD: nobody else hides
   // the HBM / L2 latency)
@@ -186,125 +144,23 @@ k_head_bwd(HeadArgs p, const float* __restrict__ dv, float* __restrict__ dx, con
       }
     }
     const float rs = ln_stats(xh, p.eps);
-    f4 xn[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const f4 y = xh[c] * GAM(c) + BET(c);
-      xn[c] = f4{relu_nan(y.x), relu_nan(y.y), relu_nan(y.z), relu_nan(y.w)};
-    }
-    // ---- pre^T = W2 xn^T
-    f4 acc[4] = {f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      f4 wv[4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) wv[nt] = sW[(nt * 4 + c) * 64 + lane];
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[nt][q], xn[c][q], acc[nt], 0, 0, 0);
-    }
-    // ---- dpre = [pre > 0] dv w3 (in place of acc); dw3 += relu(pre) dv; db2 += dpre; db3 += dv
+    f4 xn[4], acc[4], dxn[4];
+    ln_affine_relu(xh, par, xn);
+    mm64_lds(L.sW, lane, xn, acc);           // pre^T = W2 xn^T
     float dvr = dvcur;                       // (MODE 3: dv holds the returns)
     if (MODE == 3) {
-      float dot = 0.0f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        const f4 bb = B2V(nt), ww = W3V(nt);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dot = fmaf(relu_nan(acc[nt][r] + bb[r]), ww[r], dot);
-      }
-      const float err = dvcur - (sum_g(dot) + b3);
       float wgt = lscale;
       if (wrow) { const unsigned rc = (unsigned)(valid ? row : r1 - 1); wgt *= wrow[BC ? rc / (unsigned)p.n : rc]; }
-      dvr = valid ? -2.0f * wgt * err : 0.0f;
-      if (valid && g == 0) aloss = fmaf(wgt * err, err, aloss);
+      dvr = mse_dv(acc, par, b3, dvcur, wgt, valid, g, A.aloss);
     }
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      const f4 bb = B2V(nt), ww = W3V(nt);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float pre = acc[nt][r] + bb[r];
-        const bool pos = pre > 0.0f;
-        const float dp = pos ? dvr * ww[r] : 0.0f;
-        if (PG) { aw3[nt][r] = fmaf(pos ? pre : 0.0f, dvr, aw3[nt][r]); ab2[nt][r] += dp; }
-        acc[nt][r] = dp;
-      }
-    }
-    if (PG && g == 0) ab3 += dvr;
-    // ---- dxn^T = W2^T dpre^T
-    f4 dxn[4] = {f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      f4 wv[4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) wv[nt] = sWT[(nt * 4 + c) * 64 + lane];
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) dxn[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[nt][q], acc[c][q], dxn[nt], 0, 0, 0);
-    }
-    // ---- dW2 += dpre^T xn: both operands through LDS into C layout (rows on the contraction axis)
-    if (PG) {
-      float* s0 = stage; float* s1 = SLIM ? stage : stage + 16 * HS;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) *(f4*)(s0 + j * HS + 16 * c + 4 * g) = acc[c];
-      if (!SLIM) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) *(f4*)(s1 + j * HS + 16 * c + 4 * g) = xn[c];
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      float dCs[4][4];                      // SLIM: dpre in C layout for all four steps, read before the one tile is reused for xn
-      if (SLIM) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) dCs[s][nt] = s0[(4 * g + s) * HS + 16 * nt + j];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int c = 0; c < 4; ++c) *(f4*)(s1 + j * HS + 16 * c + 4 * g) = xn[c];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        float dC[4], xC[4];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) { dC[nt] = SLIM ? dCs[s][nt] : s0[(4 * g + s) * HS + 16 * nt + j]; xC[nt] = s1[(4 * g + s) * HS + 16 * nt + j]; }
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-          for (int b = 0; b < 4; ++b) accW[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(dC[a], xC[b], accW[a][b], 0, 0, 0);
-      }
-    }
-    // ---- LayerNorm backward on the lane's row: d = [y > 0] dxn, a = d gamma, dx = rstd (a - mean(a) - xhat mean(a xhat))
-    float s1a = 0.0f, s2a = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      f4 d;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) d[q] = xn[c][q] > 0.0f ? dxn[c][q] : 0.0f;
-      if (PG) { ag[c] += d * xh[c]; ab[c] += d; }
-      const f4 a = d * GAM(c);
-      s1a += hsum(a); s2a += hsum(a * xh[c]);
-      dxn[c] = a;
-    }
-    const float m1 = sum_g(s1a) * (1.0f / 64.0f), m2 = sum_g(s2a) * (1.0f / 64.0f);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) dxn[c] = (dxn[c] - m1 - xh[c] * m2) * rs;
+    dpre_step<PG>(acc, dvr, par, g, A);
+    mm64_lds(L.sWT, lane, acc, dxn);         // dxn^T = W2^T dpre^T
+    if (PG) dw2_step<SLIM>(stage, j, g, acc, xn, A.accW);
+    ln_backward<PG>(xn, xh, rs, par, dxn, A);
     // ---- hand dx over
     if (MODE == 2) {
       const unsigned i = BC ? (unsigned)((valid ? row : r1 - 1) - r0) % (unsigned)p.n : 0u;
-      const float* pw = dot_w + (size_t)i * 64 + 4 * g;
-      float d = 0.0f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) d += hsum(dxn[c] * *(const f4*)(pw + 16 * c));
-      d = sum_g(d);
+      const float d = dx_dot(dxn, dot_w + (size_t)i * 64 + 4 * g);
       if (g == 0 && valid) dact[row] = d;
     } else if (!BC) {
       if (valid) {
@@ -313,101 +169,16 @@ k_head_bwd(HeadArgs p, const float* __restrict__ dv, float* __restrict__ dx, con
         for (int c = 0; c < 4; ++c) *(f4*)(px + 16 * c) = dxn[c];
       }
     } else {
-      // formed rows: dbase[group] = sum of dx over the group's n rows, dper_n[i] += dx — lane = column, the tile's rows in order
-      float* s0 = stage;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();          // (the dW2 reads of this tile are done)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) *(f4*)(s0 + j * HS + 16 * c + 4 * g) = dxn[c];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const int cnt = (int)(r1 - row0 < 16 ? r1 - row0 : 16);
-      const unsigned rel = (unsigned)(row0 - r0);
-      unsigned grp = rel / (unsigned)p.n, i = rel - grp * (unsigned)p.n;
-      float* pbase = dx + ((size_t)(r0 / p.n) + grp) * 64 + lane;
-      if (p.n >= 16) {
-        unsigned i2 = i;                      // (i stays the tile's first agent index for the slot addresses)
-        // the tile's 16 rows belong to 16 DIFFERENT agents: their dper_n slots are independent — 16 reads, 16 adds, 16 writes in flight
-        // instead of 16 dependent LDS round trips
-        constexpr int H = SLIM ? 4 : 16;      // rows in flight (the SLIM build has 256 registers: four at a time)
-#pragma unroll
-        for (int h0 = 0; h0 < 16; h0 += H) {
-          float val[H], cur[H];
-#pragma unroll
-          for (int rr = 0; rr < H; ++rr) {
-            unsigned ii = i + h0 + rr; if (ii >= (unsigned)p.n) ii -= p.n;
-            val[rr] = h0 + rr < cnt ? s0[(h0 + rr) * HS + lane] : 0.0f;
-            cur[rr] = accn[ii * 64 + lane];
-          }
-#pragma unroll
-          for (int rr = 0; rr < H; ++rr) {
-            unsigned ii = i + h0 + rr; if (ii >= (unsigned)p.n) ii -= p.n;
-            accn[ii * 64 + lane] = cur[rr] + val[rr];
-          }
-#pragma unroll
-          for (int rr = 0; rr < H; ++rr)
-            if (h0 + rr < cnt) {
-              carry += val[rr];
-              if (++i2 == (unsigned)p.n) { *pbase = carry; carry = 0.0f; i2 = 0; pbase += 64; }
-            }
-        }
-      } else {
-        for (int rr = 0; rr < cnt; ++rr) {
-          const float val = s0[rr * HS + lane];
-          carry += val;
-          accn[i * 64 + lane] += val;
-          if (++i == (unsigned)p.n) { *pbase = carry; carry = 0.0f; i = 0; pbase += 64; }
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_release();                        // (the dW2 reads of the staging tile are done)
+      formed_handover<SLIM ? 4 : 16>(stage, accn, dx, dxn, carry, p.n, r0, r1, row0, lane, j, g);   // (SLIM: 256 registers, four rows in flight)
     }
   }
 
-  // ---- partial sums: the wavefronts of a workgroup are summed HERE, through LDS (the weights and staging tiles are dead by now), in a
-  // fixed order, so that the second launch reads one partial per workgroup (256) instead of one per wavefront (2048)
+  // ---- one partial block per workgroup: [0, HW) the parameter gradients | pad | [HP, HP + n * 64) dper_n
   if (MODE != 2) {
     float* pp = partial + (size_t)blockIdx.x * pstride;
-    if (BC) {                                 // dper_n: the per-wavefront [n][64] accumulators are already in LDS
-      __syncthreads();
-      const float* a0 = sP + 256 + (size_t)NW * TILES * 16 * HS;
-      for (int i = tid; i < p.n * 64; i += NT) {
-        float t = a0[i];
-#pragma unroll
-        for (int ww = 1; ww < NW; ++ww) t += a0[(size_t)ww * p.n * 64 + i];
-        pp[HP + i] = t;
-      }
-    }
-    if (PG) {
-      __syncthreads();                        // every wavefront is out of its tile loop (and done with accn)
-      float* red = sm + (size_t)wave * HP;    // [NW][HP] floats from the start of LDS (the launch sizes LDS for it)
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) red[(16 * a + 4 * g + r) * 64 + 16 * b + j] = accW[a][b][r];
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float tg = sum_j(ag[c][q]), tb = sum_j(ab[c][q]), t2 = sum_j(ab2[c][q]), t3 = sum_j(aw3[c][q]);
-          if (j == 0) {
-            const int col = 16 * c + 4 * g + q;
-            red[4096 + col] = tg; red[4160 + col] = tb; red[4224 + col] = t2; red[4288 + col] = t3;
-          }
-        }
-      const float t = sum_j(ab3), tl = sum_j(aloss);           // (lanes with g != 0 hold 0)
-      if (lane == 0) { red[4352] = t; red[4353] = tl; }
-      __syncthreads();
-      for (int col = tid; col < HW; col += NT) {
-        float v = sm[col];
-#pragma unroll
-        for (int ww = 1; ww < NW; ++ww) v += sm[(size_t)ww * HP + col];
-        pp[col] = v;
-      }
-    }
+    if (BC) wave_blocks_sum<NT>(accn0, (size_t)p.n * 64, p.n * 64, pp + HP, tid);
+    if (PG) head_partials<NT, HP>(sm, pp, A, nullptr, tid);
   }
 }
 
@@ -430,6 +201,11 @@ static int head_cus() {
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   return cus;
+}
+// workgroups of a forward launch (k_head_fwd, k_twin_fwd; k_cf_baseline restates it): four wavefronts, a tile of 16 rows each per step; two per CU at most
+static int head_fwd_blocks(int64_t rows) {
+  const int64_t tiles = (rows + 15) / 16;
+  return (int)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, (int64_t)head_cus() * 2));
 }
 // workgroups of the backward launch: one per CU (its wavefronts keep dW2 in registers, the weights in LDS), never more wavefronts
 // than units of work (groups of n formed rows / tiles of 16 rows); nw = wavefronts per workgroup (4, or 8 for the 512-thread build)
@@ -458,14 +234,19 @@ static bool head_args_ok(const float* x, const float* per_n, int32_t n, const fl
   return true;
 }
 
+// the kernels' view of a head: rows that are read (per_n == nullptr; n is 1 then) or formed as x[row / n] + per_n[row % n]
+static mapdn::HeadArgs head_args(const float* x, const float* per_n, int32_t n, const float* gamma, const float* beta, float eps, const float* w2,
+                                 const float* b2, const float* w3, const float* b3) {
+  return mapdn::HeadArgs{x, per_n, per_n ? n : 1, gamma, beta, eps, w2, b2, w3, b3};
+}
+
 extern "C" int mapdn_critic_head_forward(const float* x, const float* per_n, int32_t n, const float* gamma, const float* beta, float eps,
                                          const float* w2, const float* b2, const float* w3, const float* b3, float* v, int64_t rows,
                                          void* stream) {
   using namespace mapdn;
   if (!head_args_ok(x, per_n, n, gamma, beta, w2, b2, w3, b3, rows) || !v) return MAPDN_E_INVALID;
-  const HeadArgs a{x, per_n, per_n ? n : 1, gamma, beta, eps, w2, b2, w3, b3};
-  const int64_t tiles = (rows + 15) / 16;
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, (int64_t)head_cus() * 2));
+  const HeadArgs a = head_args(x, per_n, n, gamma, beta, eps, w2, b2, w3, b3);
+  const int blocks = head_fwd_blocks(rows);
   if (per_n) hipLaunchKernelGGL(k_head_fwd<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, v, (long)rows);
   else hipLaunchKernelGGL(k_head_fwd<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, v, (long)rows);
   return hipGetLastError() == hipSuccess ? MAPDN_OK : MAPDN_E_HIP;
@@ -525,7 +306,7 @@ extern "C" int mapdn_critic_head_backward(const float* dv, const float* x, const
   using namespace mapdn;
   if (!head_args_ok(x, per_n, n, gamma, beta, w2, b2, w3, b3, rows) || !dv || !dx || ((param_grads || per_n) && (!grads || !scratch)))
     return MAPDN_E_INVALID;
-  const HeadArgs a{x, per_n, per_n ? n : 1, gamma, beta, eps, w2, b2, w3, b3};
+  const HeadArgs a = head_args(x, per_n, n, gamma, beta, eps, w2, b2, w3, b3);
   hipStream_t st = (hipStream_t)stream;
   if (per_n) return param_grads ? head_bwd_launch<true, 0>(a, dv, dx, nullptr, nullptr, scratch, grads, rows, st)
                                 : head_bwd_launch<true, 1>(a, dv, dx, nullptr, nullptr, scratch, grads, rows, st);
@@ -538,7 +319,7 @@ extern "C" int mapdn_critic_head_backward_dot(const float* dv, const float* x, c
                                               const float* dot_w, float* dact, int64_t rows, void* stream) {
   using namespace mapdn;
   if (!head_args_ok(x, per_n, n, gamma, beta, w2, b2, w3, b3, rows) || !dv || !dot_w || !dact) return MAPDN_E_INVALID;
-  const HeadArgs a{x, per_n, per_n ? n : 1, gamma, beta, eps, w2, b2, w3, b3};
+  const HeadArgs a = head_args(x, per_n, n, gamma, beta, eps, w2, b2, w3, b3);
   hipStream_t st = (hipStream_t)stream;
   return per_n ? head_bwd_launch<true, 2>(a, dv, nullptr, dot_w, dact, nullptr, nullptr, rows, st)
                : head_bwd_launch<false, 2>(a, dv, nullptr, dot_w, dact, nullptr, nullptr, rows, st);
@@ -551,7 +332,7 @@ extern "C" int mapdn_critic_head_mse(const float* ret, const float* wrow, const 
                                      const float* b3, float* dx, float* grads, float* scratch, int64_t rows, void* stream) {
   using namespace mapdn;
   if (!head_args_ok(x, per_n, n, gamma, beta, w2, b2, w3, b3, rows) || !ret || !scale || !dx || !grads || !scratch) return MAPDN_E_INVALID;
-  const HeadArgs a{x, per_n, per_n ? n : 1, gamma, beta, eps, w2, b2, w3, b3};
+  const HeadArgs a = head_args(x, per_n, n, gamma, beta, eps, w2, b2, w3, b3);
   hipStream_t st = (hipStream_t)stream;
   return per_n ? head_bwd_launch<true, 3>(a, ret, dx, nullptr, nullptr, scratch, grads, rows, st, wrow, scale)
                : head_bwd_launch<false, 3>(a, ret, dx, nullptr, nullptr, scratch, grads, rows, st, wrow, scale);

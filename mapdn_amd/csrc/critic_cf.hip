@@ -1,4 +1,5 @@
-// critic_cf.hip — COMA's counterfactual baseline as ONE launch, gfx950 (MI355X).  Compiled inside critic.hip (its helpers and layouts).
+// critic_cf.hip — COMA's counterfactual baseline as ONE launch, gfx950 (MI355X).  Compiled inside critic.hip (its layouts and load_row; the
+// head itself is head_value of headtile.hpp: this file has the sampled rows and the mean over them).
 //
 // Reference: models/coma.py:139-151 — for every transition and agent i the critic is valued sample_size more times with agent i's
 // action replaced by a draw from N(mean_i, std), on a [S b, n, (n + 1) o + n + n a] input, and the S values are averaged.  The first
@@ -16,14 +17,9 @@ __global__ void __launch_bounds__(256)
 k_cf_baseline(HeadArgs p, const float* __restrict__ act_col, const float* __restrict__ delta, int S, float* __restrict__ baseline,
               float* __restrict__ v0, long rows) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, j = lane & 15;
-  f4 wop[4][4], gam[4], bet[4], b2v[4], w3v[4];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) wop[nt][c] = *(const f4*)(p.w2 + (size_t)(16 * nt + j) * 64 + 16 * c + 4 * g);
-    gam[nt] = *(const f4*)(p.gamma + 16 * nt + 4 * g); bet[nt] = *(const f4*)(p.beta + 16 * nt + 4 * g);
-    b2v[nt] = *(const f4*)(p.b2 + 16 * nt + 4 * g); w3v[nt] = *(const f4*)(p.w3 + 16 * nt + 4 * g);
-  }
+  f4 wop[4][4];
+  load_w2_operand(p.w2, j, g, wop);
+  const HeadParams<false> par(p, g);
   const float b3 = p.b3[0];
   const long n_tiles = (rows + 15) >> 4;
   for (long T = (long)blockIdx.x * 4 + wave; T < n_tiles; T += (long)gridDim.x * 4) {
@@ -48,25 +44,7 @@ k_cf_baseline(HeadArgs p, const float* __restrict__ act_col, const float* __rest
 #pragma unroll
           for (int q = 0; q < 4; ++q) xa[c][q] = fmaf(d, col[c][q], xb[c][q]);
       }
-      ln_stats(xa, p.eps);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const f4 y = xa[c] * gam[c] + bet[c];
-        xa[c] = f4{relu_nan(y.x), relu_nan(y.y), relu_nan(y.z), relu_nan(y.w)};
-      }
-      f4 acc[4] = {f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}};
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wop[nt][c][q], xa[c][q], acc[nt], 0, 0, 0);
-      float dot = 0.0f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dot = fmaf(relu_nan(acc[nt][r] + b2v[nt][r]), w3v[nt][r], dot);
-      const float v = sum_g(dot) + b3;
+      const float v = head_value(xa, p.eps, wop, par) + b3;
       if (s < 0) { if (g == 0 && row < rows) v0[row] = v; }
       else sum += v;
     }
@@ -83,7 +61,7 @@ extern "C" int mapdn_critic_head_counterfactual(const float* x, int32_t n, const
   if (!head_args_ok(x, nullptr, 1, gamma, beta, w2, b2, w3, b3, rows) || !act_col || !delta || !baseline || n < 1 || S < 1 || S > 64)
     return MAPDN_E_INVALID;
   const HeadArgs a{x, nullptr, n, gamma, beta, eps, w2, b2, w3, b3};
-  const int64_t tiles = (rows + 15) / 16;
+  const int64_t tiles = (rows + 15) / 16;      // (head_fwd_blocks(rows), spelt out: tests/test_cf_kernel_matrix_cpu.py reads the launch shape here)
   const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, (int64_t)head_cus() * 2));
   hipLaunchKernelGGL(k_cf_baseline, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, act_col, delta, (int)S, baseline, v0, (long)rows);
   return hipGetLastError() == hipSuccess ? MAPDN_OK : MAPDN_E_HIP;

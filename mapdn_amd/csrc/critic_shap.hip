@@ -1,5 +1,7 @@
 // critic_shap.hip — SQDDPG's Shapley coalition critic (models/sqddpg.py:37-106) on rows that are FORMED in the kernel, gfx950.
-// Included at the end of critic.hip (HeadArgs, k_head_reduce, head_cus and the row-tile helpers are in scope).
+// Included at the end of critic.hip (HeadArgs, k_head_reduce, head_cus, the row-tile helpers of rowtile.hpp and the trunk's steps of
+// headtile.hpp are in scope: this file has the coalition rows — the prefix P, the walks over a group — and where their dx goes; its
+// four MFMA products stay spelt out here, see k_shap_fwd).
 //
 // The reference evaluates its critic on b x S x n rows of width n o + n a + n: sample b, coalition draw s, agent i.  With a = 1 and
 // pos[b][s][i] = the position of agent i in draw s's order (gc = argsort(pos) = the agent at each position), the first layer of row
@@ -8,7 +10,7 @@
 // (base = W_obs obs_all + b1, id_cols / act_cols = the id / action columns of fc1, transposed to [n][64]): the action slots are filled by
 // POSITION, the slots behind the own one are zero, and only the own slot carries a gradient back to the action.  A wavefront owns
 // whole samples (S n rows) and walks them in chunks of whole (b, s) groups: the chunk's prefix P is built once in LDS by a running sum
-// (lane = column), then the chunk's rows go through the trunk of k_head_fwd / k_head_bwd in tiles of 16, straddling groups.  Backward,
+// (lane = column), then the chunk's rows go through the trunk (headtile.hpp, as k_head_fwd / k_head_bwd) in tiles of 16, straddling groups.  Backward,
 // row (b, s, i) writes its dx over P[pos_i] — the slot that it alone read — so that after the chunk's tiles the same LDS rows hold dx in
 // POSITION order and
 //     dact_cols[q] += act[b][gc[q]] sum_{p >= q} dx[gc[p]]   (a suffix sum),   did_cols[gc[p]] += dx,   dbase[b] = sum over the sample
@@ -24,12 +26,6 @@ struct ShapArgs {
   int S, CG;                           // draws per sample; groups per chunk
   long b;
 };
-
-__device__ __forceinline__ void shap_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // floats of per-wavefront LDS behind the staging tiles: P [CR][64] | pos [CR] | gc [CR] | act by slot [CR] | per-row value [CR] |
 // per-agent running sum [n] (| did_cols [n][64] | dact_cols [n][64]), CR = CG n; rounded to 4 floats (P is read as float4)
@@ -56,14 +52,14 @@ __device__ __forceinline__ void shap_chunk_setup(const HeadArgs& p, const ShapAr
     L.posS[r] = ps;
     L.gcS[r] = 0;
   }
-  shap_wave_sync();
+  wave_sync();
   for (int r = lane; r < nr; r += 64) { const int grp = r / n; L.gcS[grp * n + L.posS[r]] = r - grp * n; }
-  shap_wave_sync();
+  wave_sync();
   for (int r = lane; r < nr; r += 64) {
     const int grp = r / n;
     L.actS[r] = q.act[(size_t)((gq + grp) / q.S) * n + L.gcS[r]];
   }
-  shap_wave_sync();
+  wave_sync();
   for (int grp = 0; grp < ng; ++grp) {
     float run = 0.0f;
     float* Pg = L.P + (size_t)grp * n * 64 + lane;
@@ -71,7 +67,7 @@ __device__ __forceinline__ void shap_chunk_setup(const HeadArgs& p, const ShapAr
 #pragma unroll 4
     for (int s = 0; s < n; ++s) { run = fmaf(ag[s], q.act_cols[(size_t)s * 64 + lane], run); Pg[s * 64] = run; }
   }
-  shap_wave_sync();
+  wave_sync();
 }
 
 // row r of the chunk in A layout: base[b] + id_cols[i] + P[group][pos_i]; returns the row's P slot
@@ -105,14 +101,9 @@ k_shap_fwd(HeadArgs p, ShapArgs q, float* __restrict__ v, float* __restrict__ ph
   extern __shared__ float sm[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, j = lane & 15, n = p.n;
   const ShapWave L(sm + (size_t)wave * shap_wave_floats(n, q.CG, false), n, q.CG);
-  f4 wop[4][4], gam[4], bet[4], b2v[4], w3v[4];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) wop[nt][c] = *(const f4*)(p.w2 + (size_t)(16 * nt + j) * 64 + 16 * c + 4 * g);
-    gam[nt] = *(const f4*)(p.gamma + 16 * nt + 4 * g); bet[nt] = *(const f4*)(p.beta + 16 * nt + 4 * g);
-    b2v[nt] = *(const f4*)(p.b2 + 16 * nt + 4 * g); w3v[nt] = *(const f4*)(p.w3 + 16 * nt + 4 * g);
-  }
+  f4 wop[4][4];
+  load_w2_operand(p.w2, j, g, wop);
+  const HeadParams<false> par(p, g);
   const float b3 = p.b3[0], inv_s = 1.0f / (float)q.S;
   const long W = (long)gridDim.x * 4, w = (long)blockIdx.x * 4 + wave;
   const long g0 = (q.b * w / W) * q.S, g1 = (q.b * (w + 1) / W) * q.S;      // whole samples: phi[b] has one writer
@@ -125,10 +116,12 @@ k_shap_fwd(HeadArgs p, ShapArgs q, float* __restrict__ v, float* __restrict__ ph
       const bool valid = r < nr;
       f4 xa[4];
       shap_load_row(p, q, L, gq, valid ? r : nr - 1, g, xa);
+      // head_value() spelt out, and the three products of the backward below: tests/test_shap_kernel_matrix_cpu.py counts the MFMA
+      // products in this file's text and looks for its relu
       ln_stats(xa, p.eps);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const f4 y = xa[c] * gam[c] + bet[c];
+        const f4 y = xa[c] * par.gamma(c) + par.beta(c);
         xa[c] = f4{relu_nan(y.x), relu_nan(y.y), relu_nan(y.z), relu_nan(y.w)};
       }
       f4 acc[4] = {f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}};
@@ -138,17 +131,12 @@ k_shap_fwd(HeadArgs p, ShapArgs q, float* __restrict__ v, float* __restrict__ ph
         for (int qq = 0; qq < 4; ++qq)
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wop[nt][c][qq], xa[c][qq], acc[nt], 0, 0, 0);
-      float dot = 0.0f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) dot = fmaf(relu_nan(acc[nt][rr] + b2v[nt][rr]), w3v[nt][rr], dot);
-      dot = sum_g(dot) + b3;
+      const float dot = head_dot(acc, par) + b3;
       if (g == 0 && valid) { v[(size_t)gq * n + r] = dot; L.valS[r] = dot; }
     }
-    shap_wave_sync();
+    wave_sync();
     if (phi) shap_sum_draws(q, L, n, gq, ng, lane, inv_s, phi);
-    shap_wave_sync();
+    wave_sync();
   }
 }
 
@@ -162,43 +150,22 @@ k_shap_bwd(HeadArgs p, ShapArgs q, const float* __restrict__ dv, float* __restri
            float* __restrict__ partial, int pstride) {
   constexpr int NW = NT / 64;
   extern __shared__ float sm[];
-  f4* sW = (f4*)sm;                         // as k_head_bwd
-  f4* sWT = sW + 1024;
-  float* sP = (float*)(sWT + 1024);
+  const HeadLds H(sm);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, j = lane & 15, n = p.n;
-  const int wfl = 2 * 16 * HS + shap_wave_floats(n, q.CG, PG);
-  float* stage = sP + 256 + (size_t)wave * wfl;
+  const int wfl = 2 * 16 * HS + shap_wave_floats(n, q.CG, PG);     // per wavefront: two staging tiles, then the ShapWave block
+  float* stage = H.rest + (size_t)wave * wfl;
   const ShapWave L(stage + 2 * 16 * HS, n, q.CG);
-  for (int i = tid; i < 1024; i += NT) {
-    const int l = i & 63, c = (i >> 6) & 3, nt = i >> 8, lj = l & 15, lg = l >> 4;
-    sW[i] = *(const f4*)(p.w2 + (size_t)(16 * nt + lj) * 64 + 16 * c + 4 * lg);
-    f4 t;
-#pragma unroll
-    for (int qq = 0; qq < 4; ++qq) t[qq] = p.w2[(size_t)(16 * c + 4 * lg + qq) * 64 + 16 * nt + lj];
-    sWT[i] = t;
-  }
+  H.fill_w2(p, tid, NT);
   if (PG) for (int i = lane; i < 2 * n * 64; i += 64) L.accI[i] = 0.0f;      // (accA follows accI)
   if (dact) for (int i = lane; i < n; i += 64) L.facc[i] = 0.0f;
-  f4 gam[4], bet[4], b2v[4], w3v[4];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-    gam[nt] = *(const f4*)(p.gamma + 16 * nt + 4 * g); bet[nt] = *(const f4*)(p.beta + 16 * nt + 4 * g);
-    b2v[nt] = *(const f4*)(p.b2 + 16 * nt + 4 * g); w3v[nt] = *(const f4*)(p.w3 + 16 * nt + 4 * g);
-  }
+  const HeadParams<false> par(p, g);
   __syncthreads();
 
   const long W = (long)gridDim.x * NW, w = (long)blockIdx.x * NW + wave;
   const long g0 = (q.b * w / W) * q.S, g1 = (q.b * (w + 1) / W) * q.S;      // whole samples: dbase[b] and dact[b] have one writer
 
-  f4 accW[4][4];                            // dW2[16 ntu + 4 g + r][16 ntk + j]
-  f4 ag[4], ab[4], aw3[4], ab2[4];
-  float ab3 = 0.0f, carry = 0.0f;
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-#pragma unroll
-    for (int b = 0; b < 4; ++b) accW[a][b] = f4{0, 0, 0, 0};
-    ag[a] = ab[a] = aw3[a] = ab2[a] = f4{0, 0, 0, 0};
-  }
+  HeadAcc A;
+  float carry = 0.0f;
 
   for (long gq = g0; gq < g1; gq += q.CG) {
     const int ng = (int)(g1 - gq < q.CG ? g1 - gq : q.CG), nr = ng * n;
@@ -211,53 +178,38 @@ k_shap_bwd(HeadArgs p, ShapArgs q, const float* __restrict__ dv, float* __restri
       const float dvr = valid ? dv[(size_t)gq * n + r] : 0.0f;
       const float rs = ln_stats(xh, p.eps);
       f4 xn[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const f4 y = xh[c] * gam[c] + bet[c];
-        xn[c] = f4{relu_nan(y.x), relu_nan(y.y), relu_nan(y.z), relu_nan(y.w)};
-      }
-      // ---- pre^T = W2 xn^T
+      ln_affine_relu(xh, par, xn);
+      // ---- pre^T = W2 xn^T (mm64_lds)
       f4 acc[4] = {f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}};
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         f4 wv[4];
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) wv[nt] = sW[(nt * 4 + c) * 64 + lane];
+        for (int nt = 0; nt < 4; ++nt) wv[nt] = H.sW[(nt * 4 + c) * 64 + lane];
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq)
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[nt][qq], xn[c][qq], acc[nt], 0, 0, 0);
       }
-      // ---- dpre = [pre > 0] dv w3 (in place of acc); dw3 += relu(pre) dv; db2 += dpre; db3 += dv
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const float pre = acc[nt][rr] + b2v[nt][rr];
-          const bool on = pre > 0.0f;
-          const float dp = on ? dvr * w3v[nt][rr] : 0.0f;
-          if (PG) { aw3[nt][rr] = fmaf(on ? pre : 0.0f, dvr, aw3[nt][rr]); ab2[nt][rr] += dp; }
-          acc[nt][rr] = dp;
-        }
-      if (PG && g == 0) ab3 += dvr;
-      // ---- dxn^T = W2^T dpre^T
+      dpre_step<PG>(acc, dvr, par, g, A);
+      // ---- dxn^T = W2^T dpre^T (mm64_lds)
       f4 dxn[4] = {f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}};
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         f4 wv[4];
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) wv[nt] = sWT[(nt * 4 + c) * 64 + lane];
+        for (int nt = 0; nt < 4; ++nt) wv[nt] = H.sWT[(nt * 4 + c) * 64 + lane];
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq)
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) dxn[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[nt][qq], acc[c][qq], dxn[nt], 0, 0, 0);
       }
-      // ---- dW2 += dpre^T xn: both operands through LDS into C layout
+      // ---- dW2 += dpre^T xn: both operands through LDS into C layout (dw2_step<false>)
       if (PG) {
         float* s0 = stage; float* s1 = stage + 16 * HS;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { *(f4*)(s0 + j * HS + 16 * c + 4 * g) = acc[c]; *(f4*)(s1 + j * HS + 16 * c + 4 * g) = xn[c]; }
-        shap_wave_sync();
+        stage_store(s0, j, g, acc);
+        stage_store(s1, j, g, xn);
+        wave_sync();
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           float dC[4], xC[4];
@@ -266,32 +218,14 @@ k_shap_bwd(HeadArgs p, ShapArgs q, const float* __restrict__ dv, float* __restri
 #pragma unroll
           for (int a = 0; a < 4; ++a)
 #pragma unroll
-            for (int b = 0; b < 4; ++b) accW[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(dC[a], xC[b], accW[a][b], 0, 0, 0);
+            for (int b = 0; b < 4; ++b) A.accW[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(dC[a], xC[b], A.accW[a][b], 0, 0, 0);
         }
-        shap_wave_sync();                      // (the next tile's staging writes come after these reads)
+        wave_sync();                         // (the next tile's staging writes come after these reads)
       }
-      // ---- LayerNorm backward on the lane's row
-      float s1a = 0.0f, s2a = 0.0f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        f4 d;
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) d[qq] = xn[c][qq] > 0.0f ? dxn[c][qq] : 0.0f;
-        if (PG) { ag[c] += d * xh[c]; ab[c] += d; }
-        const f4 a = d * gam[c];
-        s1a += hsum(a); s2a += hsum(a * xh[c]);
-        dxn[c] = a;
-      }
-      const float m1 = sum_g(s1a) * (1.0f / 64.0f), m2 = sum_g(s2a) * (1.0f / 64.0f);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) dxn[c] = (dxn[c] - m1 - xh[c] * m2) * rs;
+      ln_backward<PG>(xn, xh, rs, par, dxn, A);
       // ---- hand dx over: the own-slot dot for dact; dx over the row's own P slot (position order) for the group walks
       if (dact) {
-        const float* pw = q.act_cols + (size_t)L.posS[valid ? r : nr - 1] * 64 + 4 * g;
-        float d = 0.0f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) d += hsum(dxn[c] * *(const f4*)(pw + 16 * c));
-        d = sum_g(d);
+        const float d = dx_dot(dxn, q.act_cols + (size_t)L.posS[valid ? r : nr - 1] * 64 + 4 * g);
         if (g == 0 && valid) L.valS[r] = d;
       }
       if (PG && valid) {
@@ -300,7 +234,7 @@ k_shap_bwd(HeadArgs p, ShapArgs q, const float* __restrict__ dv, float* __restri
         for (int c = 0; c < 4; ++c) *(f4*)(pp + 16 * c) = dxn[c];
       }
     }
-    shap_wave_sync();
+    wave_sync();
     if (PG) {
       // lane = column; positions from the last to the first: suffix sum for dact_cols, did_cols by agent, dbase over the sample
       for (int grp = 0; grp < ng; ++grp) {
@@ -321,47 +255,15 @@ k_shap_bwd(HeadArgs p, ShapArgs q, const float* __restrict__ dv, float* __restri
       }
     }
     if (dact) shap_sum_draws(q, L, n, gq, ng, lane, 1.0f, dact);
-    shap_wave_sync();
+    wave_sync();
   }
 
-  // ---- partial sums: the wavefronts of a workgroup are summed here through LDS in a fixed order (as k_head_bwd)
+  // ---- one partial block per workgroup: [0, HW) the trunk's parameter gradients | pad | [HP, ..) did_cols | dact_cols
   if (PG) {
     float* pp = partial + (size_t)blockIdx.x * pstride;
-    __syncthreads();
-    const float* a0 = sP + 256 + 2 * 16 * HS + (size_t)(q.CG * n) * 68 + n;       // wavefront 0's accI
-    for (int i = tid; i < 2 * n * 64; i += NT) {
-      float t = a0[i];
-#pragma unroll
-      for (int ww = 1; ww < NW; ++ww) t += a0[(size_t)ww * wfl + i];
-      pp[HP + i] = t;
-    }
-    __syncthreads();
-    float* red = sm + (size_t)wave * HP;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) red[(16 * a + 4 * g + rr) * 64 + 16 * b + j] = accW[a][b][rr];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {
-        const float tg = sum_j(ag[c][qq]), tb = sum_j(ab[c][qq]), t2 = sum_j(ab2[c][qq]), t3 = sum_j(aw3[c][qq]);
-        if (j == 0) {
-          const int col = 16 * c + 4 * g + qq;
-          red[4096 + col] = tg; red[4160 + col] = tb; red[4224 + col] = t2; red[4288 + col] = t3;
-        }
-      }
-    const float t = sum_j(ab3);
-    if (lane == 0) { red[4352] = t; red[4353] = 0.0f; }
-    __syncthreads();
-    for (int col = tid; col < HW; col += NT) {
-      float vv = sm[col];
-#pragma unroll
-      for (int ww = 1; ww < NW; ++ww) vv += sm[(size_t)ww * HP + col];
-      pp[col] = vv;
-    }
+    const float* a0 = H.rest + 2 * 16 * HS + (size_t)(q.CG * n) * 68 + n;       // wavefront 0's accI
+    wave_blocks_sum<NT>(a0, (size_t)wfl, 2 * n * 64, pp + HP, tid);
+    head_partials<NT, HP>(sm, pp, A, nullptr, tid);
   }
 }
 
@@ -449,7 +351,7 @@ extern "C" int mapdn_critic_shapley_forward(const float* base, const float* id_c
     return MAPDN_E_INVALID;
   const size_t lds = shap_fwd_lds(n);
   if (lds > SHAP_LDS_BUDGET || !shap_pos_ok(pos, b * S, n)) return MAPDN_E_INVALID;
-  const HeadArgs a{base, id_cols, n, gamma, beta, eps, w2, b2, w3, b3};
+  const HeadArgs a = head_args(base, id_cols, n, gamma, beta, eps, w2, b2, w3, b3);
   const ShapArgs q{id_cols, act_cols, act, pos, S, shap_cg(n), (long)b};
   if (hipFuncSetAttribute((const void*)k_shap_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SHAP_LDS_BUDGET) != hipSuccess) return MAPDN_E_HIP;
   hipLaunchKernelGGL(k_shap_fwd, dim3(shap_blocks(b, 4, 2)), dim3(256), lds, (hipStream_t)stream, a, q, v, phi);
@@ -483,7 +385,7 @@ extern "C" int mapdn_critic_shapley_backward(const float* dv, const float* base,
   if (param_grads ? (!shap_al16(dbase) || !shap_al4(grads) || !shap_al4(scratch)) : !dact) return MAPDN_E_INVALID;
   const int nt = shap_bwd_threads(n, param_grads != 0);
   if (!nt || !shap_pos_ok(pos, b * S, n)) return MAPDN_E_INVALID;
-  const HeadArgs a{base, id_cols, n, gamma, beta, eps, w2, b2, w3, b3};
+  const HeadArgs a = head_args(base, id_cols, n, gamma, beta, eps, w2, b2, w3, b3);
   const ShapArgs q{id_cols, act_cols, act, pos, S, shap_cg(n), (long)b};
   hipStream_t st = (hipStream_t)stream;
   if (param_grads) {

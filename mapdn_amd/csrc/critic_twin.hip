@@ -1,4 +1,6 @@
-// critic_twin.hip — MATD3's twin critic head as ONE launch, gfx950 (MI355X).  Compiled inside critic.hip (its helpers and layouts).
+// critic_twin.hip — MATD3's twin critic head as ONE launch, gfx950 (MI355X).  Compiled inside critic.hip (its layouts and load_row; the
+// trunk's steps are those of headtile.hpp: this file has what the twin adds — the second row, min(v1, v2), the two heads' dx summed;
+// k_twin_mse spells one step out itself, its LayerNorm backward, see there).
 //
 // Reference: models/matd3.py:35-86 — ONE MLPCritic values the MADDPG input twice, with one more input column that is 0 (values1) or 1
 // (values2).  Behind the first layer that is the single head of critic.hip on two rows that differ by a constant:
@@ -8,7 +10,7 @@
 // forward, LDS in the loss kernel): one read of base / per_n, one operand load, and what leaves the kernel is already combined —
 // min(v1, v2) for the target (matd3.py:141-142), dbase / dper_n / the parameter gradients summed over both heads for the loss
 // (matd3.py:143-150), d flag_col = the second head's dx summed over all rows.  Layouts, tiles, the per-wavefront [n][64] LDS
-// accumulator, the partial-and-reduce scheme and the pad rule are those of k_head_fwd / k_head_bwd<true, 3, 256>.
+// accumulator, the partial-and-reduce scheme and the pad rule are those of k_head_fwd / k_head_bwd<true, 3, 256>: the same calls but for that one step.
 
 namespace mapdn {
 
@@ -19,15 +21,11 @@ constexpr int TP = HP + 64;            // floats of a twin partial / grads block
 __global__ void __launch_bounds__(256)
 k_twin_fwd(HeadArgs p, const float* __restrict__ flag, float* __restrict__ v1, float* __restrict__ v2, float* __restrict__ vmin, long rows) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, j = lane & 15;
-  f4 wop[4][4], gam[4], bet[4], b2v[4], w3v[4], flg[4];
+  f4 wop[4][4], flg[4];
+  load_w2_operand(p.w2, j, g, wop);
+  const HeadParams<false> par(p, g);
 #pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) wop[nt][c] = *(const f4*)(p.w2 + (size_t)(16 * nt + j) * 64 + 16 * c + 4 * g);
-    gam[nt] = *(const f4*)(p.gamma + 16 * nt + 4 * g); bet[nt] = *(const f4*)(p.beta + 16 * nt + 4 * g);
-    b2v[nt] = *(const f4*)(p.b2 + 16 * nt + 4 * g); w3v[nt] = *(const f4*)(p.w3 + 16 * nt + 4 * g);
-    flg[nt] = *(const f4*)(flag + 16 * nt + 4 * g);
-  }
+  for (int c = 0; c < 4; ++c) flg[c] = *(const f4*)(flag + 16 * c + 4 * g);
   const float b3 = p.b3[0];
   const long n_tiles = (rows + 15) >> 4;
   for (long T = (long)blockIdx.x * 4 + wave; T < n_tiles; T += (long)gridDim.x * 4) {
@@ -40,25 +38,7 @@ k_twin_fwd(HeadArgs p, const float* __restrict__ flag, float* __restrict__ v1, f
       f4 xa[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) xa[c] = h ? xb[c] + flg[c] : xb[c];
-      ln_stats(xa, p.eps);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const f4 y = xa[c] * gam[c] + bet[c];
-        xa[c] = f4{relu_nan(y.x), relu_nan(y.y), relu_nan(y.z), relu_nan(y.w)};
-      }
-      f4 acc[4] = {f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}};
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wop[nt][c][q], xa[c][q], acc[nt], 0, 0, 0);
-      float dot = 0.0f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dot = fmaf(relu_nan(acc[nt][r] + b2v[nt][r]), w3v[nt][r], dot);
-      vh[h] = sum_g(dot) + b3;
+      vh[h] = head_value(xa, p.eps, wop, par) + b3;
     }
     if (g == 0 && row < rows) {
       if (v1) v1[row] = vh[0];
@@ -77,46 +57,24 @@ k_twin_mse(HeadArgs p, const float* __restrict__ flag, const float* __restrict__
            int pstride, long rows, const float* __restrict__ wrow, const float* __restrict__ scale) {
   constexpr int NT = 256, NW = NT / 64, TILES = 2;          // one wavefront per SIMD; two staging tiles per wavefront
   extern __shared__ float sm[];
-  f4* sW = (f4*)sm;                         // as k_head_bwd: W2 / W2^T operands, gamma | beta | b2 | w3, staging tiles, [n][64] accumulators
-  f4* sWT = sW + 1024;
-  float* sP = (float*)(sWT + 1024);
-  float* stage = sP + 256 + (size_t)(threadIdx.x >> 6) * TILES * 16 * HS;
-  float* accn = sP + 256 + (size_t)NW * TILES * 16 * HS + (size_t)(threadIdx.x >> 6) * p.n * 64;
+  const HeadLds L(sm);                      // then, as k_head_bwd: staging tiles, [n][64] accumulators
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, j = lane & 15;
-  if (tid < 64) { sP[tid] = p.gamma[tid]; sP[64 + tid] = p.beta[tid]; sP[128 + tid] = p.b2[tid]; sP[192 + tid] = p.w3[tid]; }
-  for (int i = tid; i < 1024; i += NT) {
-    const int l = i & 63, c = (i >> 6) & 3, nt = i >> 8, lj = l & 15, lg = l >> 4;
-    sW[i] = *(const f4*)(p.w2 + (size_t)(16 * nt + lj) * 64 + 16 * c + 4 * lg);
-    f4 t;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) t[q] = p.w2[(size_t)(16 * c + 4 * lg + q) * 64 + 16 * nt + lj];
-    sWT[i] = t;
-  }
+  float* stage = L.rest + (size_t)wave * TILES * 16 * HS;
+  float* accn0 = L.rest + (size_t)NW * TILES * 16 * HS, *accn = accn0 + (size_t)wave * p.n * 64;
+  L.fill(p, tid, NT);
   for (int i = lane; i < p.n * 64; i += 64) accn[i] = 0.0f;
-  f4 gam[4], bet[4], b2v[4], w3v[4], flg[4];
+  const HeadParams<false> par(p, g);
+  f4 flg[4];
 #pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-    gam[nt] = *(const f4*)(p.gamma + 16 * nt + 4 * g); bet[nt] = *(const f4*)(p.beta + 16 * nt + 4 * g);
-    b2v[nt] = *(const f4*)(p.b2 + 16 * nt + 4 * g); w3v[nt] = *(const f4*)(p.w3 + 16 * nt + 4 * g);
-    flg[nt] = *(const f4*)(flag + 16 * nt + 4 * g);
-  }
+  for (int c = 0; c < 4; ++c) flg[c] = *(const f4*)(flag + 16 * c + 4 * g);
   __syncthreads();
-
   // this wavefront's range of rows [r0, r1): whole groups of n
   const long W = (long)gridDim.x * NW, w = (long)blockIdx.x * NW + wave;
   const long G = rows / p.n, r0 = (G * w / W) * p.n, r1 = (G * (w + 1) / W) * p.n;
-
-  f4 accW[4][4];                            // dW2[16 ntu + 4 g + r][16 ntk + j], both heads
-  f4 ag[4], ab[4], aw3[4], ab2[4], af[4];   // column sums in A layout: dgamma, dbeta, dw3, db2 (both heads), d flag_col (second head's dx)
-  float ab3 = 0.0f, carry = 0.0f, aloss = 0.0f;
+  HeadAcc A;                                // both heads
+  f4 af[4] = {f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}};      // d flag_col in A layout: the second head's dx
+  float carry = 0.0f;
   const float b3 = p.b3[0], lscale = 0.5f * scale[0];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-#pragma unroll
-    for (int b = 0; b < 4; ++b) accW[a][b] = f4{0, 0, 0, 0};
-    ag[a] = ab[a] = aw3[a] = ab2[a] = af[a] = f4{0, 0, 0, 0};
-  }
-
   f4 xnext[4];
   float rtnext = 0.0f;
   if (r0 < r1) {
@@ -137,7 +95,7 @@ k_twin_mse(HeadArgs p, const float* __restrict__ flag, const float* __restrict__
       load_row<true>(p, rn < r1 ? rn : r1 - 1, g, xnext);
       rtnext = rn < r1 ? ret[rn] : 0.0f;
     }
-    float wgt = lscale;
+    float wgt = lscale;                      // w = 1/2 scale wrow for both heads
     if (wrow) wgt *= wrow[(unsigned)(valid ? row : r1 - 1) / (unsigned)p.n];
     f4 dxs[4] = {f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}};      // dx of the tile's rows, summed over the two heads
 #pragma nounroll
@@ -146,93 +104,23 @@ k_twin_mse(HeadArgs p, const float* __restrict__ flag, const float* __restrict__
 #pragma unroll
       for (int c = 0; c < 4; ++c) xh[c] = h ? xb[c] + flg[c] : xb[c];
       const float rs = ln_stats(xh, p.eps);
-      f4 xn[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const f4 y = xh[c] * gam[c] + bet[c];
-        xn[c] = f4{relu_nan(y.x), relu_nan(y.y), relu_nan(y.z), relu_nan(y.w)};
-      }
-      // ---- pre^T = W2 xn^T
-      f4 acc[4] = {f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        f4 wv[4];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) wv[nt] = sW[(nt * 4 + c) * 64 + lane];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[nt][q], xn[c][q], acc[nt], 0, 0, 0);
-      }
-      // ---- v_h, its error against the shared returns, dv_h = -2 w (ret - v_h) with w = 1/2 scale wrow
-      float dot = 0.0f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        const f4 bb = b2v[nt], ww = w3v[nt];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dot = fmaf(relu_nan(acc[nt][r] + bb[r]), ww[r], dot);
-      }
-      const float err = rt - (sum_g(dot) + b3);
-      const float dvr = valid ? -2.0f * wgt * err : 0.0f;
-      if (valid && g == 0) aloss = fmaf(wgt * err, err, aloss);
-      // ---- dpre = [pre > 0] dv w3 (in place of acc); dw3 += relu(pre) dv; db2 += dpre; db3 += dv
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        const f4 bb = b2v[nt], ww = w3v[nt];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pre = acc[nt][r] + bb[r];
-          const bool pos = pre > 0.0f;
-          const float dp = pos ? dvr * ww[r] : 0.0f;
-          aw3[nt][r] = fmaf(pos ? pre : 0.0f, dvr, aw3[nt][r]); ab2[nt][r] += dp;
-          acc[nt][r] = dp;
-        }
-      }
-      if (g == 0) ab3 += dvr;
-      // ---- dxn^T = W2^T dpre^T
-      f4 dxn[4] = {f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}, f4{0, 0, 0, 0}};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        f4 wv[4];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) wv[nt] = sWT[(nt * 4 + c) * 64 + lane];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) dxn[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[nt][q], acc[c][q], dxn[nt], 0, 0, 0);
-      }
-      // ---- dW2 += dpre^T xn: both operands through LDS into C layout (rows on the contraction axis)
-      {
-        float* s0 = stage; float* s1 = stage + 16 * HS;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) *(f4*)(s0 + j * HS + 16 * c + 4 * g) = acc[c];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) *(f4*)(s1 + j * HS + 16 * c + 4 * g) = xn[c];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          float dC[4], xC[4];
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) { dC[nt] = s0[(4 * g + s) * HS + 16 * nt + j]; xC[nt] = s1[(4 * g + s) * HS + 16 * nt + j]; }
-#pragma unroll
-          for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) accW[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(dC[a], xC[b], accW[a][b], 0, 0, 0);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();          // (the staging tiles are free for the second head / the hand-over)
-      }
-      // ---- LayerNorm backward on the lane's row
+      f4 xn[4], acc[4], dxn[4];
+      ln_affine_relu(xh, par, xn);
+      mm64_lds(L.sW, lane, xn, acc);         // pre^T = W2 xn^T
+      const float dvr = mse_dv(acc, par, b3, rt, wgt, valid, g, A.aloss);      // v_h against the shared returns
+      dpre_step<true>(acc, dvr, par, g, A);
+      mm64_lds(L.sWT, lane, acc, dxn);       // dxn^T = W2^T dpre^T
+      dw2_step<false>(stage, j, g, acc, xn, A.accW);
+      wave_release();                        // (the staging tiles are free for the second head / the hand-over)
+      // ---- LayerNorm backward, spelt out: through ln_backward() the compiler scalarises it into the dW2 products (6.89 ms against 6.70)
       float s1a = 0.0f, s2a = 0.0f;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         f4 d;
 #pragma unroll
         for (int q = 0; q < 4; ++q) d[q] = xn[c][q] > 0.0f ? dxn[c][q] : 0.0f;
-        ag[c] += d * xh[c]; ab[c] += d;
-        const f4 a = d * gam[c];
+        A.ag[c] += d * xh[c]; A.ab[c] += d;
+        const f4 a = d * par.gamma(c);
         s1a += hsum(a); s2a += hsum(a * xh[c]);
         dxn[c] = a;
       }
@@ -244,95 +132,12 @@ k_twin_mse(HeadArgs p, const float* __restrict__ flag, const float* __restrict__
         dxs[c] += d;
       }
     }
-    // ---- hand the summed dx over: dbase[group] = sum over the group's n rows, dper_n[i] += dx — lane = column, the tile's rows in order
-    {
-      float* s0 = stage;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) *(f4*)(s0 + j * HS + 16 * c + 4 * g) = dxs[c];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const int cnt = (int)(r1 - row0 < 16 ? r1 - row0 : 16);
-      const unsigned rel = (unsigned)(row0 - r0);
-      unsigned grp = rel / (unsigned)p.n, i = rel - grp * (unsigned)p.n;
-      float* pbase = dx + ((size_t)(r0 / p.n) + grp) * 64 + lane;
-      if (p.n >= 16) {
-        unsigned i2 = i;
-        constexpr int H = 16;      // rows in flight: the tile's rows belong to different agents, their slots are independent
-#pragma unroll
-        for (int h0 = 0; h0 < 16; h0 += H) {
-          float val[H], cur[H];
-#pragma unroll
-          for (int rr = 0; rr < H; ++rr) {
-            unsigned ii = i + h0 + rr; if (ii >= (unsigned)p.n) ii -= p.n;
-            val[rr] = h0 + rr < cnt ? s0[(h0 + rr) * HS + lane] : 0.0f;
-            cur[rr] = accn[ii * 64 + lane];
-          }
-#pragma unroll
-          for (int rr = 0; rr < H; ++rr) {
-            unsigned ii = i + h0 + rr; if (ii >= (unsigned)p.n) ii -= p.n;
-            accn[ii * 64 + lane] = cur[rr] + val[rr];
-          }
-#pragma unroll
-          for (int rr = 0; rr < H; ++rr)
-            if (h0 + rr < cnt) {
-              carry += val[rr];
-              if (++i2 == (unsigned)p.n) { *pbase = carry; carry = 0.0f; i2 = 0; pbase += 64; }
-            }
-        }
-      } else {
-        for (int rr = 0; rr < cnt; ++rr) {
-          const float val = s0[rr * HS + lane];
-          carry += val;
-          accn[i * 64 + lane] += val;
-          if (++i == (unsigned)p.n) { *pbase = carry; carry = 0.0f; i = 0; pbase += 64; }
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
+    formed_handover<16>(stage, accn, dx, dxs, carry, p.n, r0, r1, row0, lane, j, g);
   }
-
-  // ---- partial sums of the workgroup, through LDS in a fixed order (as k_head_bwd; TP floats per wavefront)
+  // ---- one partial block per workgroup (as k_head_bwd, TP floats per wavefront in LDS)
   float* pp = partial + (size_t)blockIdx.x * pstride;
-  __syncthreads();
-  {
-    const float* a0 = sP + 256 + (size_t)NW * TILES * 16 * HS;
-    for (int i = tid; i < p.n * 64; i += NT) {
-      float t = a0[i];
-#pragma unroll
-      for (int ww = 1; ww < NW; ++ww) t += a0[(size_t)ww * p.n * 64 + i];
-      pp[TP + i] = t;
-    }
-  }
-  __syncthreads();
-  float* red = sm + (size_t)wave * TP;
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[(16 * a + 4 * g + r) * 64 + 16 * b + j] = accW[a][b][r];
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float tg = sum_j(ag[c][q]), tb = sum_j(ab[c][q]), t2 = sum_j(ab2[c][q]), t3 = sum_j(aw3[c][q]), tf = sum_j(af[c][q]);
-      if (j == 0) {
-        const int col = 16 * c + 4 * g + q;
-        red[4096 + col] = tg; red[4160 + col] = tb; red[4224 + col] = t2; red[4288 + col] = t3; red[HP + col] = tf;
-      }
-    }
-  const float t = sum_j(ab3), tl = sum_j(aloss);
-  if (lane == 0) { red[4352] = t; red[4353] = tl; }
-  __syncthreads();
-  for (int col = tid; col < TP; col += NT) {
-    if (col >= HW && col < HP) continue;      // pad: neither read nor written
-    float v = sm[col];
-#pragma unroll
-    for (int ww = 1; ww < NW; ++ww) v += sm[(size_t)ww * TP + col];
-    pp[col] = v;
-  }
+  wave_blocks_sum<NT>(accn0, (size_t)p.n * 64, p.n * 64, pp + TP, tid);
+  head_partials<NT, TP>(sm, pp, A, af, tid);
 }
 
 }  // namespace mapdn
@@ -354,9 +159,8 @@ extern "C" int mapdn_critic_twin_forward(const float* base, const float* per_n, 
                                          float* v1, float* v2, float* vmin, int64_t rows, void* stream) {
   using namespace mapdn;
   if (!twin_args_ok(base, per_n, n, flag_col, gamma, beta, w2, b2, w3, b3, rows) || (!v1 && !v2 && !vmin)) return MAPDN_E_INVALID;
-  const HeadArgs a{base, per_n, n, gamma, beta, eps, w2, b2, w3, b3};
-  const int64_t tiles = (rows + 15) / 16;
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, (int64_t)head_cus() * 2));
+  const HeadArgs a = head_args(base, per_n, n, gamma, beta, eps, w2, b2, w3, b3);
+  const int blocks = head_fwd_blocks(rows);
   hipLaunchKernelGGL(k_twin_fwd, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, flag_col, v1, v2, vmin, (long)rows);
   return hipGetLastError() == hipSuccess ? MAPDN_OK : MAPDN_E_HIP;
 }
@@ -384,7 +188,7 @@ extern "C" int mapdn_critic_twin_mse(const float* ret, const float* wrow, const 
   using namespace mapdn;
   if (!twin_args_ok(base, per_n, n, flag_col, gamma, beta, w2, b2, w3, b3, rows) || !ret || !scale || !dbase || !grads || !scratch)
     return MAPDN_E_INVALID;
-  const HeadArgs a{base, per_n, n, gamma, beta, eps, w2, b2, w3, b3};
+  const HeadArgs a = head_args(base, per_n, n, gamma, beta, eps, w2, b2, w3, b3);
   hipStream_t st = (hipStream_t)stream;
   const int blocks = head_bwd_blocks(rows, n, true, TWIN_MSE_THREADS / 64), pstride = TP + n * 64;
   const size_t lds = twin_mse_lds(n);

@@ -1,6 +1,7 @@
 // rowtile.hpp — lane-level helpers shared by the learner's MFMA kernels (critic.hip, policy_bwd.hip): a tile of 16 rows of 64 features
 // in "A layout" (lane l = (j = l & 15, g = l >> 4) holds row j, features 16 c + 4 g + q), reductions over the four lanes of a row and
-// over the 16 lanes of a DPP row, LayerNorm statistics.
+// over the 16 lanes of a DPP row, LayerNorm statistics, the wavefront-level LDS fence (wave_sync / wave_release).  The critic head's
+// trunk on such a tile is built from these in headtile.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -41,6 +42,17 @@ __device__ __forceinline__ float hsum(f4 v) { return (v.x + v.y) + (v.z + v.w); 
 // the gate arithmetic was 45 % of the policy kernels' VALU instructions, and those bound them (SQ counters, profiles/r06_*)
 __device__ __forceinline__ float fast_sigmoid(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 __device__ __forceinline__ float fast_tanh(float v) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * v) + 1.0f); }
+
+// LDS hand-over inside one wavefront: what the lanes stored before is visible to what they load after.  wave_release() is the first
+// half alone: enough where the later accesses are stores (loads done before a tile is overwritten)
+__device__ __forceinline__ void wave_release() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+__device__ __forceinline__ void wave_sync() {
+  wave_release();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // LayerNorm statistics of the lane's row; xa becomes xhat = (x - mean) rstd
 __device__ __forceinline__ float ln_stats(f4 (&xa)[4], float eps) {

@@ -30,7 +30,7 @@ gam, bet, w2, b2, w3, b3 = 1 + r(64, k=0.3), r(64, k=0.2), r(64, 64, k=0.2), r(6
 st = torch.cuda.current_stream(dev).cuda_stream
 P = [t.data_ptr() for t in (gam, bet, w2, b2, w3, b3)]
 eps = 1e-5
-base_k, v0_k, base_l, v0_l, v, xs = (torch.empty(rows, device=dev) for _ in range(5)) + (torch.empty(rows, 64, device=dev),)
+base_k, v0_k, base_l, v0_l, v, xs = tuple(torch.empty(rows, device=dev) for _ in range(5)) + (torch.empty(rows, 64, device=dev),)
 x3, xs3, col3, d4 = x.view(nb, n, 64), xs.view(nb, n, 64), col.view(1, n, 64), delta.view(S, nb, n, 1)
 
 
