@@ -5,7 +5,7 @@
     netspec.py    NetSpec / Profiles (the pandapower columns and CSV tables the path reads), synthetic cases
     data.py       on-disk formats (reference CSV layout, netspec.npz, scenario directories)
     sharding.py   env-batch sharding over GPUs, end-of-rollout gather
-    rollout.py, replay.py, learner.py, tester.py   the callers either side of the path
+    rollout.py, replay.py, learner/, tester.py   the callers either side of the path
 
 Nothing here imports torch or loads the shared library at package-import time; there is no CPU fallback.
 """

@@ -1,4 +1,4 @@
-"""COMA learner (mapdn_amd/learner.py, alg="coma") against fixtures produced by the reference's own code
+"""COMA learner (mapdn_amd/learner/coma.py) against fixtures produced by the reference's own code
 (tests/golden/make_coma_golden.py): forward passes, value(), d value / d action, both losses, the stats and every entry of the state_dict
 after two value steps, one policy step and one soft target update, strict state_dict round trip — with the bars tests/test_matd3.py holds
 the same quantities to.  The reference draws the counterfactual actions inside get_loss; the fixtures carry the seed set before each call

@@ -1,5 +1,5 @@
 """Every row of the learner kernel matrix (tests/learner_kernel_matrix.py) on the GPU, through the C ABI, against the PyTorch modules of
-mapdn_amd/learner.py (RNNAgent, MLPCritic) deep-copied to float64.
+mapdn_amd/learner/modules.py (RNNAgent, MLPCritic) deep-copied to float64.
 
 Bars.  means: 5e-6 x max(1, max |ref|), the bar tests/test_policy_trunk.py holds against float64.  hid_out / x1_out: the error of the stock
 f32 modules against float64 on the same inputs is measured, the kernel may have 8 x that (its gates carry ~1e-7 absolute error where

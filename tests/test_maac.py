@@ -1,4 +1,4 @@
-"""MAAC learner (mapdn_amd/learner.py, alg="maac") against fixtures produced by the reference's own code
+"""MAAC learner (mapdn_amd/learner/maac.py) against fixtures produced by the reference's own code
 (tests/golden/make_maac_golden.py): forward passes, value() with its regulariser row, d value / d action, both losses, the stats and every
 entry of the state_dict after one value step, one policy step and one soft target update, strict state_dict round trip — with the bars
 tests/test_coma.py holds the same quantities to.  The reference draws twice inside get_loss; the fixtures carry the seed set before each
@@ -207,12 +207,12 @@ def test_value_is_the_reference_loop_through_the_modules():
     net = tr.behaviour_net.double()
     obs, act = b["state"].double(), b["action"].double()
     want = net.value(obs, act)
-    real = learner.attention_core
-    learner.attention_core = learner.attention_loop_reference
+    real = learner.maac.attention_core                   # (patched in the module AttentionCritic.forward looks it up in)
+    learner.maac.attention_core = learner.attention_loop_reference
     try:
         got = net.value(obs, act)
     finally:
-        learner.attention_core = real
+        learner.maac.attention_core = real
     assert float((got - want).abs().max()) <= 1e-12
 
 

@@ -1,4 +1,4 @@
-"""MATD3 learner (mapdn_amd/learner.py, alg="matd3") against fixtures produced by the reference's own code
+"""MATD3 learner (mapdn_amd/learner/ddpg.py, alg="matd3") against fixtures produced by the reference's own code
 (tests/golden/make_matd3_golden.py): forward passes (value() is [2b, n, 1]), both losses, every entry of the state_dict after two value
 steps, one policy step and one soft target update, strict state_dict round trip — with the bars tests/test_learner.py holds the other
 two algorithms to.  The reference draws the target-smoothing noise inside get_loss; the fixtures carry the seed set before each call and

@@ -1,5 +1,5 @@
 """The policy update's agent trunk as HIP launches (round 6; csrc/policy.hip: mapdn_policy_forward_train, csrc/policy_bwd.hip:
-mapdn_policy_backward; learner.py::_PolicyTrunk): fc1 + id column -> LayerNorm -> ReLU -> GRUCell -> fc2 of agents/rnn_agent.py:5-32 as
+mapdn_policy_backward; learner/modules.py::_PolicyTrunk): fc1 + id column -> LayerNorm -> ReLU -> GRUCell -> fc2 of agents/rnn_agent.py:5-32 as
 trained by models/maddpg.py:103-125 — means and the gradient of every policy parameter against the PyTorch modules in float64."""
 import copy
 

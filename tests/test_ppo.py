@@ -1,4 +1,4 @@
-"""MAPPO / IPPO learners (mapdn_amd/learner.py, alg="mappo" / "ippo") against fixtures produced by the reference's own code
+"""MAPPO / IPPO learners (mapdn_amd/learner/ppo.py) against fixtures produced by the reference's own code
 (tests/golden/make_ppo_golden.py): forward passes, value(), both losses, the stats and every entry of the state_dict after two value steps,
 one policy step and one soft target update, strict state_dict round trip — with the bars tests/test_coma.py holds the same quantities to
 (tests/test_matd3.py's).  Then what is this project's own: the refusals, ppo_old_log_prob="stored" against a hand-written ratio, the GAE

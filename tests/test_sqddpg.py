@@ -1,4 +1,4 @@
-"""SQDDPG learner (mapdn_amd/learner.py, alg="sqddpg") against fixtures produced by the reference's own code
+"""SQDDPG learner (mapdn_amd/learner/sqddpg.py) against fixtures produced by the reference's own code
 (tests/golden/make_sqddpg_golden.py): forward passes, value(), d value / d action, both losses, the stats and every entry of the state_dict
 after two value steps, one policy step and one soft target update, strict state_dict round trip — with the bars tests/test_coma.py holds
 the same quantities to.  The reference draws its coalition orders inside every marginal_contribution call; the fixtures carry the seed
