@@ -1211,85 +1211,13 @@ int mapdn_nr_time_ms(mapdn_handle* h, double* total_ms, int64_t* launches) try {
   return MAPDN_OK;
 } MAPDN_CATCH(h)
 
-// ---- droop baseline (droop.hip): the script's defaults for the fields left 0, and its refusals
-static const char* droop_resolve(const mapdn_droop_config* in, mapdn_droop_config& c) {
-  if (in) c = *in; else std::memset(&c, 0, sizeof(c));
-  if (c.va == 0.0) c.va = 0.95;                  // pf_droop_matpower_all.m: the law's breakpoints, damping, stopping rule,
-  if (c.vb == 0.0) c.vb = 1.0;                   // reactive_ratio of q_max = min(sqrt(S^2 - p^2), ratio S)
-  if (c.vc == 0.0) c.vc = 1.0;
-  if (c.vd == 0.0) c.vd = 1.05;
-  if (c.damping == 0.0) c.damping = 0.1;
-  if (c.max_iter == 0) c.max_iter = 100;
-  if (c.v_tol == 0.0) c.v_tol = 1e-4;
-  if (c.reactive_ratio == 0.0) c.reactive_ratio = 1.0;
-  if (!(c.va < c.vb && c.vb <= c.vc && c.vc < c.vd)) return "droop: the breakpoints must satisfy va < vb <= vc < vd";
-  if (!(c.damping > 0.0 && c.damping <= 1.0)) return "droop: damping must lie in (0, 1]";
-  if (c.max_iter < 1 || c.max_iter > DROOP_MAX_ITER_CAP) return "droop: max_iter must lie in 1 ... 10000";
-  if (!(c.v_tol > 0.0)) return "droop: v_tol must be > 0";
-  if (!(c.reactive_ratio > 0.0)) return "droop: reactive_ratio must be > 0";
-  return nullptr;
-}
+}  // extern "C"
 
-// the workspace of the droop loop (DroopState), once per handle
-static int droop_prepare(mapdn_handle* h) {
-  if (h->droop_ready) return MAPDN_OK;
-  const Plan& P = h->plan;
-  DroopState& s = h->droop;
-  const size_t Bp = h->d.Bp, ns = (size_t)P.ns;
-  int32_t *iters = nullptr, *nr_iters = nullptr, *n_active = nullptr; uint8_t *status = nullptr, *act = nullptr, *nr_conv = nullptr;
-  int rc;
-  if ((rc = dalloc(h, &s.a, ns * Bp)) || (rc = dalloc(h, &s.a_sol, ns * Bp)) || (rc = dalloc(h, &s.v_last, ns * Bp)) ||
-      (rc = dalloc(h, &s.dv2, ns * Bp)) ||
-      (rc = dalloc(h, &iters, Bp)) || (rc = dalloc(h, &nr_iters, Bp)) || (rc = dalloc(h, &status, Bp)) || (rc = dalloc(h, &act, Bp)) ||
-      (rc = dalloc(h, &nr_conv, Bp)) || (rc = dalloc(h, &n_active, (size_t)DROOP_MAX_ITER_CAP + 1)))
-    return rc;
-  s.iters = iters; s.nr_iters = nr_iters; s.status = status; s.act = act; s.nr_conv = nr_conv; s.n_active = n_active;
-  std::vector<int32_t> vrow(std::max<size_t>(ns, 1), 0);           // |V| of sgen j's bus: the Vout row of its node (alloc_nrbuf)
-  for (size_t j = 0; j < ns; ++j) vrow[j] = (int32_t)h->d.r_vout + VOF * P.pos_of_obus[P.sgen_bus[j]] + VO_VM;
-  const int32_t* vr = nullptr;
-  if ((rc = dupload(h, &vr, vrow))) return rc;
-  s.sg_vrow = vr; s.vm_row = h->vm_row;
-  h->droop_ready = true;
-  return MAPDN_OK;
-}
+// The traditional baselines' host side — droop_resolve / droop_prepare / droop_run, opf_resolve / opf_prepare / opf_run / opf_probe and
+// the one loop driver they share — compiled inside this unit like ppo.hip and branch.hip; the entry points below check the arguments.
+#include "baselines_host.hpp"
 
-// The loop of pf_droop_matpower_all.m:84-162 for every env at once: the start launch, then per iteration the solve (MODE_SOLVE, with
-// the droop's own active set: envs that stopped are skipped) and k_droop_update.  The host reads the number of envs still iterating
-// every DROOP_POLL iterations only, so at most DROOP_POLL - 1 solves run after the last env stopped.  Writes only what the next
-// step() overwrites before it reads it: the PV-bus and several-load-bus entries of the Sbus buffer that solve reads (d.sb_off; all of
-// it when Sbus is stale after mapdn_solve_only, as the next step() rebuilds it then anyway) and the solver's Vout rows.
-static int droop_run(mapdn_handle* h, const mapdn_droop_config& c, double* actions, double* vm_pu, int32_t* iterations,
-                     uint8_t* status, hipStream_t st) {
-  constexpr int DROOP_POLL = 4;
-  if (const int rc = droop_prepare(h)) return rc;
-  const Dev& d = h->d;
-  DroopState s = h->droop;
-  s.va = c.va; s.vb = c.vb; s.vc = c.vc; s.vd = c.vd; s.damping = c.damping; s.v_tol = c.v_tol; s.ratio = c.reactive_ratio;
-  s.max_iter = c.max_iter; s.vm_out = vm_pu;
-  HIPCHK(h, hipMemsetAsync(s.n_active, 0, ((size_t)c.max_iter + 1) * sizeof(int32_t), st));
-  if (h->sbus_stale) {                           // Sbus holds mapdn_solve_only's inputs: rebuild it from the env's loads (q = 0)
-    HIPCHK(h, hipMemsetAsync(s.a, 0, (size_t)d.ns * d.Bp * sizeof(double), st));
-    launch_inject(d, MODE_SOLVE, nullptr, MAPDN_F64, d.cur_pl, d.cur_ql, d.cur_pv, s.a, 0, st);
-  }
-  launch_droop_update(d, s, 0, st);
-  Dev dd = d;
-  dd.active = s.act; dd.iters = const_cast<int32_t*>(s.nr_iters); dd.conv = const_cast<uint8_t*>(s.nr_conv);
-  for (int i = 0; i < c.max_iter; ++i) {         // i power flows solved so far
-    if (i % DROOP_POLL == 0) {
-      int32_t left = 0;
-      HIPCHK(h, hipMemcpyAsync(&left, s.n_active + i, sizeof(left), hipMemcpyDeviceToHost, st));
-      HIPCHK(h, hipStreamSynchronize(st));
-      if (left == 0) break;
-    }
-    nr_launch(h, MODE_SOLVE, nullptr, nullptr, nullptr, st, nullptr, 0, &dd);
-    launch_droop_update(d, s, i + 1, st);
-  }
-  transpose_out(h, s.a_sol, 1.0, h->iota_idx, actions, d.ns, st);
-  launch_copy_i32(s.iters, iterations, d.B, st);
-  launch_copy_u8(s.status, status, d.B, st);
-  HIPCHK(h, hipGetLastError());
-  return MAPDN_OK;
-}
+extern "C" {
 
 int mapdn_droop_actions(mapdn_handle* h, const mapdn_droop_config* cfg, double* actions, double* vm_pu, int32_t* iterations,
                         uint8_t* status, void* stream) try {
@@ -1302,123 +1230,6 @@ int mapdn_droop_actions(mapdn_handle* h, const mapdn_droop_config* cfg, double* 
   HIPCHK(h, hipSetDevice(h->device));
   return droop_run(h, c, actions, vm_pu, iterations, status, (hipStream_t)stream);
 } MAPDN_CATCH(h)
-
-// ---- OPF baseline (opf.hip, opf.hpp): the defaults for the fields left 0, the config's ranges and what the tree sweeps do not cover
-static const char* opf_resolve(const mapdn_handle* h, const mapdn_opf_config* in, mapdn_opf_config& c) {
-  if (in) c = *in; else std::memset(&c, 0, sizeof(c));
-  if (c.v_lower == 0.0) c.v_lower = h->cfg.v_lower;
-  if (c.v_upper == 0.0) c.v_upper = h->cfg.v_upper;
-  if (c.v_tol == 0.0) c.v_tol = 5e-6;             // MATPOWER's opf.violation
-  if (c.step_tol == 0.0) c.step_tol = 1e-6;
-  if (c.max_iter == 0) c.max_iter = 50;
-  if (c.max_backtrack == 0) c.max_backtrack = 8;
-  if (!(c.v_lower > 0.0 && c.v_lower < c.v_upper)) return "opf: the bounds must satisfy 0 < v_lower < v_upper";
-  if (!(c.v_tol > 0.0)) return "opf: v_tol must be > 0";
-  if (!(c.step_tol > 0.0)) return "opf: step_tol must be > 0";
-  if (c.max_iter < 1 || c.max_iter > OPF_MAX_ITER_CAP) return "opf: max_iter must lie in 1 ... 1000";
-  if (c.max_backtrack < 1 || c.max_backtrack > 60) return "opf: max_backtrack must lie in 1 ... 60";
-  const Plan& P = h->plan;
-  if (!P.radial || h->solver != 0) return "opf: meshed nets and handles on another solver than the tree solver are not supported";
-  if (P.zip) return "opf: voltage-dependent (ZIP) loads are not supported";
-  if (P.nbo != P.nb || !P.fused_obus.empty() || !P.alias_pos.empty()) return "opf: fused buses are not supported";
-  if (P.ns > OPF_MAX_NS) return "opf: more than 64 sgens are not supported";
-  return nullptr;
-}
-
-// the tables and the workspace of the OPF loop (OpfState), once per handle
-static int opf_prepare(mapdn_handle* h) {
-  if (h->opf_ready) return MAPDN_OK;
-  const Plan& P = h->plan;
-  OpfState& s = h->opf;
-  const size_t Bp = h->d.Bp, ns = (size_t)P.ns, n = (size_t)P.n;
-  // children of every node in the canonical order of the sweeps: the chain child k - 1 first, then ascending positions
-  std::vector<int32_t> cptr(n + 1, 0), cidx;
-  {
-    std::vector<std::vector<int32_t>> ch(n);
-    for (int k = 0; k < P.n; ++k) if (P.par[k] < P.n) ch[(size_t)P.par[k]].push_back(k);     // ascending k
-    for (size_t k = 0; k < n; ++k) {
-      auto& c = ch[k];
-      if (!c.empty() && c.back() == (int32_t)k - 1) { c.pop_back(); c.insert(c.begin(), (int32_t)k - 1); }
-      cidx.insert(cidx.end(), c.begin(), c.end());
-      cptr[k + 1] = (int32_t)cidx.size();
-    }
-  }
-  // Y constants of Plan::yc, then M = (Y + Y^H) / 2: M_k,parent and M_k,slack V_slack (Y_slack,k from root_children / root_y)
-  std::vector<double> yt(std::max<size_t>(n, 1) * OPF_YT, 0.0);
-  std::vector<cplx> ysk(n, cplx(0, 0));
-  for (size_t i = 0; i < P.root_children.size(); ++i) ysk[(size_t)P.root_children[i]] = cplx(P.root_y[2 * i], P.root_y[2 * i + 1]);
-  for (size_t k = 0; k < n; ++k) {
-    const double* c = &P.yc[k * 8];
-    double* y = &yt[k * OPF_YT];
-    for (int i = 0; i < 8; ++i) y[i] = c[i];
-    const cplx mkp = 0.5 * (cplx(c[2], c[3]) + std::conj(cplx(c[4], c[5])));
-    const cplx msv = 0.5 * (cplx(c[6], c[7]) + std::conj(ysk[k]) * P.vroot);
-    y[OY_MKP] = mkp.real(); y[OY_MKP + 1] = mkp.imag(); y[OY_MSV] = msv.real(); y[OY_MSV + 1] = msv.imag();
-  }
-  std::vector<int32_t> sgn(std::max<size_t>(ns, 1), 0), par(std::max<size_t>(n, 1), 0);
-  for (size_t j = 0; j < ns; ++j) sgn[j] = P.pos_of_obus[P.sgen_bus[j]];
-  for (size_t k = 0; k < n; ++k) par[k] = P.par[k];
-  int rc;
-  if ((rc = dupload(h, &s.par, par)) || (rc = dupload(h, &s.cptr, cptr)) || (rc = dupload(h, &s.cidx, cidx)) ||
-      (rc = dupload(h, &s.sg_node, sgn)) || (rc = dupload(h, &s.yt, yt)))
-    return rc;
-  s.loss_slack = P.yrr[0] * P.vroot * P.vroot;
-  s.vm_row = h->vm_row;
-  int32_t *nr_iters = nullptr; uint8_t* nr_conv = nullptr;
-  if ((rc = dalloc(h, &s.fac, n * OPF_FAC * Bp)) || (rc = dalloc(h, &s.mv, n * 2 * Bp)) || (rc = dalloc(h, &s.X, n * ns * 2 * Bp)) ||
-      (rc = dalloc(h, &s.W, n * ns * 2 * Bp)) || (rc = dalloc(h, &s.S, n * ns * Bp)) || (rc = dalloc(h, &s.H, ns * ns * Bp)) ||
-      (rc = dalloc(h, &s.g, ns * Bp)) || (rc = dalloc(h, &s.qd, ns * Bp)) || (rc = dalloc(h, &s.qy, (ns + n) * Bp)) ||
-      (rc = dalloc(h, &s.qw, opf_qp_work((int)ns, (int)n) * Bp)) || (rc = dalloc(h, &s.a, ns * Bp)) || (rc = dalloc(h, &s.a_sol, ns * Bp)) ||
-      (rc = dalloc(h, &s.t, Bp)) || (rc = dalloc(h, &s.loss, Bp)) || (rc = dalloc(h, &s.viol, Bp)) || (rc = dalloc(h, &s.loss_out, Bp)) ||
-      (rc = dalloc(h, &s.viol_out, Bp)) || (rc = dalloc(h, &s.iters, Bp)) || (rc = dalloc(h, &s.nback, Bp)) ||
-      (rc = dalloc(h, &s.status, Bp)) || (rc = dalloc(h, &s.act, Bp)) || (rc = dalloc(h, &s.lin, Bp)) ||
-      (rc = dalloc(h, &s.qp_capped, Bp)) || (rc = dalloc(h, &nr_iters, Bp)) || (rc = dalloc(h, &nr_conv, Bp)) ||
-      (rc = dalloc(h, &s.n_active, (size_t)OPF_MAX_ITER_CAP + 1)))
-    return rc;
-  s.nr_iters = nr_iters; s.nr_conv = nr_conv;
-  h->opf_ready = true;
-  return MAPDN_OK;
-}
-
-// The SQP loop for every env at once: the start launch, then per iteration the solve (MODE_SOLVE with the OPF's own active set: envs
-// that stopped are skipped), k_opf_linearise, k_opf_qp and k_opf_update.  The host reads the number of envs still iterating every
-// OPF_POLL iterations.  Like the droop loop it writes only what the next step() overwrites before it reads it.
-static int opf_run(mapdn_handle* h, const mapdn_opf_config& c, double* actions, double* vm_pu, double* loss_mw, double* violation,
-                   int32_t* iterations, uint8_t* status, hipStream_t st) {
-  constexpr int OPF_POLL = 2;
-  if (const int rc = opf_prepare(h)) return rc;
-  const Dev& d = h->d;
-  OpfState s = h->opf;
-  s.v_lower = c.v_lower; s.v_upper = c.v_upper; s.v_tol = c.v_tol; s.step_tol = c.step_tol;
-  s.max_iter = c.max_iter; s.max_backtrack = c.max_backtrack; s.vm_out = vm_pu;
-  HIPCHK(h, hipMemsetAsync(s.n_active, 0, ((size_t)c.max_iter + 1) * sizeof(int32_t), st));
-  if (h->sbus_stale) {                           // Sbus holds mapdn_solve_only's inputs: rebuild it from the env's loads (q = 0)
-    HIPCHK(h, hipMemsetAsync(s.a, 0, (size_t)d.ns * d.Bp * sizeof(double), st));
-    launch_inject(d, MODE_SOLVE, nullptr, MAPDN_F64, d.cur_pl, d.cur_ql, d.cur_pv, s.a, 0, st);
-  }
-  launch_opf_update(d, s, 0, st);
-  Dev dd = d;
-  dd.active = s.act; dd.iters = const_cast<int32_t*>(s.nr_iters); dd.conv = const_cast<uint8_t*>(s.nr_conv);
-  for (int i = 0; i < c.max_iter; ++i) {         // i power flows solved so far
-    if (i % OPF_POLL == 0) {
-      int32_t left = 0;
-      HIPCHK(h, hipMemcpyAsync(&left, s.n_active + i, sizeof(left), hipMemcpyDeviceToHost, st));
-      HIPCHK(h, hipStreamSynchronize(st));
-      if (left == 0) break;
-    }
-    nr_launch(h, MODE_SOLVE, nullptr, nullptr, nullptr, st, nullptr, 0, &dd);
-    launch_opf_linearise(dd, s, st);
-    launch_opf_qp(dd, s, st);
-    launch_opf_update(d, s, i + 1, st);
-  }
-  transpose_out(h, s.a_sol, 1.0, h->iota_idx, actions, d.ns, st);
-  if (loss_mw) transpose_out(h, s.loss_out, d.sn, h->iota_idx, loss_mw, 1, st);
-  if (violation) transpose_out(h, s.viol_out, 1.0, h->iota_idx, violation, 1, st);
-  launch_copy_i32(s.iters, iterations, d.B, st);
-  launch_copy_u8(s.status, status, d.B, st);
-  HIPCHK(h, hipGetLastError());
-  return MAPDN_OK;
-}
 
 int mapdn_opf_actions(mapdn_handle* h, const mapdn_opf_config* cfg, double* actions, double* vm_pu, double* loss_mw, double* violation,
                       int32_t* iterations, uint8_t* status, void* stream) try {
@@ -1446,52 +1257,7 @@ int mapdn_opf_probe(mapdn_handle* h, const mapdn_opf_config* cfg, const double* 
   NEEDDEV(h);
   if (!h->was_reset) { h->err = "opf_probe before reset"; return MAPDN_E_STATE; }
   HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  if (const int rc = opf_prepare(h)) return rc;
-  const Dev& dv = h->d;
-  const int n = dv.n;
-  const int io = std::max(std::max(n * ns, ns * ns), ns + n);      // identity rows for the widest export
-  if (!h->opf_probe_a) { if (const int rc = dalloc(h, &h->opf_probe_a, (size_t)ns * dv.Bp)) return rc; }
-  if (!h->opf_probe_rows) {
-    std::vector<int32_t> rows((size_t)io + 3 * (size_t)n);
-    for (int i = 0; i < io; ++i) rows[(size_t)i] = i;
-    for (int k = 0; k < n; ++k) {
-      rows[(size_t)io + k] = (int32_t)dv.r_vout + VOF * k + VO_E; rows[(size_t)io + n + k] = (int32_t)dv.r_vout + VOF * k + VO_F;
-      rows[(size_t)io + 2 * n + k] = (int32_t)dv.r_vout + VOF * k + VO_VM;
-    }
-    if (const int rc = dupload(h, &h->opf_probe_rows, rows)) return rc;
-  }
-  const int32_t* iota = h->opf_probe_rows;
-  const int32_t* erow = iota + io;
-  OpfState s = h->opf;
-  s.v_lower = c.v_lower; s.v_upper = c.v_upper; s.v_tol = c.v_tol; s.step_tol = c.step_tol;
-  s.max_iter = c.max_iter; s.max_backtrack = c.max_backtrack; s.vm_out = nullptr; s.a0 = h->opf_probe_a;
-  launch_to_envminor(dv, a, h->opf_probe_a, ns, st);
-  HIPCHK(h, hipMemsetAsync(s.n_active, 0, sizeof(int32_t), st));
-  if (h->sbus_stale) {                           // as opf_run
-    HIPCHK(h, hipMemsetAsync(s.a, 0, (size_t)dv.ns * dv.Bp * sizeof(double), st));
-    launch_inject(dv, MODE_SOLVE, nullptr, MAPDN_F64, dv.cur_pl, dv.cur_ql, dv.cur_pv, s.a, 0, st);
-  }
-  launch_opf_update(dv, s, 0, st);
-  Dev dd = dv;
-  dd.active = s.act; dd.iters = const_cast<int32_t*>(s.nr_iters); dd.conv = const_cast<uint8_t*>(s.nr_conv);
-  nr_launch(h, MODE_SOLVE, nullptr, nullptr, nullptr, st, nullptr, 0, &dd);
-  launch_opf_linearise(dd, s, st);
-  launch_opf_qp(dd, s, st);
-  if (v_re) transpose_out(h, dv.nrbuf, 1.0, erow, v_re, n, st);
-  if (v_im) transpose_out(h, dv.nrbuf, 1.0, erow + n, v_im, n, st);
-  if (vm) transpose_out(h, dv.nrbuf, 1.0, erow + 2 * n, vm, n, st);
-  if (S) transpose_out(h, s.S, 1.0, iota, S, n * ns, st);
-  if (g) transpose_out(h, s.g, 1.0, iota, g, ns, st);
-  if (H) transpose_out(h, s.H, 1.0, iota, H, ns * ns, st);
-  if (loss_mw) transpose_out(h, s.loss, dv.sn, iota, loss_mw, 1, st);
-  if (violation) transpose_out(h, s.viol, 1.0, iota, violation, 1, st);
-  if (d) transpose_out(h, s.qd, 1.0, iota, d, ns, st);
-  if (y) transpose_out(h, s.qy, 1.0, iota, y, ns + n, st);
-  if (linearised) launch_copy_u8(s.lin, linearised, dv.B, st);
-  if (qp_capped) launch_copy_u8(s.qp_capped, qp_capped, dv.B, st);
-  HIPCHK(h, hipGetLastError());
-  return MAPDN_OK;
+  return opf_probe(h, c, a, ns, v_re, v_im, vm, S, g, H, loss_mw, violation, d, y, linearised, qp_capped, (hipStream_t)stream);
 } MAPDN_CATCH(h)
 
 // ---- the PPO half of MAPPO / IPPO's update (csrc/ppo.hip): argument checks here, nothing is launched on a refusal

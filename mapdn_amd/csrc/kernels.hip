@@ -728,5 +728,5 @@ void launch_stats(const Dev& d, long long* out, hipStream_t st) { hipLaunchKerne
 
 // the droop baseline's kernel (droop.hip) is compiled in this translation unit: one object per source file of build.SOURCES
 #include "droop.hip"
-// ... and the OPF baseline's kernels (opf.hip)
+// ... and the OPF baseline's kernels (opf.hip); the steps the two update kernels share are ctlloop.hpp's
 #include "opf.hip"

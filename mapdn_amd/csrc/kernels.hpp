@@ -157,44 +157,35 @@ void launch_copy_i32(const int32_t* s, int32_t* dd, int B, hipStream_t st);
 void launch_copy_u8(const uint8_t* s, uint8_t* dd, int B, hipStream_t st);
 void launch_stats(const Dev& d, long long* out, hipStream_t st);
 
-// ---- droop baseline (droop.hip; mapdn_droop_actions).  Per-env status as in include/mapdn.h; RUNNING only between launches.
-enum { DROOP_CONVERGED = 0, DROOP_MAX_ITER = 1, DROOP_PF_FAILED = 2, DROOP_STOPPED = 3, DROOP_RUNNING = 255 };
-struct DroopState {
+// ---- the traditional baselines: one control-loop frame (ctlloop.hpp: CtlLoop, the fields both loops keep) around the handle's solves
+}  // namespace mapdn
+#include "ctlloop.hpp"
+namespace mapdn {
+
+// ---- droop baseline (droop.hip; mapdn_droop_actions, baselines_host.hpp).  Per-env status as in include/mapdn.h.
+enum { DROOP_CONVERGED = 0, DROOP_MAX_ITER = 1, DROOP_PF_FAILED = 2, DROOP_STOPPED = CTL_STOPPED, DROOP_RUNNING = CTL_RUNNING };
+struct DroopState : CtlLoop {
   double va, vb, vc, vd, damping, v_tol, ratio;
-  int32_t max_iter;
-  double *a, *a_sol, *v_last, *dv2;  // [ns][Bp]: the action of the next solve, the action of the last converged solve, |V| of the last
-                                     // solve, the terms (v - v_last)^2 of the stop test
-  int32_t* iters;                    // [Bp] solves so far
-  uint8_t* status;                   // [Bp]
-  uint8_t* act;                      // [Bp] the solver's active flags of the droop solves (Dev::active of those launches)
-  const int32_t* nr_iters; const uint8_t* nr_conv;   // [Bp] Dev::iters / conv of those launches
+  double *v_last, *dv2;              // [ns][Bp]: |V| of the last solve, the terms (v - v_last)^2 of the stop test
   const int32_t* sg_vrow;            // [ns] row of nrbuf that holds |V| of sgen j's bus (Vout, VO_VM)
-  const int32_t* vm_row;             // [nbo] the same for every original bus
-  int32_t* n_active;                 // [max_iter + 1] envs still iterating after update i
-  double* vm_out;                    // [B][nbo] env-major, or nullptr
 };
 void launch_droop_update(const Dev& d, const DroopState& s, int iter, hipStream_t st);
 
-// ---- OPF baseline (opf.hip, opf.hpp; mapdn_opf_actions).  Per-env status (opf.hpp OPF_*) as in include/mapdn.h; RUNNING only between launches.
-struct OpfState {
+// ---- OPF baseline (opf.hip, opf.hpp; mapdn_opf_actions, baselines_host.hpp).  Per-env status (opf.hpp OPF_*) as in include/mapdn.h.
+struct OpfState : CtlLoop {
   double v_lower, v_upper, v_tol, step_tol;
-  int32_t max_iter, max_backtrack;
+  int32_t max_backtrack;
   // topology tables (by node position): parent, children in the canonical order of the sweeps (CSR), the node of every sgen's bus
-  // (n: the slack), the Y / M constants (opf.hpp OY_*), the slack's own term of the loss, the Vout row of |V| of every bus
+  // (n: the slack), the Y / M constants (opf.hpp OY_*), the slack's own term of the loss
   const int32_t *par, *cptr, *cidx, *sg_node;
   const double* yt; double loss_slack;
-  const int32_t* vm_row;
   // workspace of the linearisation, env-minor: the block-LU factors [n][OPF_FAC], M V [n][2], dV and M dV [n][ns][2], S [n][ns],
   // H [ns][ns], g [ns]; of the QP: d [ns], y [ns + n], scratch (opf_qp_work)
   double *fac, *mv, *X, *W, *S, *H, *g, *qd, *qy, *qw;
-  double *a, *a_sol;                 // [ns][Bp]: the action of the next solve, the action of the last converged solve
   const double* a0;                  // [ns][Bp] the set-points the start launch begins from (clipped to [-1, 1]: mapdn_opf_probe), or nullptr: a = 0
   double *t, *loss, *viol, *loss_out, *viol_out;   // [Bp]: step length; loss (p.u.) and violation of the last solve / of a_sol
-  int32_t *iters, *nback;                           // [Bp] solves so far, failed solves in a row
-  uint8_t *status, *act, *lin, *qp_capped;          // [Bp]; act: the solver's active flags of the OPF solves; lin: linearised by the last launch
-  const int32_t* nr_iters; const uint8_t* nr_conv;  // [Bp] Dev::iters / conv of those launches
-  int32_t* n_active;                 // [max_iter + 1] envs still iterating after update i
-  double* vm_out;                    // [B][nbo] env-major, or nullptr
+  int32_t* nback;                                   // [Bp] failed solves in a row
+  uint8_t *lin, *qp_capped;                         // [Bp]; lin: linearised by the last launch
 };
 void launch_opf_update(const Dev& d, const OpfState& s, int iter, hipStream_t st);
 void launch_opf_linearise(const Dev& d, const OpfState& s, hipStream_t st);

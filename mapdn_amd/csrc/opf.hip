@@ -2,20 +2,20 @@
 // the PV inverters' reactive power as the controls), as a batched reduced-space SQP: per env and per outer iteration
 //   power flow at a  ->  k_opf_linearise (S = d|V|/da, g, the Gauss-Newton H at the converged V)  ->  k_opf_qp (the step d)  ->
 //   k_opf_update (stop test, a <- clip(a + t d), the next Sbus).
-// The power flows are the handle's own kernels in MODE_SOLVE with the OPF's own active set (capi.hip, mapdn_opf_actions), exactly as
-// the droop loop runs them.  The arithmetic is in opf.hpp.  Included at the end of kernels.hip, after droop.hip (one translation unit).
+// The power flows are the handle's own kernels in MODE_SOLVE with the OPF's own active set (baselines_host.hpp, opf_run), in the frame
+// the droop loop runs in (ctlloop.hpp).  The arithmetic is in opf.hpp.  Included at the end of kernels.hip (one translation unit).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "kernels.hpp"
+#include "ctlloop.hpp"
 #include "opf.hpp"
-#include "droop.hip"
 
 namespace mapdn {
 
-// Layout as in droop.hip: a workgroup serves DL = 16 consecutive envs with DS = 16 sub-lanes each (thread t: env lane t % DL, sub-lane
-// t / DL), so that every env-minor row is read 128 bytes at a time.  Sub-lane s takes the columns (sgens) j = s, s + DS, ...
+// Layout: ctlloop.hpp (DL = 16 consecutive envs with DS = 16 sub-lanes each); sub-lane s takes the columns (sgens) j = s, s + DS, ...
+static_assert(OPF_STOPPED == CTL_STOPPED && OPF_RUNNING == CTL_RUNNING, "ctl_start writes the OPF's status values");
 
 // After a solve, for every env whose power flow converged: the block LU of the Jacobian on the tree (sub-lane 0, node by node, the
 // children of a node summed in the plan's canonical order: no atomics, the same bits in every run), then per column the forward path
@@ -156,22 +156,19 @@ __global__ void __launch_bounds__(64) k_opf_qp(Dev d, OpfState s) {
 }
 
 // iter == 0: start — a = 0 (or the caller's set-points s.a0, clipped: the probe), status 3 for the envs that step() would not solve,
-// the Sbus of the first solve (as k_droop_update does).
+// a NaN row of voltages for every env, the Sbus of the first solve.
 // iter = i > 0: after the i-th solve and its QP, opf_decide (opf.hpp) — the solve failed: halve t (at most max_backtrack times in a
-// row) and retry from the last solved a, or stop with status 2;  it converged: record a, |V|, loss and violation, stop with status 0
-// when |d|inf < step_tol, the violation is <= v_tol and the QP did not hit its cap, with status 1 at max_iter or at the least-violation
-// point of bounds that cannot be met; else a <- clip(a + d).  The next Sbus is written with droop_pv_row's expressions.  Counts the envs still iterating into s.n_active[iter] (the host polls it).
+// row) and retry from the last solved a, or stop with status 2 (the |V| of the last solved point stay);  it converged: record a, |V|,
+// loss and violation, stop with status 0 when |d|inf < step_tol, the violation is <= v_tol and the QP did not hit its cap, with
+// status 1 at max_iter or at the least-violation point of bounds that cannot be met; else a <- clip(a + d).  Then the next Sbus.
 __global__ void __launch_bounds__(DL * DS) k_opf_update(Dev d, OpfState s, int iter) {
   __shared__ int s_run[DL];                        // 0 not iterating, 1 next step, 2 stops at this solved point, 3 stops failed, 4 retry
-  const int el = (int)threadIdx.x % DL, sl = (int)threadIdx.x / DL;
-  const int e = (int)blockIdx.x * DL + el;
-  const bool valid = e < d.B;
+  const CtlLane t = ctl_lane(d);
+  const int el = t.el, sl = t.sl, e = t.e;
   const size_t S = (size_t)d.Bp;
-  const double* __restrict__ vout = d.nrbuf;
-  const double nan = __builtin_nan("");
   if (iter == 0) {
-    const bool run = valid && d.done[e] == 0;
-    if (valid) {
+    const bool run = ctl_start(d, s, t);
+    if (t.valid) {
       for (int j = sl; j < d.ns; j += DS) {
         const size_t o = (size_t)j * S + e;
         const double a0 = s.a0 ? opf_trial(s.a0[o], 0.0, 0.0) : 0.0;
@@ -179,29 +176,16 @@ __global__ void __launch_bounds__(DL * DS) k_opf_update(Dev d, OpfState s, int i
       }
       for (int r = sl; r < d.ns + d.n; r += DS) s.qy[(size_t)r * S + e] = 0.0;
       if (sl == 0) {
-        s.iters[e] = 0; s.nback[e] = 0; s.t[e] = 1.0; s.lin[e] = 0; s.qp_capped[e] = 0;
-        s.status[e] = run ? OPF_RUNNING : OPF_STOPPED; s.act[e] = run ? 1 : 0;
-        s.loss_out[e] = nan; s.viol_out[e] = nan;
+        s.nback[e] = 0; s.t[e] = 1.0; s.lin[e] = 0; s.qp_capped[e] = 0;
+        s.loss_out[e] = __builtin_nan(""); s.viol_out[e] = __builtin_nan("");
       }
-      if (s.vm_out) for (int b = sl; b < d.nbo; b += DS) s.vm_out[(size_t)e * d.nbo + b] = nan;
-      if (run)
-        for (int i = sl; i < d.n_mlo; i += DS) {   // (k_advance leaves these to the injection of the step)
-          const int k = d.mlo_pos[i];
-          double P = 0.0, Q = 0.0;
-          for (int q = d.load_ptr[k]; q < d.load_ptr[k + 1]; ++q) {
-            const int li = d.load_idx[q];
-            P += d.cur_pl[(size_t)li * S + e] * d.load_scale[li]; Q += d.cur_ql[(size_t)li * S + e] * d.load_scale[li];
-          }
-          ((double2*)((char*)d.nrbuf + d.sb_off))[(size_t)k * S + e] = make_double2(-P / d.sn, -Q / d.sn);
-        }
+      ctl_no_voltages(d, s, t);
+      if (run) ctl_mlo_rows(d, t);
     }
-    __syncthreads();
-    if (run) for (int jb = sl; jb < d.n_sgb; jb += DS) droop_pv_row(d, e, jb, s.a);
-    const unsigned long long m = __ballot(run && sl == 0);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(s.n_active + iter, (int)__popcll(m));
+    ctl_next_solve(d, s, t, iter, run);
     return;
   }
-  const bool act = valid && s.act[e] != 0;
+  const bool act = t.valid && s.act[e] != 0;
   if (sl == 0) {
     int run = 0;
     if (act) {
@@ -224,21 +208,16 @@ __global__ void __launch_bounds__(DL * DS) k_opf_update(Dev d, OpfState s, int i
   }
   __syncthreads();
   const int run = s_run[el];
-  if (run == 1 || run == 2) {
-    for (int j = sl; j < d.ns; j += DS) s.a_sol[(size_t)j * S + e] = s.a[(size_t)j * S + e];
-    if (s.vm_out) for (int b = sl; b < d.nbo; b += DS) s.vm_out[(size_t)e * d.nbo + b] = vout[(size_t)s.vm_row[b] * S + e];
-  }
-  if (run == 1 || run == 4) {
-    const double t = s.t[e];
+  const bool go = run == 1 || run == 4;
+  if (run == 1 || run == 2) ctl_record(d, s, t);
+  if (go) {
+    const double tt = s.t[e];
     for (int j = sl; j < d.ns; j += DS) {
       const size_t o = (size_t)j * S + e;
-      s.a[o] = opf_trial(s.a_sol[o], t, s.qd[o]);
+      s.a[o] = opf_trial(s.a_sol[o], tt, s.qd[o]);
     }
   }
-  __syncthreads();                                 // (the new a of every sgen of a bus before its row)
-  if (run == 1 || run == 4) for (int jb = sl; jb < d.n_sgb; jb += DS) droop_pv_row(d, e, jb, s.a);
-  const unsigned long long m = __ballot((run == 1 || run == 4) && sl == 0);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(s.n_active + iter, (int)__popcll(m));
+  ctl_next_solve(d, s, t, iter, go);
 }
 
 void launch_opf_update(const Dev& d, const OpfState& s, int iter, hipStream_t st) {

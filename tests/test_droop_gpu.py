@@ -15,6 +15,7 @@ from mapdn_amd.tester import PGTester
 from oracle.env_restated import INFO_KEYS, VoltageControlOracle
 from oracle.pp_restated import runpp_restated
 from tests import kernel_matrix as km
+from tests.baseline_contract import check_state_untouched_and_step_agrees, env_state
 from tests.droop_ref import droop_ref, droop_ref_oracle
 from tests.zip_nets import runpp_zip
 
@@ -39,13 +40,6 @@ def make_env(key, B, args=None, **kw):
     a = dict(ARGS)
     a.update(args or {})
     return VoltageControlBatch(net, prof, a, n_envs=B, device=DEV, obs_dtype=torch.float64, **kw)
-
-
-def env_state(env):
-    """(load_p, load_q, sgen_p, s_max) of every env: what the next step() solves with"""
-    lp, lq = env.loads()
-    pv = env.results(("sgen_p",))["sgen_p"]
-    return lp.cpu().numpy(), lq.cpu().numpy(), pv.cpu().numpy(), env.profile_stats()[1]
 
 
 def droop(env, cfg=None):
@@ -97,54 +91,13 @@ def test_parity_with_the_cpu_reference(key):
         env.close()
 
 
-def snapshot(env):
-    torch.cuda.synchronize()
-    out = dict(obs=env.get_obs().clone(), state=env.get_state().clone(), returns=env.episode_returns().clone(),
-               starts=env.start_rows().clone(), stats=env.stats(), loads=torch.cat(env.loads(), 1).clone())
-    out.update({k: v.clone() for k, v in env.results().items()})
-    return out
-
-
-def same(x, y):
-    for k in x:
-        if isinstance(x[k], torch.Tensor):
-            assert torch.equal(x[k], y[k]), k
-        else:
-            assert x[k] == y[k], k
-
-
 @pytest.mark.parametrize("key", ["case141", "case33_meshed", "case322"])
 @pytest.mark.parametrize("after_solve", [False, True])
 def test_state_untouched_and_step_agrees(key, after_solve):
-    B = 24
-    A, T = make_env(key, B), make_env(key, B)
-    try:
-        A.reset(); T.reset()
-        rng = np.random.default_rng(3)
-        for _ in range(2):
-            act = torch.as_tensor(rng.uniform(-0.8, 0.8, (B, A.n_sgen)), device=DEV)
-            A.step(act); T.step(act)
-        if after_solve:
-            lp, lq, pv, _ = env_state(A)
-            for env in (A, T):
-                env.solve(lp * 1.3, lq, pv, np.zeros_like(pv))
-        before = snapshot(A)
-        a, it, st, vm = A.droop_actions(vm_pu=True)
-        same(before, snapshot(A))
-        same(before, snapshot(T))
-        r1, t1, i1 = [x.clone() for x in A.step(a)]
-        r2, t2, i2 = [x.clone() for x in T.step(a)]
-        assert torch.equal(r1, r2) and torch.equal(t1, t2) and torch.equal(i1, i2)
-        assert torch.equal(A.get_obs(), T.get_obs())
-        ok = st <= 1
-        assert ok.any()
-        committed = A.results(("vm_pu",))["vm_pu"]
-        assert float((committed[ok] - vm[ok]).abs().max()) < 1e-12
-        r1, _, i1 = [x.clone() for x in A.step(a)]
-        r2, _, i2 = [x.clone() for x in T.step(a)]
-        assert torch.equal(r1, r2) and torch.equal(i1, i2)
-    finally:
-        A.close(); T.close()
+    def baseline(env):
+        a, it, st, vm = env.droop_actions(vm_pu=True)
+        return a, st, vm
+    check_state_untouched_and_step_agrees(lambda B: make_env(key, B), baseline, after_solve, B=24)
 
 
 def test_bits_across_compiled_tree_geometries():

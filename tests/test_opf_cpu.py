@@ -134,7 +134,7 @@ def seven_bus():
 
 
 def tree_tables(Y, slack, vroot):
-    """what opf_prepare (csrc/capi.hip) builds from the plan, from a dense Ybus of a radial net: positions (children before parents),
+    """what opf_prepare (csrc/baselines_host.hpp) builds from the plan, from a dense Ybus of a radial net: positions (children before parents),
     parent, children in the canonical order (the chain child k - 1 first, then ascending) and the OPF_YT constants per node"""
     nb = Y.shape[0]
     adj = [[m for m in range(nb) if m != k and Y[k, m] != 0] for k in range(nb)]

@@ -15,6 +15,7 @@ from mapdn_amd.netspec import make_case
 from oracle.pp_restated import runpp_restated
 from tests import kernel_matrix as km
 from tests import opf_ref as R
+from tests.baseline_contract import check_state_untouched_and_step_agrees, env_state
 
 pytestmark = pytest.mark.gpu
 
@@ -41,13 +42,6 @@ def make_env(case, B, args=None, days=3, **kw):
     a = dict(ARGS)
     a.update(args or {})
     return VoltageControlBatch(net, prof, a, n_envs=B, device=DEV, obs_dtype=torch.float64, **kw), net, prof
-
-
-def env_state(env):
-    """(load_p, load_q, sgen_p, s_max) of every env: what the next step() solves with"""
-    lp, lq = env.loads()
-    pv = env.results(("sgen_p",))["sgen_p"]
-    return lp.cpu().numpy(), lq.cpu().numpy(), pv.cpu().numpy(), env.profile_stats()[1]
 
 
 def place(env, prof, rows):
@@ -139,71 +133,36 @@ def test_runs_and_batch_sizes_give_the_same_bits(runs, case):
             assert np.array_equal(x[e], y[0], equal_nan=True), (case, e)
 
 
-def snapshot(env):
-    torch.cuda.synchronize()
-    out = dict(obs=env.get_obs().clone(), state=env.get_state().clone(), returns=env.episode_returns().clone(),
-               starts=env.start_rows().clone(), stats=env.stats(), loads=torch.cat(env.loads(), 1).clone())
-    out.update({k: v.clone() for k, v in env.results().items()})
-    return out
-
-
-def same(x, y):
-    for k in x:
-        if isinstance(x[k], torch.Tensor):
-            assert torch.equal(x[k], y[k]), k
-        else:
-            assert x[k] == y[k], k
-
-
 @pytest.mark.parametrize("case", ["case33", "case141", "case322"])
 @pytest.mark.parametrize("after_solve", [False, True])
 def test_state_untouched_and_step_agrees(case, after_solve):
     """the droop contract on the radial feeders droop is held to, from the same starts: noisy resets, two random-action steps"""
-    B = 24
     net, prof = km.make_net(case)
-    A, T = (VoltageControlBatch(net, prof, dict(ARGS), n_envs=B, device=DEV, obs_dtype=torch.float64) for _ in range(2))
-    try:
-        A.reset(); T.reset()
-        rng = np.random.default_rng(3)
-        for _ in range(2):
-            act = torch.as_tensor(rng.uniform(-0.8, 0.8, (B, A.n_sgen)), device=DEV)
-            A.step(act); T.step(act)
-        if after_solve:
-            lp, lq, pv, _ = env_state(A)
-            for env in (A, T):
-                env.solve(lp * 1.3, lq, pv, np.zeros_like(pv))
-        before = snapshot(A)
-        a, loss, viol, it, st, vm = A.opf_actions(vm_pu=True)
+
+    def baseline(env):
+        a, loss, viol, it, st, vm = env.opf_actions(vm_pu=True)
         print(case, after_solve, "status", st.tolist(), "iterations", it.tolist())
-        same(before, snapshot(A))
-        same(before, snapshot(T))
-        r1, t1, i1 = [x.clone() for x in A.step(a)]
-        r2, t2, i2 = [x.clone() for x in T.step(a)]
-        assert torch.equal(r1, r2) and torch.equal(t1, t2) and torch.equal(i1, i2)
-        assert torch.equal(A.get_obs(), T.get_obs())
-        ok = st <= 1
-        assert ok.any()
-        committed = A.results(("vm_pu",))["vm_pu"]
-        assert float((committed[ok] - vm[ok]).abs().max()) < 1e-12
-        r1, _, i1 = [x.clone() for x in A.step(a)]
-        r2, _, i2 = [x.clone() for x in T.step(a)]
-        assert torch.equal(r1, r2) and torch.equal(i1, i2)
-    finally:
-        A.close(); T.close()
+        return a, st, vm
+    check_state_untouched_and_step_agrees(lambda B: VoltageControlBatch(net, prof, dict(ARGS), n_envs=B, device=DEV, obs_dtype=torch.float64),
+                                          baseline, after_solve, B=24)
 
 
 def test_stopped_envs_get_status_3():
-    env, _, _ = make_env("case33", 8, dict(episode_limit=2))
-    try:
-        env.reset()
-        a, loss, viol, it, st, vm = opf(env)
-        assert (st <= 1).all() and np.isfinite(loss).all()
-        _, term, _ = env.step(torch.as_tensor(a, device=DEV))
-        assert bool(term.all())
-        a, loss, viol, it, st, vm = opf(env)
-        assert (st == 3).all() and (a == 0).all() and (it == 0).all() and np.isnan(vm).all() and np.isnan(loss).all() and np.isnan(viol).all()
-    finally:
-        env.close()
+    for args in (dict(episode_limit=2), dict(episode_limit=2, auto_reset=True)):
+        env, _, _ = make_env("case33", 8, args)
+        try:
+            env.reset()
+            a, loss, viol, it, st, vm = opf(env)
+            assert (st <= 1).all() and np.isfinite(loss).all()
+            _, term, _ = env.step(torch.as_tensor(a, device=DEV))
+            assert bool(term.all())                                     # terminated (frozen, or waiting for the auto-reset restart)
+            a, loss, viol, it, st, vm = opf(env)
+            assert (st == 3).all() and (a == 0).all() and (it == 0).all() and np.isnan(vm).all() and np.isnan(loss).all() and np.isnan(viol).all()
+            if args.get("auto_reset"):
+                env.step(torch.as_tensor(a, device=DEV))                # the restart
+                assert (opf(env)[4] <= 1).all()
+        finally:
+            env.close()
 
 
 def test_widest_feeder_runs():

@@ -18,7 +18,8 @@ from mapdn_amd.netspec import Profiles
 from oracle.pp_restated import make_ybus, runpp_restated
 from tests import opf_kernel_cases as K
 from tests import opf_ref as R
-from tests.test_opf_gpu import check_point_against_the_oracle, env_state, place, same, snapshot
+from tests.baseline_contract import env_state, same, snapshot
+from tests.test_opf_gpu import check_point_against_the_oracle, place
 
 pytestmark = pytest.mark.gpu
 
