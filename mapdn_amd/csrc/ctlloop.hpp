@@ -45,7 +45,7 @@ __device__ __forceinline__ void ctl_pv_row(const Dev& d, int e, int jb, const do
     P = 0.0; Q = 0.0;
     for (int i = d.load_ptr[k]; i < d.load_ptr[k + 1]; ++i) {
       const int li = d.load_idx[i];
-      P += d.cur_pl[(size_t)li * d.Bp + e] * d.load_scale[li]; Q += d.cur_ql[(size_t)li * d.Bp + e] * d.load_scale[li];
+      add_scaled(P, d.cur_pl[(size_t)li * d.Bp + e], d.load_scale[li]); add_scaled(Q, d.cur_ql[(size_t)li * d.Bp + e], d.load_scale[li]);
     }
   } else { const double2 v = ((const double2*)d.bus_ld)[(size_t)jb * d.Bp + e]; P = v.x; Q = v.y; }
   for (int i = d.sgen_ptr[k]; i < d.sgen_ptr[k + 1]; ++i) {
@@ -55,7 +55,7 @@ __device__ __forceinline__ void ctl_pv_row(const Dev& d, int e, int jb, const do
     const double sm = d.smax[j];
     const double lim = sqrt(sm * sm - p * p);
     const double q = lim * a[o];
-    P -= p * d.sgen_scale[j]; Q -= q * d.sgen_scale[j];
+    sub_scaled(P, p, d.sgen_scale[j]); sub_scaled(Q, q, d.sgen_scale[j]);
   }
   if (k < d.n) ((double2*)((char*)d.nrbuf + d.sb_off))[(size_t)k * d.Bp + e] = make_double2(-P / d.sn, -Q / d.sn);
 }
@@ -68,7 +68,7 @@ __device__ __forceinline__ void ctl_mlo_rows(const Dev& d, const CtlLane& t) {
     double P = 0.0, Q = 0.0;
     for (int q = d.load_ptr[k]; q < d.load_ptr[k + 1]; ++q) {
       const int li = d.load_idx[q];
-      P += d.cur_pl[(size_t)li * S + t.e] * d.load_scale[li]; Q += d.cur_ql[(size_t)li * S + t.e] * d.load_scale[li];
+      add_scaled(P, d.cur_pl[(size_t)li * S + t.e], d.load_scale[li]); add_scaled(Q, d.cur_ql[(size_t)li * S + t.e], d.load_scale[li]);
     }
     ((double2*)((char*)d.nrbuf + d.sb_off))[(size_t)k * S + t.e] = make_double2(-P / d.sn, -Q / d.sn);
   }

@@ -102,8 +102,8 @@ k_inject(Dev d, int mode, const AT* __restrict__ actions, const double* __restri
       const double p = profile_value(d, e, ar_row, draw, STREAM_LOAD_P, li, d.ns, add_noise);
       const double q = profile_value(d, e, ar_row, draw, STREAM_LOAD_Q, li, d.ns + d.nl, add_noise);
       d.cur_pl[o] = p; d.cur_ql[o] = q;
-      P += p * d.load_scale[li]; Q += q * d.load_scale[li];
-    } else { P += pl[o] * d.load_scale[li]; Q += ql[o] * d.load_scale[li]; }   // pd2ppc: PD = sum p_mw * scaling
+      add_scaled(P, p, d.load_scale[li]); add_scaled(Q, q, d.load_scale[li]);
+    } else { add_scaled(P, pl[o], d.load_scale[li]); add_scaled(Q, ql[o], d.load_scale[li]); }   // pd2ppc: PD = sum p_mw * scaling
   }
   if (mode != MODE_SOLVE && d.sgb_of_pos[k] >= 0)   // load part of the injection at a PV bus, kept for k_inject_sgen
     ((double2*)d.bus_ld)[(size_t)d.sgb_of_pos[k] * d.Bp + e] = make_double2(P, Q);
@@ -128,7 +128,7 @@ k_inject(Dev d, int mode, const AT* __restrict__ actions, const double* __restri
       } else q = 0.0;                            // base-net q_mvar (deepcopy of base_powergrid, :106)
       d.q_new[o] = q;
     }
-    P -= p * d.sgen_scale[j]; Q -= q * d.sgen_scale[j];
+    sub_scaled(P, p, d.sgen_scale[j]); sub_scaled(Q, q, d.sgen_scale[j]);
   }
   if (k < d.n) {   // scheduled injection as an (re, im) pair, stored by node position
     const size_t o = (size_t)k * d.Bp + e;
@@ -182,7 +182,7 @@ k_inject_sgen(Dev d, int mode, const AT* __restrict__ actions, int add_noise) {
     Ps = 0.0; Qs = 0.0;
     for (int i = d.load_ptr[kk]; i < d.load_ptr[kk + 1]; ++i) {
       const int li = d.load_idx[i];
-      Ps += d.cur_pl[(size_t)li * d.Bp + e] * d.load_scale[li]; Qs += d.cur_ql[(size_t)li * d.Bp + e] * d.load_scale[li];
+      add_scaled(Ps, d.cur_pl[(size_t)li * d.Bp + e], d.load_scale[li]); add_scaled(Qs, d.cur_ql[(size_t)li * d.Bp + e], d.load_scale[li]);
     }
   };
   if (mlo_row) {
@@ -203,7 +203,7 @@ k_inject_sgen(Dev d, int mode, const AT* __restrict__ actions, int add_noise) {
         const double p = profile_value(d, e, ar_row, draw, STREAM_LOAD_P, li, d.ns, add_noise);
         const double q = profile_value(d, e, ar_row, draw, STREAM_LOAD_Q, li, d.ns + d.nl, add_noise);
         d.cur_pl[o] = p; d.cur_ql[o] = q;
-        Ps += p * d.load_scale[li]; Qs += q * d.load_scale[li];
+        add_scaled(Ps, p, d.load_scale[li]); add_scaled(Qs, q, d.load_scale[li]);
       }
     };
     load_sum(k, P, Q);
@@ -237,7 +237,7 @@ k_inject_sgen(Dev d, int mode, const AT* __restrict__ actions, int add_noise) {
       q = lim * (d.action_low + (d.action_high - d.action_low) * u);
     } else q = 0.0;                              // base-net q_mvar (deepcopy of base_powergrid, :106)
     d.q_new[o] = q;
-    P -= p * d.sgen_scale[j]; Q -= q * d.sgen_scale[j];
+    sub_scaled(P, p, d.sgen_scale[j]); sub_scaled(Q, q, d.sgen_scale[j]);
   }
   if (k < d.n) sbp[(size_t)k * d.Bp] = make_double2(-P / d.sn, -Q / d.sn);
 }

@@ -254,12 +254,12 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
         double P, Q;
         if (nld > 1) {                             // several loads on the bus: the sum of the stored values, in CSR order
           P = 0.0; Q = 0.0;
-          P += lp0[it] * ls0[it]; Q += lq0[it] * ls0[it];
-          P += lp1[it] * ls1[it]; Q += lq1[it] * ls1[it];
+          add_scaled(P, lp0[it], ls0[it]); add_scaled(Q, lq0[it], ls0[it]);
+          add_scaled(P, lp1[it], ls1[it]); add_scaled(Q, lq1[it], ls1[it]);
 #pragma unroll 1
           for (int q = d.load_ptr[k] + 2; q < d.load_ptr[k + 1]; ++q) {     // a third, fourth ... load (rare)
             const int li = d.load_idx[q];
-            P += d.cur_pl[(size_t)li * S_ + ee] * d.load_scale[li]; Q += d.cur_ql[(size_t)li * S_ + ee] * d.load_scale[li];
+            add_scaled(P, d.cur_pl[(size_t)li * S_ + ee], d.load_scale[li]); add_scaled(Q, d.cur_ql[(size_t)li * S_ + ee], d.load_scale[li]);
           }
         } else if (j0 >= 0) { P = blv[it].x; Q = blv[it].y; }
         else { P = 0.0; Q = 0.0; }
@@ -269,7 +269,7 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
             const double lim = sqrt(sm * sm - p * p);
             const double qv = lim * a0[it];
             d.q_new[(size_t)j0 * S_ + ee] = qv;
-            P -= p * sc0[it]; Q -= qv * sc0[it];
+            sub_scaled(P, p, sc0[it]); sub_scaled(Q, qv, sc0[it]);
           }
 #pragma unroll 1
           for (int q = 1; q < nsg; ++q) {          // further sgens on the same bus (rare)
@@ -281,7 +281,7 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
             const size_t ai = (size_t)ee * d.ns + j;
             const double qv = lim * (a32 ? (double)((const float*)d.fi_actions)[ai] : ((const double*)d.fi_actions)[ai]);
             d.q_new[o] = qv;
-            P -= p * d.sgen_scale[j]; Q -= qv * d.sgen_scale[j];
+            sub_scaled(P, p, d.sgen_scale[j]); sub_scaled(Q, qv, d.sgen_scale[j]);
           }
         }
         if (sbi >= 0) ((double2*)((char*)d.nrbuf + d.sb_off))[(size_t)sbi * S_ + ee] = make_double2(-P / d.sn, -Q / d.sn);
