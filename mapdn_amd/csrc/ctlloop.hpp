@@ -35,42 +35,24 @@ __device__ __forceinline__ CtlLane ctl_lane(const Dev& d) {
 }
 
 // The PV-bus Sbus entry of bus jb of env e for the actions a (env-minor [ns][Bp]) into the Sbus buffer the next solve reads (d.sb_off):
-// the expressions of k_inject_sgen in its order — the load part of the bus (bus_ld, or the sum of the stored loads of a bus with
-// several), minus p and q = sqrt(s_max^2 - p^2) a of every sgen on it — so that the loop's solve and the step() that applies its
-// actions solve the same Sbus.
+// the row k_inject_sgen writes for a stepping env (inject.hpp), with q = sqrt(s_max^2 - p^2) a of every sgen on the bus — so that the
+// loop's solve and the step() that applies its actions solve the same Sbus.
 __device__ __forceinline__ void ctl_pv_row(const Dev& d, int e, int jb, const double* __restrict__ a) {
   const int k = d.sgb_pos[jb];
+  const EnvTurn stepping = {true, false, 0u, 0};
   double P, Q;
-  if (d.load_ptr[k + 1] - d.load_ptr[k] > 1) {
-    P = 0.0; Q = 0.0;
-    for (int i = d.load_ptr[k]; i < d.load_ptr[k + 1]; ++i) {
-      const int li = d.load_idx[i];
-      add_scaled(P, d.cur_pl[(size_t)li * d.Bp + e], d.load_scale[li]); add_scaled(Q, d.cur_ql[(size_t)li * d.Bp + e], d.load_scale[li]);
-    }
-  } else { const double2 v = ((const double2*)d.bus_ld)[(size_t)jb * d.Bp + e]; P = v.x; Q = v.y; }
-  for (int i = d.sgen_ptr[k]; i < d.sgen_ptr[k + 1]; ++i) {
-    const int j = d.sgen_idx[i];
-    const size_t o = (size_t)j * d.Bp + e;
-    const double p = d.cur_pv[o];
-    const double sm = d.smax[j];
-    const double lim = sqrt(sm * sm - p * p);
-    const double q = lim * a[o];
-    sub_scaled(P, p, d.sgen_scale[j]); sub_scaled(Q, q, d.sgen_scale[j]);
-  }
-  if (k < d.n) ((double2*)((char*)d.nrbuf + d.sb_off))[(size_t)k * d.Bp + e] = make_double2(-P / d.sn, -Q / d.sn);
+  pv_bus_load_sum(d, jb, k, e, P, Q);
+  sub_bus_sgens(d, k, e, stepping, d.cur_pv, 0, [&](int j, size_t o, double p) { return clip_q(p, d.smax[j], a[o]); }, P, Q);
+  if (k < d.n) ((double2*)((char*)d.nrbuf + d.sb_off))[(size_t)k * d.Bp + e] = sbus_entry(P, Q, d.sn);
 }
 
 // The Sbus rows of the load-only buses with several loads (k_advance leaves these to the injection of the step)
 __device__ __forceinline__ void ctl_mlo_rows(const Dev& d, const CtlLane& t) {
-  const size_t S = (size_t)d.Bp;
   for (int i = t.sl; i < d.n_mlo; i += DS) {
     const int k = d.mlo_pos[i];
-    double P = 0.0, Q = 0.0;
-    for (int q = d.load_ptr[k]; q < d.load_ptr[k + 1]; ++q) {
-      const int li = d.load_idx[q];
-      add_scaled(P, d.cur_pl[(size_t)li * S + t.e], d.load_scale[li]); add_scaled(Q, d.cur_ql[(size_t)li * S + t.e], d.load_scale[li]);
-    }
-    ((double2*)((char*)d.nrbuf + d.sb_off))[(size_t)k * S + t.e] = make_double2(-P / d.sn, -Q / d.sn);
+    double P, Q;
+    stored_load_sum(d, k, t.e, d.cur_pl, d.cur_ql, P, Q);
+    ((double2*)((char*)d.nrbuf + d.sb_off))[(size_t)k * d.Bp + t.e] = sbus_entry(P, Q, d.sn);
   }
 }
 

@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(DL * DS) k_droop_update(Dev d, DroopState s, i
       const double v = vout[(size_t)s.sg_vrow[j] * S + e];
       const double a = s.a[o];
       const double p = d.cur_pv[o], sm = d.smax[j];
-      const double lim = sqrt(sm * sm - p * p);
+      const double lim = q_limit(p, sm);
       s.v_last[o] = v;
       s.a_sol[o] = a;
       s.a[o] = droop_damped(a, droop_target(droop_law(v, s.va, s.vb, s.vc, s.vd), s.ratio, sm, lim), s.damping);

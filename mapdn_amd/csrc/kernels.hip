@@ -15,8 +15,7 @@
 
 #include <type_traits>
 
-#include "kernels.hpp"
-#include "philox.hpp"     // Philox4x32-10, u53 (host-checkable: tests/test_philox.py)
+#include "kernels.hpp"    // Dev, and inject.hpp: the injection, the env's turn, the Philox noise
 #include "nr_common.hpp"
 #include "nr_inst_list.hpp"
 
@@ -28,35 +27,8 @@ namespace mapdn {
 //     build_bus._calc_pq_elements_and_add_on_ppc + makeSbus: Sbus[k] = -(sum load - sum sgen)/sn_mva
 //     by element->bus CSR (no atomics).  thread = (position k, env e); the thread of a bus computes
 //     the q of the sgens on that bus, so q_new is written exactly once.  MODE_SOLVE takes all four
-//     element-power arrays as given (mapdn_solve_only).
+//     element-power arrays as given (mapdn_solve_only).  The arithmetic is inject.hpp's.
 // =================================================================================================
-// episode start row of reset(): hour, day, interval sampled in the order of voltage_control_env.py:111-113 from the
-// env's Philox stream (mapping in oracle/philox.py)
-__device__ __forceinline__ int64_t sample_start_row(const Dev& d, int e, uint32_t draw) {
-  uint32_t x[4];
-  philox4x32_10((uint32_t)(d.env_id_offset + e), draw, STREAM_START, 0u, d.seed_lo, d.seed_hi, x);
-  const int64_t hour = (int64_t)(((uint64_t)x[0] * 24u) >> 32);                        // :384
-  const int64_t day = (int64_t)(((uint64_t)x[1] * (uint64_t)d.n_start_days) >> 32);    // :398
-  const int64_t interval = (int64_t)(((uint64_t)x[2] * (uint64_t)d.per_hour) >> 32);   // :389
-  return interval + hour * d.per_hour + day * d.per_day;                                // :445
-}
-// one column of _set_demand_and_pv (:491-513): table value + std/100 * |N(0,1)|; column j of a stream takes the cosine
-// (even j) or sine (odd j) Box-Muller branch of Philox block j >> 1 — the same numbers k_advance produces pairwise
-__device__ __forceinline__ double profile_value(const Dev& d, int e, int64_t row, uint32_t draw, int stream, int j, int col0, int add_noise) {
-  double v = d.table[(size_t)row * d.ncol + col0 + j];
-  if (add_noise) {
-    uint32_t x[4];
-    philox4x32_10((uint32_t)(d.env_id_offset + e), draw, (uint32_t)stream, (uint32_t)(j >> 1), d.seed_lo, d.seed_hi, x);
-    const double u1 = (u53(x[0], x[1]) + 0.5) * (1.0 / 9007199254740992.0);
-    const double u2 = u53(x[2], x[3]) * (1.0 / 9007199254740992.0);
-    const double r = sqrt(-2.0 * log(u1));
-    double sn, cs;
-    sincos(2.0 * M_PI * u2, &sn, &cs);
-    v += d.stdv[col0 + j] * fabs(r * ((j & 1) ? sn : cs));
-  }
-  return v;
-}
-
 template <typename AT>
 __global__ void __launch_bounds__(256)
 k_inject(Dev d, int mode, const AT* __restrict__ actions, const double* __restrict__ pl, const double* __restrict__ ql,
@@ -64,75 +36,21 @@ k_inject(Dev d, int mode, const AT* __restrict__ actions, const double* __restri
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   const int k = blockIdx.y;                      // 0..n (n == slack: only its sgens' q, no Sbus row)
   if (e >= d.Bp) return;
-  bool act = true;
-  // auto_reset: an env that terminated in an earlier call starts its next episode in this one (reset(), :96-135, for
-  // this env alone): new start row, first profile row of the window (+ noise), random initial action — computed here
-  // element by element by the thread of the element's bus, so that every cur_* entry still has exactly one writer
-  bool ar = false;
-  int64_t ar_row = 0;
-  uint32_t draw = 0;
-  if (mode != MODE_SOLVE) {
-    if (e >= d.B) act = false;
-    else if (mode == MODE_STEP) {
-      const bool dn = d.done[e] != 0;
-      ar = dn && d.auto_reset;
-      act = !dn || ar;
-    } else act = d.pending[e] != 0;
-    draw = mode == MODE_STEP ? d.draw[e] : d.adv_draw[e];
-    if (ar) {
-      const int64_t start = sample_start_row(d, e, draw);
-      ar_row = start + 1;                        // t = self.steps == 1 (:100, :473)
-      if (k == 0) d.start_row[e] = start;
-    }
-    if (k == 0) {
-      d.active[e] = act ? 1 : 0;
-      if (mode == MODE_STEP) {
-        d.resetting[e] = ar ? 1 : 0;
-        // step(): the next profile row is row `steps` (before the increment, :199 vs :202) of the episode window and
-        // uses the env's current draw counter; queued here, before the solve (frozen / restarting envs do not advance)
-        d.adv_row[e] = (act && !ar) ? d.start_row[e] + d.steps[e] : -1; d.adv_draw[e] = draw;
-      }
-    }
-  }
-  double P = 0.0, Q = 0.0;
-  for (int i = d.load_ptr[k]; i < d.load_ptr[k + 1]; ++i) {
-    const int li = d.load_idx[i];
-    const size_t o = (size_t)li * d.Bp + e;
-    if (ar) {
-      const double p = profile_value(d, e, ar_row, draw, STREAM_LOAD_P, li, d.ns, add_noise);
-      const double q = profile_value(d, e, ar_row, draw, STREAM_LOAD_Q, li, d.ns + d.nl, add_noise);
-      d.cur_pl[o] = p; d.cur_ql[o] = q;
-      add_scaled(P, p, d.load_scale[li]); add_scaled(Q, q, d.load_scale[li]);
-    } else { add_scaled(P, pl[o], d.load_scale[li]); add_scaled(Q, ql[o], d.load_scale[li]); }   // pd2ppc: PD = sum p_mw * scaling
-  }
+  const EnvTurn t = env_turn(d, mode, e);        // (inject.hpp: a restarting env is refreshed by the thread of each element's bus)
+  if (k == 0) note_turn(d, mode, e, t);
+  double P, Q;
+  if (t.ar) restart_load_sum(d, k, e, t.ar_row, t.draw, add_noise, P, Q);
+  else stored_load_sum(d, k, e, pl, ql, P, Q);
   if (mode != MODE_SOLVE && d.sgb_of_pos[k] >= 0)   // load part of the injection at a PV bus, kept for k_inject_sgen
     ((double2*)d.bus_ld)[(size_t)d.sgb_of_pos[k] * d.Bp + e] = make_double2(P, Q);
-  for (int i = d.sgen_ptr[k]; i < d.sgen_ptr[k + 1]; ++i) {
-    const int j = d.sgen_idx[i];
-    const size_t o = (size_t)j * d.Bp + e;
-    double p;
-    if (ar) { p = profile_value(d, e, ar_row, draw, STREAM_PV, j, 0, add_noise); d.cur_pv[o] = p; d.cur_q[o] = 0.0; }
-    else p = pv[o];
-    double q;
-    if (mode == MODE_SOLVE) q = qin[o];
-    else if (!act) q = d.q_new[o];
-    else {
-      const double sm = d.smax[j];
-      const double lim = sqrt(sm * sm - p * p);
-      if (mode == MODE_STEP && !ar) q = lim * (double)actions[(size_t)e * d.ns + j];
-      else if (d.reset_action) {
-        uint32_t x[4];
-        philox4x32_10((uint32_t)(d.env_id_offset + e), draw, STREAM_ACTION, (uint32_t)(j >> 1), d.seed_lo, d.seed_hi, x);
-        const double u = ((j & 1) ? u53(x[2], x[3]) : u53(x[0], x[1])) * (1.0 / 9007199254740992.0);
-        q = lim * (d.action_low + (d.action_high - d.action_low) * u);
-      } else q = 0.0;                            // base-net q_mvar (deepcopy of base_powergrid, :106)
-      d.q_new[o] = q;
-    }
-    sub_scaled(P, p, d.sgen_scale[j]); sub_scaled(Q, q, d.sgen_scale[j]);
-  }
+  sub_bus_sgens(d, k, e, t, pv, add_noise, [&](int j, size_t o, double p) {
+    if (mode == MODE_SOLVE) return qin[o];       // all four element-power arrays as given
+    if (!t.act) return d.q_new[o];               // frozen
+    return d.q_new[o] = turn_q(d, mode, t, actions, e, j, p);
+  }, P, Q);
   if (k < d.n) {   // scheduled injection as an (re, im) pair, stored by node position
     const size_t o = (size_t)k * d.Bp + e;
-    const double2 v = make_double2(-P / d.sn, -Q / d.sn);
+    const double2 v = sbus_entry(P, Q, d.sn);
     ((double2*)((char*)d.nrbuf + d.sb_off))[o] = v;
     if (mode != MODE_SOLVE) ((double2*)((char*)d.nrbuf + d.sb_off_alt))[o] = v;   // both Sbus buffers (see k_advance) are current afterwards
   }
@@ -142,7 +60,7 @@ k_inject(Dev d, int mode, const AT* __restrict__ actions, const double* __restri
 //      k_advance at the end of the previous one, which also leaves the finished Sbus entry of every bus WITHOUT sgens and,
 //      for the buses with sgens, the load part of the injection (bus_ld).  So this launch has one thread per
 //      (PV bus, env) — 22 rows instead of 141 on the 141-bus feeder: q = a sqrt(s_max^2 - p^2) of the bus's sgens and
-//      Sbus = -((loads) - (sgens)) / sn, the same expressions in the same order as k_inject (bit-identical).
+//      Sbus = -((loads) - (sgens)) / sn, the same functions in the same order as k_inject (bit-identical).
 //      An env that auto-resets in this call (rare) refreshes ALL its loads here, its threads striding over the load buses.
 //      (n_sgb >= 1 always: build_plan refuses a net without sgens — no agents — so row 0, which does the step bookkeeping, exists.)
 //      Round 4: in step() of a handle without auto_reset these rows run in the prologue of k_nr_tree instead (nr_tree.hpp).
@@ -154,92 +72,33 @@ k_inject_sgen(Dev d, int mode, const AT* __restrict__ actions, int add_noise) {
   if (e >= d.B) return;
   const bool mlo_row = jb >= d.n_sgb;
   const int k = mlo_row ? d.mlo_pos[jb - d.n_sgb] : d.sgb_pos[jb];   // elimination position (n == slack: q only, no Sbus row)
-  bool act, ar = false;
-  if (mode == MODE_STEP) {
-    const bool dn = d.done[e] != 0;
-    ar = dn && d.auto_reset;
-    act = !dn || ar;
-  } else act = d.pending[e] != 0;
-  const uint32_t draw = mode == MODE_STEP ? d.draw[e] : d.adv_draw[e];
-  int64_t ar_row = 0;
-  if (ar) {
-    const int64_t start = sample_start_row(d, e, draw);
-    ar_row = start + 1;                          // t = self.steps == 1 (:100, :473)
-    if (jb == 0) d.start_row[e] = start;
-  }
-  if (jb == 0) {
-    d.active[e] = act ? 1 : 0;
-    if (mode == MODE_STEP) {
-      d.resetting[e] = ar ? 1 : 0;
-      d.adv_row[e] = (act && !ar) ? d.start_row[e] + d.steps[e] : -1; d.adv_draw[e] = draw;
-    }
-  }
-  if (!act) return;                              // frozen: q_new, Sbus stay as they are
+  const EnvTurn t = env_turn(d, mode, e);
+  if (jb == 0) note_turn(d, mode, e, t);
+  if (!t.act) return;                            // frozen: q_new, Sbus stay as they are
   double2* const sbp = (double2*)((char*)d.nrbuf + d.sb_off) + e;
-  // the load sum of a bus with several loads needs ONE thread (canonical order of its CSR list): formed here from the load
-  // values k_advance stored for this step (a restarting env forms all its sums below)
-  auto stored_load_sum = [&](int kk, double& Ps, double& Qs) {
-    Ps = 0.0; Qs = 0.0;
-    for (int i = d.load_ptr[kk]; i < d.load_ptr[kk + 1]; ++i) {
-      const int li = d.load_idx[i];
-      add_scaled(Ps, d.cur_pl[(size_t)li * d.Bp + e], d.load_scale[li]); add_scaled(Qs, d.cur_ql[(size_t)li * d.Bp + e], d.load_scale[li]);
-    }
-  };
-  if (mlo_row) {
-    if (ar || k >= d.n) return;
-    double Ps, Qs;
-    stored_load_sum(k, Ps, Qs);
-    sbp[(size_t)k * d.Bp] = make_double2(-Ps / d.sn, -Qs / d.sn);
+  double P, Q;
+  if (mlo_row) {   // the load sum of a bus with several loads needs ONE thread: formed here from the load values k_advance stored
+    if (t.ar || k >= d.n) return;                // (a restarting env forms all its sums below)
+    stored_load_sum(d, k, e, d.cur_pl, d.cur_ql, P, Q);
+    sbp[(size_t)k * d.Bp] = sbus_entry(P, Q, d.sn);
     return;
   }
-  double2* const bl = (double2*)d.bus_ld + (size_t)jb * d.Bp + e;
-  double P, Q;
-  if (ar) {
-    auto load_sum = [&](int kk, double& Ps, double& Qs) {
-      Ps = 0.0; Qs = 0.0;
-      for (int i = d.load_ptr[kk]; i < d.load_ptr[kk + 1]; ++i) {
-        const int li = d.load_idx[i];
-        const size_t o = (size_t)li * d.Bp + e;
-        const double p = profile_value(d, e, ar_row, draw, STREAM_LOAD_P, li, d.ns, add_noise);
-        const double q = profile_value(d, e, ar_row, draw, STREAM_LOAD_Q, li, d.ns + d.nl, add_noise);
-        d.cur_pl[o] = p; d.cur_ql[o] = q;
-        add_scaled(Ps, p, d.load_scale[li]); add_scaled(Qs, q, d.load_scale[li]);
-      }
-    };
-    load_sum(k, P, Q);
-    *bl = make_double2(P, Q);
+  if (t.ar) {
+    restart_load_sum(d, k, e, t.ar_row, t.draw, add_noise, P, Q);
+    ((double2*)d.bus_ld)[(size_t)jb * d.Bp + e] = make_double2(P, Q);
     for (int i = jb; i < d.n_lb; i += d.n_sgb) {   // the buses with loads but no sgens, shared out over this env's threads
       const int kk = d.lb_pos[i];
       double Ps, Qs;
-      load_sum(kk, Ps, Qs);
+      restart_load_sum(d, kk, e, t.ar_row, t.draw, add_noise, Ps, Qs);
       if (kk < d.n) {                             // a restarting env is not advanced by this call's k_advance: both Sbus buffers
-        const double2 v = make_double2(-Ps / d.sn, -Qs / d.sn);
+        const double2 v = sbus_entry(Ps, Qs, d.sn);
         sbp[(size_t)kk * d.Bp] = v;
         ((double2*)((char*)d.nrbuf + d.sb_off_alt))[(size_t)kk * d.Bp + e] = v;
       }
     }
-  } else if (d.load_ptr[k + 1] - d.load_ptr[k] > 1) stored_load_sum(k, P, Q);
-  else { const double2 v = *bl; P = v.x; Q = v.y; }
-  for (int i = d.sgen_ptr[k]; i < d.sgen_ptr[k + 1]; ++i) {
-    const int j = d.sgen_idx[i];
-    const size_t o = (size_t)j * d.Bp + e;
-    double p;
-    if (ar) { p = profile_value(d, e, ar_row, draw, STREAM_PV, j, 0, add_noise); d.cur_pv[o] = p; d.cur_q[o] = 0.0; }
-    else p = d.cur_pv[o];
-    const double sm = d.smax[j];
-    const double lim = sqrt(sm * sm - p * p);
-    double q;
-    if (mode == MODE_STEP && !ar) q = lim * (double)actions[(size_t)e * d.ns + j];
-    else if (d.reset_action) {
-      uint32_t x[4];
-      philox4x32_10((uint32_t)(d.env_id_offset + e), draw, STREAM_ACTION, (uint32_t)(j >> 1), d.seed_lo, d.seed_hi, x);
-      const double u = ((j & 1) ? u53(x[2], x[3]) : u53(x[0], x[1])) * (1.0 / 9007199254740992.0);
-      q = lim * (d.action_low + (d.action_high - d.action_low) * u);
-    } else q = 0.0;                              // base-net q_mvar (deepcopy of base_powergrid, :106)
-    d.q_new[o] = q;
-    sub_scaled(P, p, d.sgen_scale[j]); sub_scaled(Q, q, d.sgen_scale[j]);
-  }
-  if (k < d.n) sbp[(size_t)k * d.Bp] = make_double2(-P / d.sn, -Q / d.sn);
+  } else pv_bus_load_sum(d, jb, k, e, P, Q);
+  sub_bus_sgens(d, k, e, t, d.cur_pv, add_noise, [&](int j, size_t o, double p) { return d.q_new[o] = turn_q(d, mode, t, actions, e, j, p); }, P, Q);
+  if (k < d.n) sbp[(size_t)k * d.Bp] = sbus_entry(P, Q, d.sn);
 }
 
 // =================================================================================================
@@ -284,36 +143,39 @@ __global__ void __launch_bounds__(256) k_reset_begin(Dev d, const int64_t* __res
 //      write the buffer of the next solve (`sb_write_off`: the other one in step(), the same one in reset(), where the
 //      advance comes before the solve); the host flips the buffers after every step.
 // =================================================================================================
-// the pieces of k_advance as device functions:
-// Box-Muller pair of Philox block b of a stream: the two half-normal noise factors of columns 2b, 2b + 1
-__device__ __forceinline__ void noise_pair(const Dev& d, int e, uint32_t draw, int stream, int b, double& n0, double& n1) {
-  uint32_t x[4];
-  philox4x32_10((uint32_t)(d.env_id_offset + e), draw, (uint32_t)stream, (uint32_t)b, d.seed_lo, d.seed_hi, x);
-  const double u1 = (u53(x[0], x[1]) + 0.5) * (1.0 / 9007199254740992.0);
-  const double u2 = u53(x[2], x[3]) * (1.0 / 9007199254740992.0);
-  const double r = sqrt(-2.0 * log(u1));
-  double sn_, cs_;
-  sincos(2.0 * M_PI * u2, &sn_, &cs_);
-  n0 = fabs(r * cs_); n1 = fabs(r * sn_);
+// the pieces of k_advance and k_commit_fused as device functions (the noise is inject.hpp's noise_pair):
+// the solution (e, f, |V|, angle) of the node at position k (n == slack) of env e: Vout rows, S doubles apart
+__device__ __forceinline__ const double* node_vout(const Dev& d, int k, int e, size_t S) {
+  return d.nrbuf + ((size_t)d.r_vout + (size_t)VOF * k) * S + e;
+}
+__device__ __forceinline__ double node_vm(const Dev& d, int k, int e, size_t S) {
+  const double* vo = node_vout(d, k, e, S);
+  const double ek = vo[(size_t)VO_E * S], fk = vo[(size_t)VO_F * S];
+  return sqrt(ek * ek + fk * fk);
+}
+// current the slack node feeds into the network: I = Y_rr V_r + sum_neighbours Y_rk V_k
+__device__ __forceinline__ void slack_current(const Dev& d, int e, size_t S, double& ir, double& ii) {
+  ir = d.yrr0 * d.vroot; ii = d.yrr1 * d.vroot;
+  for (int j = 0; j < d.n_root_children; ++j) {
+    const double* cb = node_vout(d, d.root_children[j], e, S);
+    const double g = d.root_y[2 * j], b = d.root_y[2 * j + 1], ec = cb[(size_t)VO_E * S], fc = cb[(size_t)VO_F * S];
+    ir += g * ec - b * fc; ii += g * fc + b * ec;
+  }
 }
 // K6 commit of one res_bus row (ORIGINAL bus b_; bus fusion: several buses may share an electrical node) of env e, for envs whose
 // solve was accepted (pandapower pfsoln / _extract_results): vm_pu = |V|, va = angle(V), p_mw / q_mvar = bus demand (-Sbus sn) +
-// shunt |V|^2, slack = -(V conj(I)) sn.  WANT: the caller needs the row as res_bus holds it after this call in any case
-// (a fused commit + obs launch was tried and removed: profiles/r04_wide_kernel_parts_experiment.txt).
-template <bool WANT>
-__device__ __forceinline__ void commit_bus(const Dev& d, int b_, int e, size_t S, double& v, double& va, double& P, double& Q) {
+// shunt |V|^2, slack = -(V conj(I)) sn.
+// (One launch for commit + advance + get_obs is not built: at best it saves one launch gap)
+__device__ __forceinline__ void commit_bus(const Dev& d, int b_, int e, size_t S) {
   const size_t o = (size_t)b_ * S + e;
-  if (!d.commit[e]) {
-    if (WANT) { v = d.vm[o]; va = d.va[o]; P = d.res_p[o]; Q = d.res_q[o]; }
-    return;
-  }
+  if (!d.commit[e]) return;
   const int k = d.pos_of_obus[b_];               // elimination position of its node, n == slack
+  double v, va, P, Q;
   if (k < d.n) {
-    const double* vo = d.nrbuf + ((size_t)d.r_vout + (size_t)VOF * k) * S + e;
+    const double* vo = node_vout(d, k, e, S);
     const double2 sb = ((const double2*)((const char*)d.nrbuf + d.sb_off))[(size_t)k * S + e];
-    const double ek = vo[(size_t)VO_E * S], fk = vo[(size_t)VO_F * S];
-    v = sqrt(ek * ek + fk * fk);
-    va = atan2(fk, ek);
+    v = node_vm(d, k, e, S);
+    va = atan2(vo[(size_t)VO_F * S], vo[(size_t)VO_E * S]);
     P = -sb.x * d.sn; Q = -sb.y * d.sn;
     if (d.zip) {                                 // voltage-dependent loads (results_bus): the bus's loads x (cp + ci |V| + cz |V|^2), its
       const double ci = d.zip_c[2 * k], cz = d.zip_c[2 * k + 1];   // sgens as they are: demand + loads (vd - 1), the loads as the
@@ -329,31 +191,22 @@ __device__ __forceinline__ void commit_bus(const Dev& d, int b_, int e, size_t S
     }
   } else {
     v = d.vroot; va = 0.0;
-    double ir = d.yrr0 * d.vroot, ii = d.yrr1 * d.vroot;     // I = Y_rr V_r + sum_neighbours Y_rk V_k
-    for (int j = 0; j < d.n_root_children; ++j) {
-      const double* cb = d.nrbuf + ((size_t)d.r_vout + (size_t)VOF * d.root_children[j]) * S + e;
-      const double g = d.root_y[2 * j], b = d.root_y[2 * j + 1], ec = cb[(size_t)VO_E * S], fc = cb[(size_t)VO_F * S];
-      ir += g * ec - b * fc; ii += g * fc + b * ec;
-    }
+    double ir, ii;
+    slack_current(d, e, S, ir, ii);
     P = -(d.vroot * ir) * d.sn; Q = (d.vroot * ii) * d.sn;
   }
   d.va[o] = va;
   d.vm[o] = v;
-  if (d.cm_kind[b_] == 0) { P = P + d.shunt_p[k] * v * v; Q = Q + d.shunt_q[k] * v * v; d.res_p[o] = P; d.res_q[o] = Q; }
   // (a bus of a fused group reports its OWN elements: k_commit_fused wrote p_mw / q_mvar before this launch)
-  else if (WANT) { P = d.res_p[o]; Q = d.res_q[o]; }
+  if (d.cm_kind[b_] == 0) { P = P + d.shunt_p[k] * v * v; Q = Q + d.shunt_q[k] * v * v; d.res_p[o] = P; d.res_q[o] = Q; }   // (both loads ahead of both stores)
 }
 // PV columns 2b, 2b + 1 of the next profile row (one Philox block + one Box-Muller pair)
-template <bool WANT>
-__device__ __forceinline__ void advance_pv_pair(const Dev& d, int e, int b, int add_noise, size_t S, double& v0, double& v1) {
+__device__ __forceinline__ void advance_pv_pair(const Dev& d, int e, int b, int add_noise, size_t S) {
   const int j0 = 2 * b, j1 = 2 * b + 1;
   const int64_t row = d.adv_row[e];
-  if (row < 0 || row >= d.T) {                     // never read outside the table
-    if (WANT) { v0 = d.cur_pv[(size_t)j0 * S + e]; v1 = (j1 < d.ns) ? d.cur_pv[(size_t)j1 * S + e] : 0.0; }
-    return;
-  }
+  if (row < 0 || row >= d.T) return;               // never read outside the table
   const double* trow = d.table + (size_t)row * d.ncol;
-  v0 = trow[j0]; v1 = (j1 < d.ns) ? trow[j1] : 0.0;
+  double v0 = trow[j0], v1 = (j1 < d.ns) ? trow[j1] : 0.0;
   if (add_noise) {
     double n0, n1;
     noise_pair(d, e, d.adv_draw[e], STREAM_PV, b, n0, n1);
@@ -389,31 +242,24 @@ __device__ __forceinline__ void advance_load_pair(const Dev& d, int e, int b, in
     const int dd = d.ld_dest[li];
     const double sc = d.load_scale[li];
     const double ps = p * sc, qs = q * sc;
-    if ((dd & 3) == 0) sbw[(size_t)(dd >> 2) * S] = make_double2(-ps / d.sn, -qs / d.sn);
+    if ((dd & 3) == 0) sbw[(size_t)(dd >> 2) * S] = sbus_entry(ps, qs, d.sn);
     else if ((dd & 3) == 1) ((double2*)d.bus_ld)[(size_t)(dd >> 2) * S + e] = make_double2(ps, qs);
   };
   put(j0, p0, q0);
   if (has1) put(j1, p1, q1);
 }
 
-__device__ __forceinline__ void advance_body(const Dev& d, int add_noise, int do_profiles, int do_commit, uint32_t sb_write_off,
-                                             unsigned blk_x, unsigned blk_y) {
-  const int e = (int)(blk_x * 256u + threadIdx.x);
+// (do_commit only sizes the grid: launch_advance)
+__global__ void __launch_bounds__(256) k_advance(Dev d, int add_noise, int do_profiles, int do_commit, uint32_t sb_write_off) {
+  const int e = (int)(blockIdx.x * 256u + threadIdx.x);
   if (e >= d.B) return;
   const int npv = (d.ns + 1) >> 1, npl = (d.nl + 1) >> 1;
   const int npairs = do_profiles ? npv + npl : 0;
+  const int row = (int)blockIdx.y;
   const size_t S = (size_t)d.Bp;
-  if ((int)blk_y >= npairs) {                      // rows [npairs, npairs + nbo): thread = (original bus, env)
-    double v, va, P, Q;
-    commit_bus<false>(d, (int)blk_y - npairs, e, S, v, va, P, Q);
-    return;
-  }
-  if ((int)blk_y < npv) { double v0, v1; advance_pv_pair<false>(d, e, (int)blk_y, add_noise, S, v0, v1); }
-  else advance_load_pair(d, e, (int)blk_y - npv, add_noise, S, sb_write_off);
-}
-
-__global__ void __launch_bounds__(256) k_advance(Dev d, int add_noise, int do_profiles, int do_commit, uint32_t sb_write_off) {
-  advance_body(d, add_noise, do_profiles, do_commit, sb_write_off, blockIdx.x, blockIdx.y);
+  if (row >= npairs) commit_bus(d, row - npairs, e, S);   // rows [npairs, npairs + nbo): thread = (original bus, env)
+  else if (row < npv) advance_pv_pair(d, e, row, add_noise, S);
+  else advance_load_pair(d, e, row - npv, add_noise, S, sb_write_off);
 }
 
 // K6'  res_bus p_mw / q_mvar of the buses of FUSED groups (closed bus-bus switches): pandapower reports, per pandapower bus, the bus's
@@ -436,24 +282,15 @@ __global__ void __launch_bounds__(256) k_commit_fused(Dev d) {
   };
   const int i = blockIdx.y;
   const int b_ = d.fused_obus[i], k = d.pos_of_obus[b_];
-  double v = d.vroot;
-  if (k < d.n) {
-    const double* vo = d.nrbuf + ((size_t)d.r_vout + (size_t)VOF * k) * S + e;
-    const double ek = vo[(size_t)VO_E * S], fk = vo[(size_t)VO_F * S];
-    v = sqrt(ek * ek + fk * fk);
-  }
+  const double v = k < d.n ? node_vm(d, k, e, S) : d.vroot;
   double P, Q;
   own(i, P, Q);
   P += d.ob_shunt_p[i] * v * v; Q += d.ob_shunt_q[i] * v * v;
   if (d.cm_kind[b_] == 2) {                          // the ext_grid's own bus: minus the ext_grid's injection = (demand of the whole
     double Dp = 0.0, Dq = 0.0;                       // group) + (power the slack node feeds into the network)
     for (int m = 0; m < d.n_slack_group; ++m) { double p_, q_; own(d.slack_group[m], p_, q_); Dp += p_; Dq += q_; }
-    double ir = d.yrr0 * d.vroot, ii = d.yrr1 * d.vroot;
-    for (int j = 0; j < d.n_root_children; ++j) {
-      const double* cb = d.nrbuf + ((size_t)d.r_vout + (size_t)VOF * d.root_children[j]) * S + e;
-      const double g = d.root_y[2 * j], b = d.root_y[2 * j + 1], ec = cb[(size_t)VO_E * S], fc = cb[(size_t)VO_F * S];
-      ir += g * ec - b * fc; ii += g * fc + b * ec;
-    }
+    double ir, ii;
+    slack_current(d, e, S, ir, ii);
     P -= Dp + (d.vroot * ir) * d.sn; Q -= Dq - (d.vroot * ii) * d.sn;
   }
   d.res_p[(size_t)b_ * S + e] = P; d.res_q[(size_t)b_ * S + e] = Q;
@@ -469,9 +306,10 @@ __global__ void __launch_bounds__(256) k_commit_fused(Dev d) {
 // =================================================================================================
 #define GATHER_HAS_EXTRA 0x40000000   // flag bit in a row descriptor: the column has add-back rows (x_ptr/x_row)
 template <typename T>
-__device__ __forceinline__ void gather_body(const double* __restrict__ base, const int32_t* rows_g, const double* scales_g,
-                                            double scale_all, const int32_t* x_ptr_g, const int32_t* x_row_g,
-                                            T* __restrict__ out, int C, int B, int Bp, unsigned blk_x, unsigned blk_y, unsigned grd_x, unsigned grd_y) {
+__global__ void __launch_bounds__(256)
+k_gather(const double* __restrict__ base, const int32_t* rows_g, const double* scales_g,
+         double scale_all, const int32_t* x_ptr_g, const int32_t* x_row_g,
+         T* __restrict__ out, int C, int B, int Bp) {
   __shared__ T tile[64][65];                      // output-typed tile: 16.6 KB for f32 -> 8 workgroups per CU
   // descriptors are wave-uniform (a wave handles whole columns): read them through the constant
   // address space -> s_load on the scalar unit, no VMEM round trip ahead of the data loads
@@ -482,10 +320,10 @@ __device__ __forceinline__ void gather_body(const double* __restrict__ base, con
   // XCD-aware tile order: consecutive workgroups land on consecutive XCDs (block b on XCD b % 8, observed; only speed depends
   // on it), and a source row of 64 envs is read by every column tile whose zones contain that bus (2.4 of them on average) —
   // so all column tiles of an env tile go to ONE XCD, whose L2 then serves the re-reads: XCD k takes env tiles k, k + 8, ...
-  unsigned bx = blk_x, by = blk_y;
-  if ((grd_y & 7u) == 0u) {
-    const unsigned lin = blk_y * grd_x + blk_x, xcd = lin & 7u, slot = lin >> 3;
-    by = (slot / grd_x) * 8u + xcd; bx = slot % grd_x;
+  unsigned bx = blockIdx.x, by = blockIdx.y;
+  if ((gridDim.y & 7u) == 0u) {
+    const unsigned lin = blockIdx.y * gridDim.x + blockIdx.x, xcd = lin & 7u, slot = lin >> 3;
+    by = (slot / gridDim.x) * 8u + xcd; bx = slot % gridDim.x;
   }
   const int c0 = (int)bx * 64, e0 = (int)by * 64;
   const int tx = threadIdx.x & 63, ty = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -527,14 +365,6 @@ __device__ __forceinline__ void gather_body(const double* __restrict__ base, con
       for (int u = 0; u < 4; ++u) if (c + u < C) o[u] = tile[q4 + u][r];
     }
   }
-}
-
-template <typename T>
-__global__ void __launch_bounds__(256)
-k_gather(const double* __restrict__ base, const int32_t* rows_g, const double* scales_g,
-         double scale_all, const int32_t* x_ptr_g, const int32_t* x_row_g,
-         T* __restrict__ out, int C, int B, int Bp) {
-  gather_body<T>(base, rows_g, scales_g, scale_all, x_ptr_g, x_row_g, out, C, B, Bp, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
 }
 
 // env-major [B, n] -> env-minor [n][Bp] (zero-fills the pad lanes)

@@ -104,12 +104,10 @@ struct Dev {
   const double* zip_c; uint32_t zip_c_bytes;     // [n + 2][2] by position: (ci, cz) (plan.hpp Plan::zip_c)
 };
 
-// One term of a bus's element sum, PD = sum p_mw x scaling (pd2ppc).  k_inject, k_inject_sgen, the prologue of k_nr_tree and the control
-// loops (ctlloop.hpp) form the same sums and must land on the same bits, so the fused multiply-add is spelled out here: written as
-// `P += p * s` the compiler fused it in some of these loops and not in others.  Scalings of 1 cannot show that (both forms are then
-// P + p); a bus with several loads and scalings other than 1 did (tests/test_element_edges_gpu.py).
-__device__ __forceinline__ void add_scaled(double& acc, double x, double s) { acc = fma(x, s, acc); }
-__device__ __forceinline__ void sub_scaled(double& acc, double x, double s) { acc = fma(-x, s, acc); }
+// ---- the bus injection every injecting kernel shares (inject.hpp: device functions on Dev)
+}  // namespace mapdn
+#include "inject.hpp"
+namespace mapdn {
 
 void launch_inject(const Dev& d, int mode, const void* actions, int dtype, const double* pl, const double* ql,
                    const double* pv, const double* q, int add_noise, hipStream_t st);

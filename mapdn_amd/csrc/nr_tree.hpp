@@ -180,9 +180,9 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
   const unsigned voS = d.sb_off + e * 16u;       // the injection Sbus, one (re, im) pair row per NODE (entry n + 1, the trash node idle steps work on, stays 0)
   // ---- fused PV-bus injection (step() of a handle without auto_reset; otherwise k_inject_sgen ran as a launch of its own).
   // _clip_reactive_power (voltage_control_env.py:568-572): q = a sqrt(s_max^2 - p^2) of the sgens of every PV bus of this workgroup's
-  // envs, Sbus = -((loads) - (sgens)) / sn with the load part k_advance left in bus_ld — the expressions of k_inject_sgen for an env
-  // that is not restarting, in the same order (bit-identical: test_fused_injection_equals_the_injection_launch) — and the step
-  // bookkeeping its first row does.  One item per (PV bus, env), env fastest; a launch of its own cost 6.8 us for 90 k such
+  // envs, Sbus = -((loads) - (sgens)) / sn with the load part k_advance left in bus_ld.  inject.hpp is the definition this copy has to
+  // match: what k_inject_sgen calls there for an env that is not restarting, in the same order (bit-identical:
+  // test_fused_injection_equals_the_injection_launch*), and note_turn's bookkeeping.  One item per (PV bus, env), env fastest; a launch of its own cost 6.8 us for 90 k such
   // items (launch + a chain of dependent loads); here the chain runs once per workgroup beside the LDS initialisation.  The
   // Sbus entries are read back by this workgroup only, after the barrier that ends the prologue.
   if (d.fi_actions) {

@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(DL * DS) k_opf_linearise(Dev d, OpfState s) {
       const OpfVec x{s.X + (size_t)j * 2 * Bp + ee, Bp}, w{s.W + (size_t)j * 2 * Bp + ee, Bp};
       const size_t o = (size_t)j * Bp + ee;
       const double p = d.cur_pv[o], sm = d.smax[j];
-      const double wj = sqrt(sm * sm - p * p) * d.sgen_scale[j] / d.sn;
+      const double wj = q_limit(p, sm) * d.sgen_scale[j] / d.sn;
       opf_solve_column(s.sg_node[j], wj, n, s.par, fac, x, xs);
       for (int k = 0; k < n; ++k) {                // S, then dV = (u + j dtheta) V in place of (dtheta, u)
         const double th = x[(size_t)k * xs], u = x[(size_t)k * xs + 1];
