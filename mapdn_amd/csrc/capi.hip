@@ -335,7 +335,11 @@ static int validate(mapdn_handle* h, const mapdn_env_config& c) {
 static int settle_general_solver(mapdn_handle* h) {
   const Plan& P = h->plan;
   Dev& d = h->d;
-  if (h->solver == 2) { d.dn_N = (2 * P.n + 15) / 16 * 16; d.dn_lda = d.dn_N + 2; return MAPDN_OK; }
+  if (h->solver == 2) {
+    d.dn_N = (2 * P.n + 15) / 16 * 16; d.dn_lda = d.dn_N + 2;
+    h->lds_bytes = nr_dense_lds_bytes(d.dn_N, d.dn_lda, P.n);   // (setup_dense finds the same once the slab exists)
+    return MAPDN_OK;
+  }
   if (h->solver != 1) return MAPDN_OK;
   if (h->knobs.sp_lanes) h->sp_lanes = h->knobs.sp_lanes;      // pinned envs per workgroup (16 / 8 / 4 / 2)
   else {

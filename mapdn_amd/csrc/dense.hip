@@ -279,6 +279,11 @@ size_t nr_dense_lds_bytes(const Dev& d) {
   const int W = dense_waves(d);
   return dense_lds_doubles(d.dn_N, d.dn_lda, d.n, 64 * W, d.dn_A != nullptr) * sizeof(double);
 }
+// the same from the Jacobian order alone (host-only handles have no slab: what settle_general_solver reports before any device call)
+size_t nr_dense_lds_bytes(int N, int lda, int n) {
+  const bool ga = nr_dense_ga(N);
+  return dense_lds_doubles(N, lda, n, 64 * nr_dense_waves(N, ga), ga) * sizeof(double);
+}
 
 // dynamic LDS limit of k_nr_dense: the CU's 160 KB minus the 256 bytes of static LDS that __syncthreads_and's
 // cross-wave reduction allocates (asking for all 160 KB makes hipFuncSetAttribute fail with invalid value)

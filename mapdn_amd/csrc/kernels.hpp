@@ -148,6 +148,7 @@ void launch_nr_sparse(const Dev& d, int mode, double* reward, uint8_t* term, dou
 static inline bool nr_dense_ga(int N) { return N > 128; }
 int nr_dense_waves(int N, bool ga);
 size_t nr_dense_lds_bytes(const Dev& d);
+size_t nr_dense_lds_bytes(int N, int lda, int n);
 int nr_dense_prepare(const Dev& d);
 void launch_nr_dense(const Dev& d, int mode, double* reward, uint8_t* term, double* info, hipStream_t st);
 int dense_solve_debug(const double* A, const double* b, double* x, int n, int batch, hipStream_t st);

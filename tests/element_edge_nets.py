@@ -226,7 +226,13 @@ def _all_pv():
 
 @functools.lru_cache(maxsize=None)
 def make(name):
-    """(NetSpec, Profiles) of a net of this module; cached, so treat both as read-only"""
+    """(NetSpec, Profiles) of a net of this module, or of a key of tests/meshed_edge_nets.py (whose step() tests replay the plans below);
+    cached, so treat both as read-only"""
+    if name not in NETS:
+        from tests import meshed_edge_nets
+        if name not in meshed_edge_nets.KEYS:
+            raise KeyError(name)
+        return meshed_edge_nets.make_net(name)
     if name == "one_sgen":
         return _one_sgen()
     if name == "all_pv":
@@ -280,13 +286,14 @@ PLANS = dict(auto=dict(auto_reset=True, dtype=np.float64, calls=10, forced_call=
              frozen=dict(auto_reset=False, dtype=np.float32, calls=7, forced_call=1, reset_before=(4,)))
 
 
-def actions(name, plan, B=B_WATCH):
-    """[calls, B, ns] seeded actions in (-0.8, 0.8) of a plan, in its dtype (float32: rounded once; the oracle gets these values as float64)"""
+def actions(name, plan, B=B_WATCH, unsolvable=UNSOLVABLE):
+    """[calls, B, ns] seeded actions in (-0.8, 0.8) of a plan, in its dtype (float32: rounded once; the oracle gets these values as float64);
+    `unsolvable`: the forced action (a stiffer net needs a larger one to have no power-flow solution)"""
     p = PLANS[plan]
     net, _ = make(name)
     rng = np.random.default_rng(sum(map(ord, name + plan)))
     a = rng.uniform(-0.8, 0.8, (p["calls"], B, net.n_sgen))
-    a[p["forced_call"], FORCED_ENV] = UNSOLVABLE
+    a[p["forced_call"], FORCED_ENV] = unsolvable
     return a.astype(p["dtype"])
 
 
@@ -327,13 +334,13 @@ def first_draw_reset(o, start=None):
     return out
 
 
-def replay(name, plan):
+def replay(name, plan, unsolvable=UNSOLVABLE):
     """Generator over a plan.  Yields ("reset", None, None, oracles) after every whole-batch reset and ("step", call, (act, expect), oracles)
     after every call: act [B, ns] in the plan's dtype, expect[e] = (kind, reward, terminated, info dict or None) with kind "step" |
     "restart" (auto_reset: this call was the env's reset) | "frozen"; the oracles are in the state after that call."""
     p = PLANS[plan]
     os_ = oracles(name)
-    acts = actions(name, plan)
+    acts = actions(name, plan, unsolvable=unsolvable)
     for o in os_:
         first_draw_reset(o)
     yield "reset", None, None, os_

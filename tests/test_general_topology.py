@@ -10,6 +10,7 @@ import pytest
 from mapdn_amd import _lib
 from mapdn_amd.netspec import NetSpec, Profiles, add_lines, case33_meshed, make_case
 from tests.edge_rule import same_newton_count
+from tests.meshed_edge_nets import dense_newton, emulate_program as _emulate_program, positions as _positions
 from oracle.pp_restated import make_ybus, residual_inf, runpp_restated
 
 
@@ -105,7 +106,6 @@ def test_large_meshed_nets_are_accepted_and_disconnected_ones_refused_loudly(mon
 
 def test_oracle_on_meshed_nets_meets_the_residual_certificate_and_a_dense_solve():
     """the checker itself on loops: SuperLU path vs the residual certificate and vs a dense numpy Newton iteration"""
-    from oracle.pp_restated import bus_demand, make_sbus
     for seed in range(6):
         net, prof = random_meshed_net(seed)
         rng = np.random.default_rng(seed)
@@ -114,22 +114,8 @@ def test_oracle_on_meshed_nets_meets_the_residual_certificate_and_a_dense_solve(
         res = runpp_restated(net, prof.load_p[r], prof.load_q[r], prof.pv[r], qs)
         assert res.converged
         assert residual_inf(net, res.V, prof.load_p[r], prof.load_q[r], prof.pv[r], qs) < 1e-8 / net.sn_mva
-        # independent dense Newton in rectangular coordinates
-        y = make_ybus(net)[0].toarray()
-        sb = make_sbus(net, *bus_demand(net, prof.load_p[r], prof.load_q[r], prof.pv[r], qs))
-        pq = np.array([b for b in range(net.n_bus) if b != net.ext_grid_bus])
-        v = np.full(net.n_bus, net.ext_grid_vm_pu, complex)
-        for _ in range(20):
-            i_ = y @ v
-            mis = (v * np.conj(i_) - sb)[pq]
-            # dS/de = diag(conj(I)) + diag(V) conj(Y),  dS/df = j diag(conj(I)) - j diag(V) conj(Y)
-            de = np.diag(np.conj(i_)) + np.diag(v) @ np.conj(y)
-            df = 1j * np.diag(np.conj(i_)) - 1j * np.diag(v) @ np.conj(y)
-            J = np.block([[de[np.ix_(pq, pq)].real, df[np.ix_(pq, pq)].real], [de[np.ix_(pq, pq)].imag, df[np.ix_(pq, pq)].imag]])
-            dx = np.linalg.solve(J, -np.r_[mis.real, mis.imag])
-            v[pq] += dx[:len(pq)] + 1j * dx[len(pq):]
-            if np.abs(dx).max() < 1e-14:
-                break
+        # independent dense Newton in rectangular coordinates (tests/meshed_edge_nets.py)
+        v = dense_newton(net, prof.load_p[r], prof.load_q[r], prof.pv[r], qs, n_it=20)
         assert np.abs(v - res.V).max() < 1e-9
 
 
@@ -279,39 +265,7 @@ def test_meshed_env_episode_matches_the_oracle_env(solver, which, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ sparse program (CPU)
-def _emulate_program(n, S, dims, ops, slots_ij, J, b):
-    """execute the host-compiled elimination program in numpy: blocks B[slot] (2x2), rhs as [b | 0] blocks"""
-    nblk, nph = dims[0], dims[2]
-    B = np.zeros((nblk, 2, 2))
-    for i in range(n):
-        B[i] = J[2 * i:2 * i + 2, 2 * i:2 * i + 2]
-        B[n + i][:, 0] = b[2 * i:2 * i + 2]
-    covered = np.zeros((n, n), bool)
-    for i, j, s in slots_ij.reshape(-1, 3):
-        B[s] = J[2 * i:2 * i + 2, 2 * j:2 * j + 2]
-        covered[i, j] = True
-    for i in range(n):
-        for j in range(n):
-            if i != j and not covered[i, j]:
-                assert not J[2 * i:2 * i + 2, 2 * j:2 * j + 2].any()      # every structural block has a slot
-    ops = ops.reshape(nph, S, 4)
-    for p in range(nph):
-        rd = [(B[a].copy(), B[bb].copy(), B[c].copy()) for (t, c, a, bb) in ops[p]]          # all lanes read, then all write
-        writes = set()
-        hints = {int(t) >> 8 for (t, c, a, bb) in ops[p]}
-        assert len(hints) == 1                                        # the phase hints are wave-uniform
-        kinds = {int(t) & 255 for (t, c, a, bb) in ops[p]}
-        assert ((1 in kinds) == bool(next(iter(hints)) & 1)) and ((3 in kinds) == bool(next(iter(hints)) & 2))
-        for (t, c, a, bb), (Aa, Bb, Cc) in zip(ops[p], rd):
-            t = int(t) & 255
-            if t == 0:
-                continue
-            assert c not in writes, "two writes of one block in a phase"
-            writes.add(c)
-            B[c] = np.linalg.inv(Aa) if t == 1 else (Aa @ Bb if t == 2 else Cc - Aa @ Bb)
-    return np.concatenate([B[n + i][:, 0] for i in range(n)])
-
-
+# (the numpy interpreter of the program and the position export live in tests/meshed_edge_nets.py, which runs them on more shapes)
 @pytest.mark.parametrize("which,S", [("case33_tie5", 4), ("case33_tie5", 16), ("rand3", 8), ("rand6", 32), ("case141_ties", 8), ("case322_ties", 16), ("case141_radial", 8)])
 def test_sparse_elimination_program_solves_the_jacobian(which, S):
     """host symbolic factorisation (minimum degree, fill) + list-scheduled block program, executed in numpy, against
@@ -357,14 +311,3 @@ def test_sparse_elimination_program_solves_the_jacobian(which, S):
         assert dims[1] == 0 and nph < 200                # a tree has no fill; list scheduling finds its parallelism
     lib.mapdn_destroy(h)
 
-
-def _positions(lib, h, net):
-    """bus id of every position (position n = slack): meshed plans use ascending bus ids, radial ones export it"""
-    n = net.n_bus - 1
-    dims = _lib.CDims()
-    assert lib.mapdn_dims(h, C.byref(dims)) == 0
-    if dims.is_radial:
-        fac = np.zeros((n, 12)); bop = np.zeros(n + 1, np.int32)
-        assert lib.mapdn_get_flat_factors(h, _lib._p(fac, _lib._pd), _lib._p(bop, _lib._pi)) == 0
-        return bop.tolist()
-    return [b for b in range(net.n_bus) if b != net.ext_grid_bus] + [int(net.ext_grid_bus)]
