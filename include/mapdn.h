@@ -736,6 +736,32 @@ int mapdn_opf_probe(mapdn_handle* h, const mapdn_opf_config* cfg, const double* 
                     double* g, double* H, double* loss_mw, double* violation, double* d, double* y, uint8_t* linearised,
                     uint8_t* qp_capped, void* stream);
 
+/* ---- What-if: the reward and info of candidate actions without a step.
+ * For every env e and candidate k: exactly what mapdn_step with actions[e][k] would report as reward and info from the env's current
+ * state (voltage_control_env.py:178-196, 548-623) — the loads and PV of the current profile row, q_j = sqrt(s_max_j^2 - p_j^2) a_j by
+ * the step path's own function, the handle's own power flow (tree, sparse or dense; DC start, ZIP loads and fused buses included), then
+ * _calc_reward or the unsolvable branch of step() — and nothing of that state is committed or advanced.  Env-major buffers:
+ *   actions    [B, K, ns] of actions_dtype (MAPDN_F32 / MAPDN_F64, widened as mapdn_step widens them); K = n_candidates,
+ *              1 ... MAPDN_WHATIF_MAX_CANDIDATES
+ *   reward     f64 [B, K];   info f64 [B, K, MAPDN_N_INFO] (column order as above)
+ *   status     u8 [B, K], the values of the droop / OPF codes that apply:
+ *              0 solved: the 11 infos of a converged step; iterations = the Newton count of the candidate's solve; vm_pu = the solved |V|
+ *              2 the power flow did not converge: as step() reports it — the statistics of the committed state, reward - 200,
+ *                destroy = 1, totally_controllable_ratio = 0, q_loss = mean |q| of the candidate's raw q; iterations as above; vm_pu NaN
+ *              3 not evaluated: step() would not solve this env (terminated and frozen, or waiting for its auto-reset restart):
+ *                reward, info and vm_pu NaN, iterations 0
+ *   iterations i32 [B, K] or NULL;   vm_pu f64 [B, K, nb] or NULL
+ * Device pointers on `stream`.  Only enqueues (three launches per candidate: the candidate's Sbus rows, the solve, the scoring); no
+ * host synchronisation; the workspace, which does not grow with K, is allocated on the first call.  An env's row has the same bits
+ * whatever B, K, the env's place in the batch and the other candidates are.  The obs, state, results, returns, counters, flags, RNG
+ * draws and the next mapdn_step are what they would have been without the call, also after mapdn_solve_only.
+ * Refused, by name in mapdn_last_error and with nothing launched: MAPDN_E_INVALID for a NULL actions / reward / info / status, a bad
+ * dtype, n_candidates < 1 or > MAPDN_WHATIF_MAX_CANDIDATES (checked on host-only handles too); MAPDN_E_STATE before mapdn_reset and on
+ * a host-only handle. */
+#define MAPDN_WHATIF_MAX_CANDIDATES 1024
+int mapdn_evaluate_actions(mapdn_handle* h, const void* actions, int32_t actions_dtype, int32_t n_candidates,
+                           double* reward, double* info, uint8_t* status, int32_t* iterations, double* vm_pu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 // baselines_host.hpp — the host side of the traditional baselines (mapdn_droop_actions, mapdn_opf_actions, mapdn_opf_probe): their
-// configs' defaults and refusals, their workspaces, and the one loop driver both run in (the device side of that frame: ctlloop.hpp).
+// configs' defaults and refusals, their workspaces, and the one loop driver both run in (the device side of that frame: ctlloop.hpp);
+// and of mapdn_evaluate_actions, which scores candidate actions in the same frame (whatif_prepare, whatif_run at the end).
 // Included by capi.hip after mapdn_handle and its helpers (dalloc, dupload, nr_launch, transpose_out), outside its extern "C" block;
-// the three entry points stay there.
+// the entry points stay there.
 #pragma once
 
 // ---- the frame.  Before the first solve: nobody counted yet in n_active[0 .. solves]; an Sbus that holds
@@ -246,6 +247,43 @@ static int opf_probe(mapdn_handle* h, const mapdn_opf_config& c, const double* a
   if (y) transpose_out(h, s.qy, 1.0, iota, y, ns + n, st);
   if (linearised) launch_copy_u8(s.lin, linearised, dv.B, st);
   if (qp_capped) launch_copy_u8(s.qp_capped, qp_capped, dv.B, st);
+  HIPCHK(h, hipGetLastError());
+  return MAPDN_OK;
+}
+
+// ---- mapdn_evaluate_actions (whatif.hip): the workspace of the frame (the CtlLoop arrays, sized like droop's), once per handle.
+// Nothing in it grows with the number of candidates: only the caller's outputs do.
+static int whatif_prepare(mapdn_handle* h) {
+  if (h->whatif_ready) return MAPDN_OK;
+  WhatifState& s = h->whatif;
+  const size_t Bp = h->d.Bp, ns = (size_t)h->plan.ns;
+  int32_t *iters = nullptr, *nr_iters = nullptr, *n_active = nullptr; uint8_t *status = nullptr, *act = nullptr, *nr_conv = nullptr;
+  int rc;
+  if ((rc = dalloc(h, &s.a, ns * Bp)) || (rc = dalloc(h, &iters, Bp)) || (rc = dalloc(h, &nr_iters, Bp)) || (rc = dalloc(h, &status, Bp)) ||
+      (rc = dalloc(h, &act, Bp)) || (rc = dalloc(h, &nr_conv, Bp)) || (rc = dalloc(h, &n_active, 1)))
+    return rc;
+  s.a_sol = nullptr; s.iters = iters; s.nr_iters = nr_iters; s.status = status; s.act = act; s.nr_conv = nr_conv; s.n_active = n_active;
+  s.vm_row = h->vm_row; s.max_iter = 0;
+  h->whatif_ready = true;
+  return MAPDN_OK;
+}
+
+// The frame without a stop test, so without a poll: ctl_begin, then per candidate the start launch (the candidate's Sbus rows), the
+// solve on the frame's active set and k_whatif_score.  Only enqueues.  Writes what ctl_drive writes (the PV-bus and several-load-bus
+// entries of the Sbus buffer the next solve reads, all of it when Sbus is stale; the solver's Vout rows) and the caller's outputs.
+static int whatif_run(mapdn_handle* h, const void* actions, int dtype, int K, double* reward, double* info, uint8_t* status,
+                      int32_t* iterations, double* vm_pu, hipStream_t st) {
+  if (const int rc = whatif_prepare(h)) return rc;
+  const Dev& d = h->d;
+  WhatifState s = h->whatif;
+  s.K = K; s.reward = reward; s.info = info; s.status_out = status; s.iters_out = iterations; s.vm_out = vm_pu;
+  Dev dd;
+  if (const int rc = ctl_begin(h, s, 0, st, &dd)) return rc;
+  for (int k = 0; k < K; ++k) {
+    launch_whatif_start(d, s, actions, dtype, k, st);
+    nr_launch(h, MODE_SOLVE, nullptr, nullptr, nullptr, st, nullptr, 0, &dd);
+    launch_whatif_score(d, s, k, st);
+  }
   HIPCHK(h, hipGetLastError());
   return MAPDN_OK;
 }

@@ -99,6 +99,9 @@ struct mapdn_handle {
   // OPF baseline (mapdn_opf_actions): likewise
   OpfState opf{};
   bool opf_ready = false;
+  // mapdn_evaluate_actions: the frame's workspace, likewise
+  WhatifState whatif{};
+  bool whatif_ready = false;
   // res_line / res_trafo (mapdn_get_branch_results, mapdn_get_loading_summary): the plan's branch records with the ratings of
   // mapdn_set_branch_ratings folded in, and their device copy
   std::vector<BranchRec> branches;
@@ -1262,6 +1265,21 @@ int mapdn_opf_probe(mapdn_handle* h, const mapdn_opf_config* cfg, const double* 
   if (!h->was_reset) { h->err = "opf_probe before reset"; return MAPDN_E_STATE; }
   HIPCHK(h, hipSetDevice(h->device));
   return opf_probe(h, c, a, ns, v_re, v_im, vm, S, g, H, loss_mw, violation, d, y, linearised, qp_capped, (hipStream_t)stream);
+} MAPDN_CATCH(h)
+
+// What step() would report for n_candidates joint actions of every env, without taking the step (whatif.hip; whatif_run).  The
+// argument checks come first, so that a host-only handle names a bad argument too; nothing is launched on a refusal.
+int mapdn_evaluate_actions(mapdn_handle* h, const void* actions, int32_t actions_dtype, int32_t n_candidates, double* reward, double* info,
+                           uint8_t* status, int32_t* iterations, double* vm_pu, void* stream) try {
+  if (!h) return MAPDN_E_INVALID;
+  if (!actions || !reward || !info || !status) return api_fail(h, MAPDN_E_INVALID, "evaluate_actions: null buffer (actions, reward, info and status are required)");
+  if (actions_dtype != MAPDN_F32 && actions_dtype != MAPDN_F64) return api_fail(h, MAPDN_E_INVALID, "evaluate_actions: bad actions dtype");
+  if (n_candidates < 1 || n_candidates > MAPDN_WHATIF_MAX_CANDIDATES)
+    return api_fail(h, MAPDN_E_INVALID, "evaluate_actions: n_candidates must lie in 1 ... 1024 (MAPDN_WHATIF_MAX_CANDIDATES)");
+  NEEDDEV(h);
+  if (!h->was_reset) { h->err = "evaluate_actions before reset"; return MAPDN_E_STATE; }
+  HIPCHK(h, hipSetDevice(h->device));
+  return whatif_run(h, actions, actions_dtype, n_candidates, reward, info, status, iterations, vm_pu, (hipStream_t)stream);
 } MAPDN_CATCH(h)
 
 // ---- the PPO half of MAPPO / IPPO's update (csrc/ppo.hip): argument checks here, nothing is launched on a refusal

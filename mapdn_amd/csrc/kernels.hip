@@ -560,3 +560,5 @@ void launch_stats(const Dev& d, long long* out, hipStream_t st) { hipLaunchKerne
 #include "droop.hip"
 // ... and the OPF baseline's kernels (opf.hip); the steps the two update kernels share are ctlloop.hpp's
 #include "opf.hip"
+// ... and the candidate scoring of mapdn_evaluate_actions (whatif.hip), which runs in the same frame
+#include "whatif.hip"

@@ -197,6 +197,18 @@ void launch_opf_update(const Dev& d, const OpfState& s, int iter, hipStream_t st
 void launch_opf_linearise(const Dev& d, const OpfState& s, hipStream_t st);
 void launch_opf_qp(const Dev& d, const OpfState& s, hipStream_t st);
 
+// ---- mapdn_evaluate_actions (whatif.hip, whatif.hpp; baselines_host.hpp whatif_run): K candidate actions per env scored in the frame.
+// Per-(env, candidate) status as in include/mapdn.h: the values of the droop / OPF codes that apply.
+enum { WHATIF_SOLVED = 0, WHATIF_PF_FAILED = 2, WHATIF_STOPPED = CTL_STOPPED };
+struct WhatifState : CtlLoop {       // (vm_out here: [B][K][nbo], or nullptr; a_sol, n_active: not used)
+  int32_t K;
+  double *reward, *info;             // [B][K], [B][K][MAPDN_N_INFO]
+  uint8_t* status_out;               // [B][K]
+  int32_t* iters_out;                // [B][K] Newton iterations of the candidate's solve, or nullptr
+};
+void launch_whatif_start(const Dev& d, const WhatifState& s, const void* actions, int dtype, int k, hipStream_t st);
+void launch_whatif_score(const Dev& d, const WhatifState& s, int k, hipStream_t st);
+
 // ---- res_line / res_trafo (branch.hip, branch.hpp; mapdn_get_branch_results, mapdn_get_loading_summary).  Their own small argument
 // blocks: Dev stays what every other launch takes.
 enum { BR_TILE = 16, LS_WAVES = 8 };

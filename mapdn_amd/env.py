@@ -465,6 +465,56 @@ class VoltageControlBatch:
                                                    loss.data_ptr(), viol.data_ptr(), it.data_ptr(), st.data_ptr(), self._stream()), self._h)
         return (act, loss, viol, it, st, vm) if vm_pu else (act, loss, viol, it, st)
 
+    def evaluate_actions(self, actions, vm_pu=False):
+        """What step(actions[:, k]) would return as reward and info from the current state of every env, for K candidate joint actions
+        at once and without taking the step (mapdn_evaluate_actions, include/mapdn.h).  actions: [B, K, n_sgen] float32 / float64
+        ([B, n_sgen]: K = 1), passed through as step() passes them.  Returns (reward float64 [B, K], info float64 [B, K, 11] in
+        INFO_KEYS order, status uint8 [B, K]: 0 solved, 2 the power flow did not converge — the row is what step() reports then:
+        reward - 200, destroy = 1 —, 3 not evaluated: step() would not solve this env, NaN row; iterations int32 [B, K] Newton
+        iterations), and vm_pu float64 [B, K, n_bus] (NaN for status 2 and 3) when vm_pu=True.  The env's state and its next step()
+        are not affected."""
+        a = actions
+        if not torch.is_tensor(a):
+            a = torch.as_tensor(np.asarray(a), device=self.device)
+        if a.device != self.device:
+            a = a.to(self.device)
+        if a.dtype not in (torch.float32, torch.float64):
+            a = a.to(torch.float64)
+        B, dv, f64 = self.n_envs, self.device, torch.float64
+        if a.dim() == 2:
+            a = a.reshape(B, 1, self.n_sgen)
+        if a.dim() != 3 or a.shape[0] != B or a.shape[2] != self.n_sgen or a.shape[1] < 1:
+            raise ValueError(f"evaluate_actions: actions must be [{B}, K, {self.n_sgen}] or [{B}, {self.n_sgen}], got {tuple(a.shape)}")
+        a = a.contiguous()
+        K = int(a.shape[1])
+        reward = torch.empty(B, K, dtype=f64, device=dv)
+        info = torch.empty(B, K, N_INFO, dtype=f64, device=dv)
+        st = torch.empty(B, K, dtype=torch.uint8, device=dv)
+        it = torch.empty(B, K, dtype=torch.int32, device=dv)
+        vm = torch.empty(B, K, self.n_bus, dtype=f64, device=dv) if vm_pu else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mapdn_evaluate_actions(self._h, a.data_ptr(), self._code(a.dtype), K, reward.data_ptr(), info.data_ptr(),
+                                                        st.data_ptr(), it.data_ptr(), vm.data_ptr() if vm_pu else None,
+                                                        self._stream()), self._h)
+        return (reward, info, st, it, vm) if vm_pu else (reward, info, st, it)
+
+    def difference_rewards(self, actions, default=0.0):
+        """Ground-truth difference rewards of a joint action [B, n_agents]: r(a) - r(a with agent i's entry replaced by `default`), by one
+        evaluate_actions call on n_agents + 1 candidates (the joint action first).  Returns (reward float64 [B], difference float64
+        [B, n_agents], status uint8 [B, n_agents + 1] of the candidates)."""
+        a = actions
+        if not torch.is_tensor(a):
+            a = torch.as_tensor(np.asarray(a), device=self.device)
+        if a.dtype not in (torch.float32, torch.float64):
+            a = a.to(torch.float64)
+        a = a.to(self.device).reshape(self.n_envs, self.n_sgen)
+        n = self.n_sgen
+        cand = a.unsqueeze(1).repeat(1, n + 1, 1)
+        idx = torch.arange(n, device=self.device)
+        cand[:, idx + 1, idx] = default
+        reward, _, st, _ = self.evaluate_actions(cand)
+        return reward[:, 0], reward[:, :1] - reward[:, 1:], st
+
     def opf_probe(self, a, config=None):
         """Diagnostic (mapdn_opf_probe, include/mapdn.h): one linearisation and one QP of the OPF baseline at the set-points a [B, n_sgen]
         in [-1, 1], by the launches of opf_actions' first iteration.  Returns a dict of tensors by NODE (elimination position; `bus_of_node`
@@ -701,6 +751,14 @@ class VoltageControl(MultiAgentEnv):
         out = self._b.opf_actions(config, vm_pu=vm_pu)
         r = (out[0][0].cpu().numpy(), float(out[1][0].item()), float(out[2][0].item()), int(out[3][0].item()), int(out[4][0].item()))
         return r + (out[5][0].cpu().numpy(),) if vm_pu else r
+
+    def evaluate_actions(self, candidates):
+        """VoltageControlBatch.evaluate_actions for this one env, as numpy: candidates [K, n_sgen] -> (rewards ndarray [K], infos list
+        of K dicts keyed by INFO_KEYS, status ndarray [K]): what step(candidates[k]) would return, without taking the step"""
+        c = np.asarray(candidates, dtype=np.float64).reshape(1, -1, self._b.n_sgen)
+        r, info, st, _ = self._b.evaluate_actions(torch.as_tensor(c))
+        vals = info[0].cpu().numpy()
+        return r[0].cpu().numpy(), [{k: float(v) for k, v in zip(INFO_KEYS, row)} for row in vals], st[0].cpu().numpy()
 
     def _obs_list(self, obs):
         o = obs[0].double().cpu().numpy()
