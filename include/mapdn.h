@@ -115,6 +115,23 @@ typedef struct mapdn_netspec {
                                        loads at one bus with different fractions (runpp solves with their mean, reports each with its
                                        own), a ZIP load on the ext_grid bus, ZIP loads with bus_alias (fused buses) or with nr_solver =
                                        dense.  All-zero columns are the constant-power path.                                       */
+  int32_t n_gen;                    /* generators (in-service rows of net.gen): each makes its bus a GEN BUS — |V| held at gen_vm_pu, P =
+                                       gen_p_mw * gen_scaling injected (constant, no profile column), Q free (runpp's default
+                                       enforce_q_lims=False: no limits).  Newton unknowns: theta on gen and PQ buses, |V| on PQ buses;
+                                       ||F||inf runs over P of both kinds and Q of the PQ buses.  0 (with NULL columns) = the path of
+                                       before.  Gens are not agents: obs / state sizes do not change, the gen bus's p_mw / q_mvar reach
+                                       get_obs / get_state through res_bus.  MAPDN_E_INVALID (with a message): two gens on one bus, a gen
+                                       on the ext_grid bus, gens with bus_alias (fused buses), with voltage-dependent loads or with
+                                       nr_solver = dense.  mapdn_droop_actions / mapdn_opf_actions refuse such a handle.              */
+  const int32_t* gen_bus;           /* [n_gen] net.gen.bus                                                                            */
+  const double* gen_p_mw;           /* [n_gen] net.gen.p_mw                                                                           */
+  const double* gen_vm_pu;          /* [n_gen] net.gen.vm_pu (> 0)                                                                    */
+  const double* gen_scaling;        /* [n_gen] net.gen.scaling; NULL = 1                                                              */
+  double vm_init_pu;                /* |V| every PQ bus starts from (runpp init_vm_pu="auto": the mean of the vm_pu of the ext_grid and of
+                                       ALL net.gen rows, in service or not — so it is the caller's to give when the net holds
+                                       out-of-service gens).  0 or NaN = the mean of ext_grid_vm_pu and gen_vm_pu[0 .. n_gen); with no
+                                       gens that is ext_grid_vm_pu, the start of before.  The slack starts at its set-point and a gen bus
+                                       at its own vm_pu; the DC-angle start (nr_init = 2) uses these magnitudes.                       */
 } mapdn_netspec;
 
 /* Constructor kwargs of VoltageControl (args/env_args/var_voltage_control.yaml:3-20). */
@@ -211,6 +228,7 @@ typedef struct mapdn_dims_t {
   int32_t n_envs, n_bus, n_line, n_load, n_sgen, n_agents, n_actions, obs_size, state_size, n_info;
   int32_t is_radial;
   int32_t max_zone_size;
+  int32_t n_gen;                    /* generators (mapdn_netspec.n_gen): the columns of mapdn_get_res_gen */
 } mapdn_dims_t;
 
 typedef struct mapdn_handle mapdn_handle;
@@ -364,14 +382,24 @@ int mapdn_get_nr_geometry(const mapdn_handle* h, int32_t* out20);
  * computed on the host from the handle's plan constants in the solver's own order of operations — the tree sweeps of k_nr_tree, or
  * the block program of k_nr_sparse on the Bbus assembly.  Solves Bbus[pvpq, pvpq] Va[pvpq] = Pbus[pvpq] with
  * Bbus = (Cf - Ct)' diag(1 / (x |tap|)) (Cf - Ct), Pbus = -P_demand / sn_mva - (Cf - Ct)' (b (-shift)) - GS / sn_mva (pandapower
- * run_dc_pf).  HOST pointers; works on host-only handles.  MAPDN_E_INVALID on a net with fused buses. */
+ * run_dc_pf).  The generators' P (mapdn_netspec.gen_p_mw * gen_scaling) is subtracted from the demand of their buses here, as the
+ * injection does: p_bus_demand_mw holds loads minus sgens only.  HOST pointers; works on host-only handles.  MAPDN_E_INVALID on a net
+ * with fused buses. */
 int mapdn_get_dc_angles(const mapdn_handle* h, const double* p_bus_demand_mw, double* va_rad);
 
 /* Host-side export of the flat-start factorisation the NR kernel's first iteration uses (plan check, CPU tests):
  * factors [n][12] per elimination position = S_calc (re, im), D^-1 (4, row-major), A_pk (re, im), G (4, row-major)
- * of the block LU of the Jacobian at V = ext_grid vm_pu everywhere, unknowns [dtheta, d|V|/|V|];
+ * of the block LU of the Jacobian at the start of runpp's init="auto" — the slack at ext_grid vm_pu, every gen bus at its own vm_pu,
+ * every other bus at mapdn_netspec.vm_init_pu (without generators: ext_grid vm_pu everywhere), all angles 0 — unknowns
+ * [dtheta, d|V|/|V|], the block of a gen bus masked (csrc/gen_mask.hpp: D^-1 = [[1 / D0, 0], [0, 1]], second row of G zero);
  * bus_of_pos [n+1] (optional) = bus id of every elimination position (position n is the slack). */
 int mapdn_get_flat_factors(const mapdn_handle* h, double* factors, int32_t* bus_of_pos);
+
+/* res_gen of the env's committed state (pandapower results_gen): DEVICE f64 [n_envs, n_gen] each, any pointer NULL —
+ * p_mw = gen_p_mw * gen_scaling, q_mvar = Im(V_k conj((Ybus V)_k)) sn_mva + QD_k (QD: the bus's loads - sgens + shunt q |V|^2),
+ * vm_pu and va_degree those of the gen's bus.  Rolled back with the rest of the state after an unsolvable step.  A handle without
+ * generators writes nothing.  MAPDN_E_STATE before the first reset. */
+int mapdn_get_res_gen(mapdn_handle* h, double* p_mw, double* q_mvar, double* vm_pu, double* va_degree, void* stream);
 
 /* Host-side export of the general sparse solver's elimination PROGRAM for S sub-lanes (plan check, CPU tests): dims [6] =
  * block slots, fill-only blocks, phases, assembly rows per sub-lane, max row entries, number of off-diagonal blocks;
@@ -652,8 +680,8 @@ int mapdn_nr_time_ms(mapdn_handle* h, double* total_ms, int64_t* launches);
 
 /* Host-side export of the power-flow kernel instantiation this handle launches (coverage tests; also for device == -1 handles):
  * out[8] = solver, then by solver
- *   0 k_nr_tree<W, L, HL, GL, RES, DC, ZIP>: W, L, HL, GL, RES, DC, ZIP (RES 0: the generic residency body; csrc/nr_inst_list.hpp)
- *   1 k_nr_sparse<L, DC>:                    L, DC, ZIP (ZIP is decided at run time), 0, 0, 0, 0
+ *   0 k_nr_tree<W, L, HL, GL, RES, DC, ZIP, GEN>: W, L, HL, GL, RES, DC, ZIP | GEN << 1 (RES 0: the generic residency body; csrc/nr_inst_list.hpp)
+ *   1 k_nr_sparse<L, DC>:                    L, DC, ZIP | GEN << 1 (both decided at run time), 0, 0, 0, 0
  *   2 k_nr_dense<W, GA>:                     W, GA (the Jacobian in global memory), 0, 0, 0, 0, 0 */
 int mapdn_get_nr_kernel(const mapdn_handle* h, int32_t* out8);
 

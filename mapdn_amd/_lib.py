@@ -42,7 +42,7 @@ EXPORTS = (
     "mapdn_attention_forward", "mapdn_attention_backward", "mapdn_attention_scratch_floats", "mapdn_attention_max_agents",
     "mapdn_critic_shapley_forward", "mapdn_critic_shapley_backward", "mapdn_critic_shapley_scratch_floats", "mapdn_critic_shapley_geometry",
     "mapdn_ppo_gae", "mapdn_ppo_loss_blocks", "mapdn_ppo_policy_loss", "mapdn_ppo_value_loss",
-    "mapdn_set_branch_ratings", "mapdn_get_branch_results", "mapdn_get_loading_summary",
+    "mapdn_set_branch_ratings", "mapdn_get_branch_results", "mapdn_get_loading_summary", "mapdn_get_res_gen",
 )
 
 _pd = C.POINTER(C.c_double)
@@ -64,6 +64,7 @@ class CNetSpec(C.Structure):
         ("ext_grid_bus", C.c_int32), ("ext_grid_vm_pu", C.c_double), ("sn_mva", C.c_double), ("f_hz", C.c_double),
         ("br_g_pu", _pd), ("load_scaling", _pd), ("sgen_scaling", _pd), ("bus_alias", _pi),
         ("load_const_z", _pd), ("load_const_i", _pd),
+        ("n_gen", C.c_int32), ("gen_bus", _pi), ("gen_p_mw", _pd), ("gen_vm_pu", _pd), ("gen_scaling", _pd), ("vm_init_pu", C.c_double),
     ]
 
 
@@ -149,7 +150,7 @@ def make_opf_config(cfg=None) -> COPFConfig:
 class CDims(C.Structure):
     _fields_ = [(k, C.c_int32) for k in (
         "n_envs", "n_bus", "n_line", "n_load", "n_sgen", "n_agents", "n_actions", "obs_size", "state_size",
-        "n_info", "is_radial", "max_zone_size")]
+        "n_info", "is_radial", "max_zone_size", "n_gen")]
 
 
 BRANCH_COLUMNS = ("p_from_mw", "q_from_mvar", "p_to_mw", "q_to_mvar", "pl_mw", "ql_mvar", "i_from_ka", "i_to_ka", "i_ka", "loading_percent")
@@ -299,6 +300,7 @@ def load():
     lib.mapdn_set_branch_ratings.argtypes = [vp, _pd, _pd, _pd, _pd, _pd]
     lib.mapdn_get_branch_results.argtypes = [vp, vp, vp, C.POINTER(CBranchOut), C.POINTER(CBranchOut), vp]
     lib.mapdn_get_loading_summary.argtypes = [vp, C.c_double, vp, vp, vp, vp]
+    lib.mapdn_get_res_gen.argtypes = [vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("mapdn_last_error", "mapdn_destroy", "mapdn_build_info"):
             getattr(lib, name).restype = C.c_int
@@ -361,6 +363,12 @@ def make_cnetspec(net: NetSpec):
     zl = net.has_zip_loads                          # NULL columns: constant-power loads, the path of before
     s.load_const_z = _p(net.load_const_z, _pd) if zl else C.cast(None, _pd)
     s.load_const_i = _p(net.load_const_i, _pd) if zl else C.cast(None, _pd)
+    s.n_gen = net.n_gen                             # 0 / NULL columns / vm_init_pu 0: no generators, the path of before
+    s.gen_bus = _p(net.gen_bus, _pi)
+    s.gen_p_mw = _p(net.gen_p_mw, _pd)
+    s.gen_vm_pu = _p(net.gen_vm_pu, _pd)
+    s.gen_scaling = _p(net.gen_scaling, _pd)
+    s.vm_init_pu = float(net.start_vm_pu) if (net.n_gen or net.vm_init_pu > 0.0) else 0.0
     return s, keep
 
 
@@ -418,11 +426,14 @@ NR_KERNEL_KEYS = {0: ("W", "L", "HL", "GL", "RES", "DC", "ZIP"), 1: ("L", "DC", 
 
 def nr_kernel(handle) -> dict:
     """the power-flow kernel instantiation this handle launches (mapdn_get_nr_kernel): solver 0 k_nr_tree<W, L, HL, GL, RES, DC, ZIP>,
-    1 k_nr_sparse<L, DC> (+ the run-time ZIP flag), 2 k_nr_dense<W, GA>"""
+    1 k_nr_sparse<L, DC> (+ the run-time ZIP and GEN flags), 2 k_nr_dense<W, GA>; GEN: the form for nets with generators"""
     out = (C.c_int32 * 8)()
     check(load().mapdn_get_nr_kernel(handle, out), handle)
     solver = int(out[0])
-    return dict(solver=solver, **{k: int(out[1 + i]) for i, k in enumerate(NR_KERNEL_KEYS[solver])})
+    k = dict(solver=solver, **{k: int(out[1 + i]) for i, k in enumerate(NR_KERNEL_KEYS[solver])})
+    if "ZIP" in k:                                  # the slot holds ZIP | GEN << 1 (generators: the GEN form of the kernel)
+        k["GEN"], k["ZIP"] = k["ZIP"] >> 1, k["ZIP"] & 1
+    return k
 
 
 def policy_forward_geometry(obs_dim: int, id_dim: int):

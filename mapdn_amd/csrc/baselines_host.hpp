@@ -120,6 +120,8 @@ static const char* opf_resolve(const mapdn_handle* h, const mapdn_opf_config* in
   const Plan& P = h->plan;
   if (!P.radial || h->solver != 0) return "opf: meshed nets and handles on another solver than the tree solver are not supported";
   if (P.zip) return "opf: voltage-dependent (ZIP) loads are not supported";
+  if (P.n_gen) return "opf_actions: nets with generators (net.gen, gen buses) are not supported (k_opf_linearise takes every non-slack bus as a PQ bus)";
+  if (P.gen_start) return "opf_actions: a start other than ext_grid_vm_pu (vm_init_pu: out-of-service net.gen rows) is not supported (the loop's solves start at the ext_grid set-point)";
   if (P.nbo != P.nb || !P.fused_obus.empty() || !P.alias_pos.empty()) return "opf: fused buses are not supported";
   if (P.ns > OPF_MAX_NS) return "opf: more than 64 sgens are not supported";
   return nullptr;

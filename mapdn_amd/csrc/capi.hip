@@ -66,7 +66,7 @@ struct mapdn_handle {
   Knobs knobs;
   int solver = 0;                 // 0 tree (radial), 1 general sparse (k_nr_sparse), 2 general dense (k_nr_dense)
   int sp_lanes = 0;
-  int nr_var = 0;                 // k_nr_tree variant: NR_VAR_DC | NR_VAR_ZIP
+  int nr_var = 0;                 // k_nr_tree variant: NR_VAR_DC | NR_VAR_ZIP | NR_VAR_GEN
   mapdn_env_config cfg;
   Dev d;
   int device = 0;
@@ -81,8 +81,8 @@ struct mapdn_handle {
   struct Geo { int W = 0, L = 0, lean = 0, rows = 0, h_lds = 0, g_lds = 0, rec_lds = 0, flat_lds = 0, line_lds = 0, mm_pass = 0, ncl = 0;
                size_t lds = 0; long wgs = 0; int resident = 0, rounds = 0; double model_ns = 0.0; } geo;
   int32_t *obs_rows = nullptr, *state_rows = nullptr, *iota_idx = nullptr, *vm_row = nullptr, *va_row = nullptr;
-  int32_t *obs_xptr = nullptr, *obs_xrow = nullptr;
-  double *obs_scale = nullptr, *state_scale = nullptr;
+  int32_t *obs_xptr = nullptr, *obs_xrow = nullptr, *gen_bus_rows = nullptr;
+  double *obs_scale = nullptr, *state_scale = nullptr, *gen_p_rows = nullptr;
   double *t_pl = nullptr, *t_ql = nullptr, *t_pv = nullptr, *t_q = nullptr;
   double* table = nullptr; double* stdv = nullptr; double* smax = nullptr;
   std::vector<double> stdv_host, smax_host;     // what set_profiles computed (mapdn_get_profile_stats)
@@ -322,6 +322,11 @@ static int validate(mapdn_handle* h, const mapdn_env_config& c) {
   if (h->solver == 2 && P.zip)
     return api_fail(h, MAPDN_E_INVALID, "voltage-dependent loads (load_const_z / load_const_i) are not built for nr_solver = dense (k_nr_dense solves "
                                         "constant-power loads only): use the tree or the sparse solver");
+  if (h->solver == 2 && P.gen_start)
+    return api_fail(h, MAPDN_E_INVALID, P.n_gen ? "generators (net.gen, gen buses) are not built for nr_solver = dense (k_nr_dense solves PQ buses from the "
+                                                  "flat start only): use the tree or the sparse solver"
+                                                : "vm_init_pu other than ext_grid_vm_pu (out-of-service net.gen rows move runpp's start) is not built for "
+                                                  "nr_solver = dense (k_nr_dense starts every bus at the ext_grid set-point): use the tree or the sparse solver");
   if (c.overlap_advance) return api_fail(h, MAPDN_E_INVALID, "overlap_advance was removed (measured slower than the single stream): it must be 0");
   if (c.xcd_map) return api_fail(h, MAPDN_E_INVALID, "xcd_map was removed (the XCD-aligned env order measured a wash): it must be 0");
   if (k.fuse_inject == 1 && h->solver != 0)
@@ -390,6 +395,13 @@ static int upload_topology(mapdn_handle* h) {
   if (d.nr_init == 2) UP(dc_pc, P.dc_pc);
   d.zip = P.zip ? 1 : 0;
   if (d.zip) { UP(zip_c, P.zip_c); d.zip_c_bytes = (uint32_t)(P.zip_c.size() * sizeof(double)); }
+  d.n_gen = P.n_gen; d.gen_start = P.gen_start ? 1 : 0;
+  if (d.gen_start) {                              // generators: plan.hpp Plan::n_gen ...
+    UP(is_gen, P.is_gen); UP(gen_p_pos, P.gen_p_pos); UP(v0, P.v0); d.v0_bytes = (uint32_t)(P.v0.size() * sizeof(double));
+    UP(gen_of_pos, P.gen_of_pos); UP(gq_ptr, P.gq_ptr);
+    { std::vector<int32_t> gc(P.gq_col); if (gc.empty()) gc.push_back(0); UP(gq_col, gc); }
+    { std::vector<double> gv(P.gq_val); if (gv.empty()) gv.push_back(0.0); UP(gq_val, gv); }
+  }
   UP(bus_of_pos, P.bus_of_pos); UP(root_children, P.root_children); UP(root_y, P.root_y);
   UP(pos_of_obus, P.pos_of_obus); UP(cm_kind, P.cm_kind);
   d.n_fused = (int32_t)P.fused_obus.size(); d.n_alias = (int32_t)P.alias_pos.size(); d.n_slack_group = (int32_t)P.slack_group.size();
@@ -465,6 +477,12 @@ static int setup_env_state(mapdn_handle* h) {
   Dev& d = h->d;
   const size_t Bp = d.Bp;
   AL(q_new, d.ns); AL(cur_pl, d.nl); AL(cur_ql, d.nl); AL(pl, d.n_line);
+  if (d.n_gen) {
+    AL(res_gen_q, d.n_gen);
+    std::vector<double> gp((size_t)d.n_gen * Bp);                // res_gen.p_mw, env-minor like every result row: the same constant per env
+    for (int g = 0; g < d.n_gen; ++g) std::fill_n(gp.begin() + (size_t)g * Bp, Bp, h->plan.gen_p[g]);
+    if (const int rc_ = dupload(h, &h->gen_p_rows, gp)) return rc_;
+  }
   const GbufRows r = gbuf_rows(d);
   AL(gbuf, r.n);
   d.cur_pv = d.gbuf + (size_t)r.pv * Bp;
@@ -518,8 +536,13 @@ static int setup_gather_tables(mapdn_handle* h) {
     return rc;
   tables(P.state_kind, P.state_idx, rows, scale, xptr, xrow);     // get_state has no add-back
   if ((rc = dupload(h, &h->state_rows, rows)) || (rc = dupload(h, &h->state_scale, scale))) return rc;
-  std::vector<int32_t> io(std::max(std::max(d.nbo, d.n_line), std::max(d.nl, d.ns)));   // identity rows of the result exports
+  std::vector<int32_t> io(std::max(std::max(std::max(d.nbo, d.n_line), std::max(d.nl, d.ns)), d.n_gen));   // identity rows of the result exports
   for (size_t i = 0; i < io.size(); ++i) io[i] = (int32_t)i;
+  if (d.n_gen) {                                 // res_gen vm_pu / va_degree: the res_bus rows of the gens' buses (no fused buses with generators)
+    std::vector<int32_t> gb(P.n_gen);
+    for (int g = 0; g < P.n_gen; ++g) gb[g] = P.bus_of_pos[P.gen_pos[g]];
+    if ((rc = dupload(h, &h->gen_bus_rows, gb))) return rc;
+  }
   return dupload(h, &h->iota_idx, io);
 }
 
@@ -627,7 +650,7 @@ static int create_impl(mapdn_handle* h, const mapdn_netspec* net, const mapdn_en
   if (!rc) rc = choose_solver(h);
   if (!rc) rc = validate(h, *cfg);
   if (rc) return rc;
-  h->nr_var = (cfg->nr_init == 2 ? NR_VAR_DC : 0) | (h->plan.zip ? NR_VAR_ZIP : 0);
+  h->nr_var = (cfg->nr_init == 2 ? NR_VAR_DC : 0) | (h->plan.zip ? NR_VAR_ZIP : 0) | (h->plan.gen_start ? NR_VAR_GEN : 0);
   // composition of the step() launches: the PV-bus injection runs in the prologue of k_nr_tree unless the handle auto-resets (its
   // restarting envs refresh all their loads in the injection launch), rebuilds all of Sbus on every call, or pins fuse_inject = 2
   h->fuse_inject = h->solver == 0 && !cfg->auto_reset && !h->knobs.inject_full && h->knobs.fuse_inject != 2;
@@ -688,7 +711,7 @@ int mapdn_dims(const mapdn_handle* h, mapdn_dims_t* out) try {
   const Plan& P = h->plan;
   out->n_envs = h->d.B; out->n_bus = P.nbo; out->n_line = P.n_line; out->n_load = P.nl; out->n_sgen = P.ns;
   out->n_agents = P.n_agents; out->n_actions = 1; out->obs_size = P.obs_size; out->state_size = P.state_size;
-  out->n_info = MAPDN_N_INFO; out->is_radial = P.radial ? 1 : 0; out->max_zone_size = P.max_zone;
+  out->n_info = MAPDN_N_INFO; out->is_radial = P.radial ? 1 : 0; out->max_zone_size = P.max_zone; out->n_gen = P.n_gen;
   return MAPDN_OK;
 } MAPDN_CATCH(h)
 
@@ -886,6 +909,24 @@ int mapdn_get_results(mapdn_handle* h, double* vm_pu, double* va_degree, double*
   return MAPDN_OK;
 } MAPDN_CATCH(h)
 
+// res_gen: p_mw is a constant of the plan, q_mvar what commit_bus left, vm_pu / va_degree the rows of the gens' buses
+int mapdn_get_res_gen(mapdn_handle* h, double* p_mw, double* q_mvar, double* vm_pu, double* va_degree, void* stream) try {
+  if (!h) return MAPDN_E_INVALID;
+  if (!h->was_reset) { h->err = "get_res_gen before reset"; return MAPDN_E_STATE; }
+  NEEDDEV(h);
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  const Dev& d = h->d;
+  const int ng = d.n_gen;
+  if (ng == 0) return MAPDN_OK;
+  if (p_mw) transpose_out(h, h->gen_p_rows, 1.0, h->iota_idx, p_mw, ng, st);   // constant rows, uploaded once (setup_env_state)
+  if (q_mvar) transpose_out(h, d.res_gen_q, 1.0, h->iota_idx, q_mvar, ng, st);
+  if (vm_pu) transpose_out(h, d.vm, 1.0, h->gen_bus_rows, vm_pu, ng, st);
+  if (va_degree) transpose_out(h, d.va, 180.0 / M_PI, h->gen_bus_rows, va_degree, ng, st);
+  HIPCHK(h, hipGetLastError());
+  return MAPDN_OK;
+} MAPDN_CATCH(h)
+
 int mapdn_get_loads(mapdn_handle* h, double* load_p, double* load_q, void* stream) try {
   if (!h) return MAPDN_E_INVALID;
   NEEDDEV(h);
@@ -1061,13 +1102,13 @@ int mapdn_get_nr_geometry(const mapdn_handle* h, int32_t* out) try {
 
 int mapdn_get_nr_kernel(const mapdn_handle* h, int32_t* out) try {
   if (!h || !out) return MAPDN_E_INVALID;
-  const int dc = h->cfg.nr_init == 2 ? 1 : 0, zip = h->plan.zip ? 1 : 0;
+  const int dc = h->cfg.nr_init == 2 ? 1 : 0, zip = (h->plan.zip ? 1 : 0) | (h->plan.gen_start ? 2 : 0);   // bit 1: the GEN form
   int32_t v[8] = {h->solver, 0, 0, 0, 0, 0, 0, 0};
   if (h->solver == 0) {
     const mapdn_handle::Geo& g = h->geo;
     const NrInst* I = nr_inst_of(g.W, g.L, g.h_lds, g.g_lds, g.rec_lds, g.flat_lds, h->nr_var);
     if (!I) return api_fail(h, MAPDN_E_INTERNAL, "mapdn_get_nr_kernel: the handle's geometry has no k_nr_tree instantiation");
-    const int32_t t[7] = {I->W, I->L, I->HL, I->GL, I->RES, (I->VAR & NR_VAR_DC) ? 1 : 0, (I->VAR & NR_VAR_ZIP) ? 1 : 0};
+    const int32_t t[7] = {I->W, I->L, I->HL, I->GL, I->RES, (I->VAR & NR_VAR_DC) ? 1 : 0, ((I->VAR & NR_VAR_ZIP) ? 1 : 0) | ((I->VAR & NR_VAR_GEN) ? 2 : 0)};
     std::memcpy(v + 1, t, sizeof(t));
   } else if (h->solver == 1) {
     v[1] = h->sp_lanes; v[2] = dc; v[3] = zip;
@@ -1086,7 +1127,7 @@ int mapdn_get_dc_angles(const mapdn_handle* h, const double* p_bus_demand_mw, do
                                                                           : "the DC-angle start is not defined on a net with fused buses (bus_alias)");
   const int n = P.n;
   std::vector<double> pbus(n);                   // Pbus = Re(Sbus) + dc_pc, Re(Sbus) = -P_demand / sn (as the injection forms it)
-  for (int k = 0; k < n; ++k) pbus[k] = -p_bus_demand_mw[P.bus_of_pos[k]] / P.sn_mva + P.dc_pc[k];
+  for (int k = 0; k < n; ++k) pbus[k] = -(p_bus_demand_mw[P.bus_of_pos[k]] - P.gen_p_pos[k]) / P.sn_mva + P.dc_pc[k];   // (sbus_entry: P_gen is a negative demand)
   std::vector<double> th(n + 1, 0.0);            // by position; the slack (n) stays 0
   if (h->solver == 0) {                          // k_nr_tree's sweeps, node by node (children in the canonical order)
     Schedule S;
@@ -1110,7 +1151,7 @@ int mapdn_get_dc_angles(const mapdn_handle* h, const double* p_bus_demand_mw, do
       const int i = (int)R.node;
       for (int q = 0; q < G.max_nnz; ++q) {
         const SpNz& z = G.nz[r * G.max_nnz + q];
-        if ((int)z.col == i) B[(size_t)i * 4] = z.bdc;
+        if ((int)(z.col & ~SP_COL_GEN) == i) B[(size_t)i * 4] = z.bdc;
         else if (z.slot >= 0) { double* o = &B[(size_t)z.slot * 4]; o[0] = z.bdc; o[1] = o[2] = o[3] = 0.0; }
       }
       B[(size_t)i * 4 + 3] = 1.0;
@@ -1231,6 +1272,8 @@ int mapdn_droop_actions(mapdn_handle* h, const mapdn_droop_config* cfg, double* 
   if (!h) return MAPDN_E_INVALID;
   mapdn_droop_config c;
   if (const char* why = droop_resolve(cfg, c)) return api_fail(h, MAPDN_E_INVALID, why);
+  if (h->plan.n_gen) return api_fail(h, MAPDN_E_INVALID, "droop_actions: nets with generators (net.gen, gen buses) are not supported (the reference's droop script has no voltage-controlled buses)");
+  if (h->plan.gen_start) return api_fail(h, MAPDN_E_INVALID, "droop_actions: a start other than ext_grid_vm_pu (vm_init_pu: out-of-service net.gen rows) is not supported (the loop's solves start at the ext_grid set-point)");
   if (!actions || !iterations || !status) { h->err = "droop_actions: null buffer"; return MAPDN_E_INVALID; }
   NEEDDEV(h);
   if (!h->was_reset) { h->err = "droop_actions before reset"; return MAPDN_E_STATE; }

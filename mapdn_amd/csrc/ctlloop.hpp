@@ -43,7 +43,7 @@ __device__ __forceinline__ void ctl_pv_row(const Dev& d, int e, int jb, const do
   double P, Q;
   pv_bus_load_sum(d, jb, k, e, P, Q);
   sub_bus_sgens(d, k, e, stepping, d.cur_pv, 0, [&](int j, size_t o, double p) { return clip_q(p, d.smax[j], a[o]); }, P, Q);
-  if (k < d.n) ((double2*)((char*)d.nrbuf + d.sb_off))[(size_t)k * d.Bp + e] = sbus_entry(P, Q, d.sn);
+  if (k < d.n) ((double2*)((char*)d.nrbuf + d.sb_off))[(size_t)k * d.Bp + e] = sbus_entry(d, k, P, Q);
 }
 
 // The Sbus rows of the load-only buses with several loads (k_advance leaves these to the injection of the step)
@@ -52,7 +52,7 @@ __device__ __forceinline__ void ctl_mlo_rows(const Dev& d, const CtlLane& t) {
     const int k = d.mlo_pos[i];
     double P, Q;
     stored_load_sum(d, k, t.e, d.cur_pl, d.cur_ql, P, Q);
-    ((double2*)((char*)d.nrbuf + d.sb_off))[(size_t)k * d.Bp + t.e] = sbus_entry(P, Q, d.sn);
+    ((double2*)((char*)d.nrbuf + d.sb_off))[(size_t)k * d.Bp + t.e] = sbus_entry(d, k, P, Q);
   }
 }
 

@@ -14,8 +14,13 @@ namespace mapdn {
 // P + p); a bus with several loads and scalings other than 1 did (tests/test_element_edges_gpu.py).
 __device__ __forceinline__ void add_scaled(double& acc, double x, double s) { acc = fma(x, s, acc); }
 __device__ __forceinline__ void sub_scaled(double& acc, double x, double s) { acc = fma(-x, s, acc); }
-// scheduled injection of a bus as an (re, im) pair from its demand (loads - sgens, MW / MVAr)
-__device__ __forceinline__ double2 sbus_entry(double P, double Q, double sn) { return make_double2(-P / sn, -Q / sn); }
+// scheduled injection of the bus at position k as an (re, im) pair from its demand (loads - sgens, MW / MVAr).  A generator on the bus
+// (mapdn_netspec.gen_*) is a constant negative demand, Sbus_k = (P_gen - PD_k - j QD_k) / sn_mva: every path that writes an Sbus entry
+// comes through here, so they all see it (d.n_gen == 0, a wave-uniform test: the expression of before)
+__device__ __forceinline__ double2 sbus_entry(const Dev& d, int k, double P, double Q) {
+  if (d.n_gen) P -= d.gen_p_pos[k];
+  return make_double2(-P / d.sn, -Q / d.sn);
+}
 // _clip_reactive_power: the reactive limit of a sgen at active power p, and q = a x limit
 __device__ __forceinline__ double q_limit(double p, double sm) { return sqrt(sm * sm - p * p); }
 __device__ __forceinline__ double clip_q(double p, double sm, double a) {

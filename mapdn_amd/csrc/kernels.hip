@@ -50,7 +50,7 @@ k_inject(Dev d, int mode, const AT* __restrict__ actions, const double* __restri
   }, P, Q);
   if (k < d.n) {   // scheduled injection as an (re, im) pair, stored by node position
     const size_t o = (size_t)k * d.Bp + e;
-    const double2 v = sbus_entry(P, Q, d.sn);
+    const double2 v = sbus_entry(d, k, P, Q);
     ((double2*)((char*)d.nrbuf + d.sb_off))[o] = v;
     if (mode != MODE_SOLVE) ((double2*)((char*)d.nrbuf + d.sb_off_alt))[o] = v;   // both Sbus buffers (see k_advance) are current afterwards
   }
@@ -80,7 +80,7 @@ k_inject_sgen(Dev d, int mode, const AT* __restrict__ actions, int add_noise) {
   if (mlo_row) {   // the load sum of a bus with several loads needs ONE thread: formed here from the load values k_advance stored
     if (t.ar || k >= d.n) return;                // (a restarting env forms all its sums below)
     stored_load_sum(d, k, e, d.cur_pl, d.cur_ql, P, Q);
-    sbp[(size_t)k * d.Bp] = sbus_entry(P, Q, d.sn);
+    sbp[(size_t)k * d.Bp] = sbus_entry(d, k, P, Q);
     return;
   }
   if (t.ar) {
@@ -91,14 +91,14 @@ k_inject_sgen(Dev d, int mode, const AT* __restrict__ actions, int add_noise) {
       double Ps, Qs;
       restart_load_sum(d, kk, e, t.ar_row, t.draw, add_noise, Ps, Qs);
       if (kk < d.n) {                             // a restarting env is not advanced by this call's k_advance: both Sbus buffers
-        const double2 v = sbus_entry(Ps, Qs, d.sn);
+        const double2 v = sbus_entry(d, kk, Ps, Qs);
         sbp[(size_t)kk * d.Bp] = v;
         ((double2*)((char*)d.nrbuf + d.sb_off_alt))[(size_t)kk * d.Bp + e] = v;
       }
     }
   } else pv_bus_load_sum(d, jb, k, e, P, Q);
   sub_bus_sgens(d, k, e, t, d.cur_pv, add_noise, [&](int j, size_t o, double p) { return d.q_new[o] = turn_q(d, mode, t, actions, e, j, p); }, P, Q);
-  if (k < d.n) sbp[(size_t)k * d.Bp] = sbus_entry(P, Q, d.sn);
+  if (k < d.n) sbp[(size_t)k * d.Bp] = sbus_entry(d, k, P, Q);
 }
 
 // =================================================================================================
@@ -197,6 +197,23 @@ __device__ __forceinline__ void commit_bus(const Dev& d, int b_, int e, size_t S
   }
   d.va[o] = va;
   d.vm[o] = v;
+  if (d.n_gen && d.gen_of_pos[k] >= 0) {         // a gen bus (no fused buses with generators): Q is what the network takes, as on the slack row
+    const int g = d.gen_of_pos[k];
+    const double* vo = node_vout(d, k, e, S);
+    double ir = 0.0, ii = 0.0;                   // (Ybus V)_k from the node's Ybus row (plan.hpp Plan::gq_*)
+    for (int q = d.gq_ptr[g]; q < d.gq_ptr[g + 1]; ++q) {
+      const double* cb = node_vout(d, d.gq_col[q], e, S);
+      const double gg = d.gq_val[2 * q], bb = d.gq_val[2 * q + 1], ec = cb[(size_t)VO_E * S], fc = cb[(size_t)VO_F * S];
+      ir += gg * ec - bb * fc; ii += gg * fc + bb * ec;
+    }
+    const double ek = vo[(size_t)VO_E * S], fk = vo[(size_t)VO_F * S];
+    const double sq = (fk * ir - ek * ii) * d.sn;                  // Im(V_k conj((Ybus V)_k)) sn: Ybus holds the shunt
+    const double qd = Q + d.shunt_q[k] * v * v;                    // QD_k = loads - sgens + shunt q |V|^2
+    d.res_gen_q[(size_t)g * S + e] = sq + qd;                      // res_gen.q_mvar
+    d.res_p[o] = P + d.shunt_p[k] * v * v;                         // loads - sgens - P_gen (+ shunt): Sbus holds P_gen
+    d.res_q[o] = -sq;                                              // loads - sgens + shunt - Q_gen
+    return;
+  }
   // (a bus of a fused group reports its OWN elements: k_commit_fused wrote p_mw / q_mvar before this launch)
   if (d.cm_kind[b_] == 0) { P = P + d.shunt_p[k] * v * v; Q = Q + d.shunt_q[k] * v * v; d.res_p[o] = P; d.res_q[o] = Q; }   // (both loads ahead of both stores)
 }
@@ -242,7 +259,7 @@ __device__ __forceinline__ void advance_load_pair(const Dev& d, int e, int b, in
     const int dd = d.ld_dest[li];
     const double sc = d.load_scale[li];
     const double ps = p * sc, qs = q * sc;
-    if ((dd & 3) == 0) sbw[(size_t)(dd >> 2) * S] = sbus_entry(ps, qs, d.sn);
+    if ((dd & 3) == 0) sbw[(size_t)(dd >> 2) * S] = sbus_entry(d, dd >> 2, ps, qs);
     else if ((dd & 3) == 1) ((double2*)d.bus_ld)[(size_t)(dd >> 2) * S + e] = make_double2(ps, qs);
   };
   put(j0, p0, q0);
@@ -458,7 +475,7 @@ void launch_inject(const Dev& d, int mode, const void* actions, int dtype, const
 }
 // k_nr_tree instantiations: tables exported by the parts of nr_inst.hip (nr_inst_list.hpp).  RES is the residency of the step
 // records / flat-start constants as a compile-time fact (1 both, 2 neither, 3 records only); 0 = the generic body.
-// var: the variant (NrInst::VAR: NR_VAR_DC the DC-angle start, nr_init = 2; NR_VAR_ZIP voltage-dependent loads)
+// var: the variant (NrInst::VAR: NR_VAR_DC the DC-angle start, nr_init = 2; NR_VAR_ZIP voltage-dependent loads; NR_VAR_GEN generators)
 #define NR_TABLES \
   const NrInst* tabs[NR_INST_PARTS] = {nr_insts_0, nr_insts_1, nr_insts_2, nr_insts_3}; \
   const int cnt[NR_INST_PARTS] = {nr_n_insts_0, nr_n_insts_1, nr_n_insts_2, nr_n_insts_3};
@@ -497,7 +514,7 @@ void launch_nr(const Dev& d, int mode, double* reward, uint8_t* term, double* in
   const size_t lds = nr_lds_bytes(d.nr_waves, d.nr_lanes, d.n, d.nr_cslots, d.nr_xslots, d.nr_nclist, d.nr_h_lds, d.nr_g_lds,
                                   d.nr_line_lds ? d.n_line : 0, d.nr_rec_lds ? d.nr_rows : 0, d.nr_flat_lds ? d.nr_rows : 0);
   const NrInst* I = nr_pick(d.nr_waves, d.nr_lanes, d.nr_h_lds, d.nr_g_lds, d.nr_rec_lds, d.nr_flat_lds,
-                            (d.nr_init == 2 ? NR_VAR_DC : 0) | (d.zip ? NR_VAR_ZIP : 0));
+                            (d.nr_init == 2 ? NR_VAR_DC : 0) | (d.zip ? NR_VAR_ZIP : 0) | (d.gen_start ? NR_VAR_GEN : 0));
   if (!I) return;                                   // (mapdn_create refuses such a geometry: nr_set_lds_limit)
 #ifdef MAPDN_NR_STAMPS
   { NR_TABLES

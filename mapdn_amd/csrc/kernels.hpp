@@ -102,6 +102,16 @@ struct Dev {
   // k_nr_sparse scale Sbus_k by cp + ci |V_k| + cz |V_k|^2 after iteration 0; commit_bus reports the loads at the converged |V|
   int32_t zip;
   const double* zip_c; uint32_t zip_c_bytes;     // [n + 2][2] by position: (ci, cz) (plan.hpp Plan::zip_c)
+  // ---- generators (mapdn_netspec.gen_*; appended likewise; plan.hpp Plan::n_gen ...).  n_gen: the bus injection (inject.hpp sbus_entry)
+  // subtracts gen_p_pos from the demand and commit_bus writes res_gen_q and the gen bus's q_mvar.  gen_start: k_nr_tree<..., GEN = true> /
+  // k_nr_sparse start from v0 and mask the blocks of the nodes flagged in is_gen (gen_mask.hpp)
+  int32_t n_gen, gen_start;
+  const uint8_t* is_gen;                         // [n + 2] by position
+  const double *gen_p_pos, *v0;                  // [n + 2] by position: P_gen (MW; 0 elsewhere), start magnitude
+  uint32_t v0_bytes;
+  const int32_t *gen_of_pos, *gq_ptr, *gq_col;   // [n + 2] gen at a position or -1; CSR over the gens: their Ybus rows (columns: positions)
+  const double* gq_val;                          // (re, im) per entry
+  double* res_gen_q;                             // [n_gen][Bp] res_gen.q_mvar of the committed state
 };
 
 // ---- the bus injection every injecting kernel shares (inject.hpp: device functions on Dev)
@@ -116,8 +126,9 @@ void launch_inject_sgen(const Dev& d, int mode, const void* actions, int dtype, 
 // fused_actions != nullptr (MODE_STEP only): k_nr_tree's prologue performs the PV-bus injection itself (no k_inject_sgen launch)
 void launch_nr(const Dev& d, int mode, double* reward, uint8_t* term, double* info, hipStream_t st,
                const void* fused_actions = nullptr, int fused_dtype = 0);
-// var: the variant — NR_VAR_DC the DC-angle-start instantiations (mapdn_env_config.nr_init = 2), NR_VAR_ZIP the voltage-dependent-load ones
-enum { NR_VAR_DC = 1, NR_VAR_ZIP = 2 };
+// var: the variant — NR_VAR_DC the DC-angle-start instantiations (mapdn_env_config.nr_init = 2), NR_VAR_ZIP the voltage-dependent-load ones,
+// NR_VAR_GEN the ones for nets with generators (gen buses; never together with ZIP)
+enum { NR_VAR_DC = 1, NR_VAR_ZIP = 2, NR_VAR_GEN = 4 };
 int nr_set_lds_limit(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, size_t bytes, int var = 0);   // -2: geometry not instantiated
 int nr_geometry_compiled(int waves, int lanes, int h_lds, int g_lds, int rec_lds, int flat_lds, int var = 0);
 // the instantiation launch_nr runs for this geometry / residency / variant (nullptr: none; host-side, mapdn_get_nr_kernel)

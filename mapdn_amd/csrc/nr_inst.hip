@@ -15,9 +15,12 @@ namespace mapdn {
 #define NR_ENTRY_DC(w, l, hl, gl, res) {w, l, hl, gl, res, (const void*)k_nr_tree<w, l, hl, gl, res, true>, NR_VAR_DC},
 #define NR_ENTRY_ZIP(w, l, hl, gl, res) {w, l, hl, gl, res, (const void*)k_nr_tree<w, l, hl, gl, res, false, true>, NR_VAR_ZIP}, \
                                         {w, l, hl, gl, res, (const void*)k_nr_tree<w, l, hl, gl, res, true, true>, NR_VAR_DC | NR_VAR_ZIP},
+#define NR_ENTRY_GEN(w, l, hl, gl, res) {w, l, hl, gl, res, (const void*)k_nr_tree<w, l, hl, gl, res, false, false, true>, NR_VAR_GEN}, \
+                                        {w, l, hl, gl, res, (const void*)k_nr_tree<w, l, hl, gl, res, true, false, true>, NR_VAR_DC | NR_VAR_GEN},
 
 extern const NrInst NR_CAT(nr_insts_, NR_INST_PART)[] = { NR_CAT(NR_INSTS_, NR_INST_PART)(NR_ENTRY) NR_CAT(NR_INSTS_DC_, NR_INST_PART)(NR_ENTRY_DC)
-                                                          NR_CAT(NR_INSTS_ZIP_, NR_INST_PART)(NR_ENTRY_ZIP) };
+                                                          NR_CAT(NR_INSTS_ZIP_, NR_INST_PART)(NR_ENTRY_ZIP)
+                                                          NR_CAT(NR_INSTS_GEN_, NR_INST_PART)(NR_ENTRY_GEN) };
 extern const int NR_CAT(nr_n_insts_, NR_INST_PART) = (int)(sizeof(NR_CAT(nr_insts_, NR_INST_PART)) / sizeof(NrInst));
 
 #ifdef MAPDN_NR_STAMPS

@@ -53,8 +53,20 @@
   X(4, 8, true, false, 3) X(4, 8, true, false, 2) X(4, 16, false, false, 2) X(4, 8, false, false, 0)
 #define NR_INSTS_ZIP_3(X)
 
+// generators (k_nr_tree<..., GEN = true>, mapdn_netspec.gen_*), with the flat and with the DC start: the geometries of the ZIP lists —
+// the specialised ones of the three feeder classes and the lean generic body of each candidate pair, so that the chooser always finds
+// one — dealt over the four parts so that they compile in about the same time; other geometries are refused ("not compiled in")
+#define NR_INSTS_GEN_0(X) \
+  X(1, 16, true, true, 1) X(4, 16, true, false, 1)
+#define NR_INSTS_GEN_1(X) \
+  X(2, 16, false, false, 2) X(4, 16, true, false, 3)
+#define NR_INSTS_GEN_2(X) \
+  X(4, 8, true, false, 3) X(4, 8, true, false, 2)
+#define NR_INSTS_GEN_3(X) \
+  X(4, 16, false, false, 0) X(1, 16, false, false, 0) X(2, 16, false, false, 0) X(4, 16, false, false, 2) X(4, 8, false, false, 0)
+
 namespace mapdn {
-struct NrInst { int W, L, HL, GL, RES; const void* fn; int VAR; };   // VAR: 0 | NR_VAR_DC (DC-angle start) | NR_VAR_ZIP (ZIP loads), or both
+struct NrInst { int W, L, HL, GL, RES; const void* fn; int VAR; };   // VAR: 0 | NR_VAR_DC (DC-angle start) | NR_VAR_ZIP (ZIP loads) | NR_VAR_GEN (generators)
 enum { NR_INST_PARTS = 4 };
 extern const NrInst nr_insts_0[]; extern const int nr_n_insts_0;
 extern const NrInst nr_insts_1[]; extern const int nr_n_insts_1;

@@ -10,13 +10,14 @@
 
 #include <type_traits>
 
+#include "gen_mask.hpp"
 #include "kernels.hpp"
 #include "nr_common.hpp"
 
 namespace mapdn {
 
 // =================================================================================================
-// K2-K5  Newton-Raphson power flow — pandapower/pypower/newtonpf.py (flat start, polar form, full
+// K2-K5 Newton-Raphson power flow — pandapower/pypower/newtonpf.py (flat start, polar form, full
 //        Jacobian every iteration, ||F||inf < tol, <= 10 iterations), for a radial feeder.
 //
 //  Per iteration:
@@ -146,7 +147,15 @@ struct BwdF { d2 h, g01, g23; };                        // factors of one step w
 // after iteration 0 is formed against Sbus_k (cp + ci |V_k| + cz |V_k|^2) with the node's (ci, cz) from d.zip_c (global, L2-resident,
 // read beside the Sbus entry); iteration 0 (the flat-start sweep or the DC start's first full sweep) and the Jacobian stay as they are
 // (no load derivative: runpp's chord-like scheme).  The stored Sbus stays constant-power.  ZIP = false compiles to the kernel of before.
-template <int W, int L, bool HL, bool GL, int RES = 0, bool DC = false, bool ZIP = false>
+// GEN: nets with generators (mapdn_netspec.gen_*; gen_mask.hpp).  A gen bus keeps |V|: the node's block loses its Q row and its |V|
+// column.  The flag travels as bit S_GEN of the step record's flag word (MM_GEN in a record of the mismatch pass) — nothing new is
+// loaded per row — and differs from lane to lane (the workers of a wave hold different nodes), so the mask is a handful of selects in
+// the dependent chain, never a branch: D1 = D2 = 0, D3 = 1, r1 = 0, G2 = G3 = 0; Fq of a gen node reaches neither the right-hand side
+// nor note_mismatch, in the full sweep, the mismatch-only sweep, the flat-start sweep and the mismatch pass alike.  Every node starts
+// at its own magnitude d.v0 (gen bus: its vm_pu; PQ bus: mapdn_netspec.vm_init_pu), the host's flat-start factors are those of that
+// start, and the DC variant scales e^{j theta} by it.  P_gen is in Sbus already (inject.hpp sbus_entry; the fused prologue below
+// subtracts it as well).  GEN = false compiles to the kernel of before.
+template <int W, int L, bool HL, bool GL, int RES = 0, bool DC = false, bool ZIP = false, bool GEN = false>
 __global__ void __launch_bounds__(64 * W)
 k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ terminated, double* __restrict__ info) {
   extern __shared__ d2 lds2[];
@@ -284,6 +293,7 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
             sub_scaled(P, p, d.sgen_scale[j]); sub_scaled(Q, qv, d.sgen_scale[j]);
           }
         }
+        if constexpr (GEN) { if (d.n_gen) P -= d.gen_p_pos[k]; }   // (sbus_entry: a generator on the bus is a constant negative demand)
         if (sbi >= 0) ((double2*)((char*)d.nrbuf + d.sb_off))[(size_t)sbi * S_ + ee] = make_double2(-P / d.sn, -Q / d.sn);
       }
     }
@@ -309,7 +319,8 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
   char* s_flat = s_rec + (d.nr_rec_lds ? (size_t)Wt * R * sizeof(StepRec) : 0);
   {  // LDS init: flat start (runpp init="auto": every bus at the slack set-point), ZERO slots, small tables
     const d2 v0 = {vroot, 0.0}, z2 = {0.0, 0.0};
-    for (unsigned k = t; k < n + 2; k += Wt) sV[(size_t)k * L] = v0;
+    if constexpr (GEN) { for (unsigned k = t; k < n + 2; k += Wt) sV[(size_t)k * L] = d2{d.v0[k], 0.0}; }   // every node at its own magnitude
+    else for (unsigned k = t; k < n + 2; k += Wt) sV[(size_t)k * L] = v0;
     for (unsigned i = threadIdx.x; i < (unsigned)d.nr_nclist; i += 64u * W) s_clist[i] = d.clist[i];
     if (HL && t == 0) sH[(size_t)n * L] = z2;    // the slack entry of the h / x array: the x an elimination root reads
     if (t == 0) {                                // the ZERO slots (second-to-last of each kind) read as 0 forever
@@ -447,7 +458,8 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
         if (k == n) continue;
         double sn_, cs_;
         sincos(sV[(size_t)k * L].y, &sn_, &cs_);
-        sV[(size_t)k * L] = k < n ? d2{vroot * cs_, vroot * sn_} : d2{vroot, 0.0};
+        if constexpr (GEN) { const double vk0 = d.v0[k]; sV[(size_t)k * L] = k < n ? d2{vk0 * cs_, vk0 * sn_} : d2{vroot, 0.0}; }
+        else sV[(size_t)k * L] = k < n ? d2{vroot * cs_, vroot * sn_} : d2{vroot, 0.0};
       }
       if (W > 1) lds_barrier();
     }
@@ -666,18 +678,25 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
         const double sr = base_r + aS0, si = base_i + aS1;
         d2 sbk = T.sb;
         if constexpr (ZIP) sbk = zip_sb(T.sb, zq[u % 3], v2);
-        const double Fp = sr - sbk.x, Fq = si - sbk.y;
+        const bool gen = GEN && (fl & S_GEN) != 0;       // (lane-divergent: selects below, no branch)
+        const double Fp = sr - sbk.x;
+        double Fq = si - sbk.y;
+        if constexpr (GEN) Fq = gen_mask_fq(gen, Fq);
         pFp = Fp; pFq = Fq; pLive = (fl & S_LIVE) != 0;
         if constexpr (K == 0) {
-          const double D0 = -(si - akk_i) - aD0, D1 = (sr + akk_r) - aD1;
-          const double D2 = (sr - akk_r) - aD2, D3 = (si + akk_i) - aD3;
-          const double r0 = Fp - aR0, r1 = Fq - aR1;
+          const double D0 = -(si - akk_i) - aD0;
+          double D1 = (sr + akk_r) - aD1, D2 = (sr - akk_r) - aD2, D3 = (si + akk_i) - aD3;
+          const double r0 = Fp - aR0;
+          double r1 = Fq - aR1;
+          if constexpr (GEN) gen_mask_pivot(gen, D1, D2, D3, r1);
           const double idet = rcp_nr(D0 * D3 - D1 * D2);
-          const double I0 = D3 * idet, I1 = -D1 * idet, I2 = -D2 * idet, I3 = D0 * idet;
+          double I0 = D3 * idet, I1 = -D1 * idet, I2 = -D2 * idet, I3 = D0 * idet;
+          if constexpr (GEN) gen_pivot_inverse(gen, D0, D1, D2, D3, idet, I0, I1, I2, I3);
           const double h0 = I0 * r0 + I1 * r1, h1 = I2 * r0 + I3 * r1;
           // U = J'(k,p) = [[Im A_kp, Re A_kp], [-Re A_kp, Im A_kp]],  L = J'(p,k) likewise from A_pk
           const double G0 = I0 * akp_i - I1 * akp_r, G1 = I0 * akp_r + I1 * akp_i;
-          const double G2 = I2 * akp_i - I3 * akp_r, G3 = I2 * akp_r + I3 * akp_i;
+          double G2 = I2 * akp_i - I3 * akp_r, G3 = I2 * akp_r + I3 * akp_i;
+          if constexpr (GEN) gen_mask_factor(gen, G2, G3);
           const double s0 = apk_i * G0 + apk_r * G2, s1 = apk_i * G1 + apk_r * G3;
           const double s2 = apk_i * G2 - apk_r * G0, s3 = apk_i * G3 - apk_r * G1;
           const double t0 = apk_i * h0 + apk_r * h1, t1 = apk_i * h1 - apk_r * h0;
@@ -750,7 +769,10 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
         SCHED_FENCE();
         STAMP2(230);
         const double s_r = T.s.x, s_i = T.s.y, i0 = T.i01.x, i1 = T.i01.y, i2 = T.i23.x, i3 = T.i23.y, ap_r = T.ap.x, ap_i = T.ap.y;
-        const double Fp = s_r - T.sb.x, Fq = s_i - T.sb.y;           // shadow: the flat-start mismatch does not depend on children
+        const bool gen = GEN && (fl & S_GEN) != 0;
+        const double Fp = s_r - T.sb.x;                              // shadow: the flat-start mismatch does not depend on children
+        double Fq = s_i - T.sb.y;
+        if constexpr (GEN) Fq = gen_mask_fq(gen, Fq);
         note_mismatch(Fp, Fq, (fl & S_LIVE) != 0);
         const double m = (fl & S_CARRY_IN) ? 1.0 : 0.0;
         SCHED_FENCE();
@@ -770,7 +792,9 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
             }
           }
         }
-        const double r0 = Fp - aR0, r1 = Fq - aR1;
+        const double r0 = Fp - aR0;
+        double r1 = Fq - aR1;
+        if constexpr (GEN) r1 = gen ? 0.0 : r1;                      // (the host's D^-1 of a gen node is [[1 / D0, 0], [0, 1]]: h1 = r1 = 0)
         const double h0 = i0 * r0 + i1 * r1, h1 = i2 * r0 + i3 * r1;
         const double t0 = ap_i * h0 + ap_r * h1, t1 = ap_i * h1 - ap_r * h0;
         cR0 = t0; cR1 = t1;
@@ -980,7 +1004,9 @@ k_nr_tree(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ te
         const double sr = base_r + aS0, si = base_i + aS1;
         d2 sbk = sb;
         if constexpr (ZIP) sbk = zip_sb(sb, zc, v2);
-        note_mismatch(sr - sbk.x, si - sbk.y, (ix.x & 1u) != 0);
+        double Fq = si - sbk.y;
+        if constexpr (GEN) Fq = gen_mask_fq((ix.x & MM_GEN) != 0, Fq);
+        note_mismatch(sr - sbk.x, Fq, (ix.x & 1u) != 0);
         STAMP(120);
       }
     }

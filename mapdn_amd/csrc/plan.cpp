@@ -1,5 +1,6 @@
 // plan.cpp — see plan.hpp.  Host only (no HIP).
 #include "plan.hpp"
+#include "gen_mask.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -88,6 +89,30 @@ int build_plan(const mapdn_netspec& net_o, const mapdn_env_config& cfg, Plan& P,
       }
     }
   }
+  if (net_o.n_gen < 0) { err = "netspec: n_gen must be >= 0"; return MAPDN_E_INVALID; }
+  if (net_o.n_gen > 0) {   // generators: validated here, on the caller's buses; reduced to per-node constants in build_plan_nodes
+    if (!net_o.gen_bus || !net_o.gen_p_mw || !net_o.gen_vm_pu) { err = "netspec: n_gen > 0 needs gen_bus, gen_p_mw and gen_vm_pu"; return MAPDN_E_INVALID; }
+    if (fused) { err = "generators (net.gen) on a net with fused buses (bus_alias) are not supported"; return MAPDN_E_INVALID; }
+    for (int i = 0; i < net_o.n_load; ++i)
+      if ((net_o.load_const_z && net_o.load_const_z[i] != 0.0) || (net_o.load_const_i && net_o.load_const_i[i] != 0.0)) {
+        err = "generators (net.gen) together with voltage-dependent loads (load_const_z / load_const_i) are not supported"; return MAPDN_E_INVALID; }
+    std::vector<int> at(nbo, -1);
+    for (int g = 0; g < net_o.n_gen; ++g) {
+      const int b = net_o.gen_bus[g];
+      if (b < 0 || b >= nbo) { err = "netspec: gen bus out of range"; return MAPDN_E_INVALID; }
+      if (b == net_o.ext_grid_bus) {
+        err = "gen " + std::to_string(g) + " on the ext_grid bus (the slack bus) is not supported: the slack already holds that voltage"; return MAPDN_E_INVALID; }
+      if (at[b] >= 0) {
+        err = "gens " + std::to_string(at[b]) + " and " + std::to_string(g) + " share bus " + std::to_string(b) +
+              ": two in-service gens on one bus are not supported (runpp merges them into one voltage-controlled bus and splits Q between them)";
+        return MAPDN_E_INVALID; }
+      at[b] = g;
+      const double sc = net_o.gen_scaling ? net_o.gen_scaling[g] : 1.0;
+      if (!std::isfinite(net_o.gen_p_mw[g]) || !std::isfinite(sc) || !(net_o.gen_vm_pu[g] > 0.0) || !std::isfinite(net_o.gen_vm_pu[g])) {
+        err = "netspec: gen " + std::to_string(g) + " needs finite p_mw / scaling and a finite vm_pu > 0"; return MAPDN_E_INVALID; }
+    }
+  }
+  if (std::isfinite(net_o.vm_init_pu) && net_o.vm_init_pu < 0.0) { err = "netspec: vm_init_pu must be > 0 (0 or NaN = derive it)"; return MAPDN_E_INVALID; }
   if (!fused) {
     int rc = build_plan_nodes(net_o, net_o, cfg, P, err);
     if (rc) return rc;
@@ -124,7 +149,8 @@ int build_plan(const mapdn_netspec& net_o, const mapdn_env_config& cfg, Plan& P,
   E.ext_grid_bus = eid[net_o.ext_grid_bus]; E.bus_alias = nullptr;
   int rc = build_plan_nodes(E, net_o, cfg, P, err);
   if (rc) return rc;
-  P.dc_ok = false;                                // the DC-angle start is not defined on fused buses (as oracle/pp_restated.py refuses it)
+  if (P.gen_start) { err = "vm_init_pu other than ext_grid_vm_pu (out-of-service net.gen rows move runpp's start) on a net with fused buses (bus_alias) is not supported"; return MAPDN_E_INVALID; }
+  P.dc_ok = false;                              // the DC-angle start is not defined on fused buses (as oracle/pp_restated.py refuses it)
   // ---- the reporting layer
   P.nbo = nbo;
   P.pos_of_obus.resize(nbo);
@@ -425,6 +451,33 @@ static int build_plan_nodes(const mapdn_netspec& net, const mapdn_netspec& net_o
     P.zip_c[2 * k] = c; P.zip_c[2 * k + 1] = z;
     P.zip = true;
   }
+  // ---- generators (build_plan checked them): gen buses, the start magnitudes of runpp's init_vm_pu="auto", the Ybus rows Q_gen needs
+  P.n_gen = net.n_gen;
+  P.gen_pos.assign(P.n_gen, 0); P.gen_p.assign(P.n_gen, 0.0); P.gen_vm.assign(P.n_gen, 1.0);
+  P.gen_of_pos.assign((size_t)P.n + 2, -1); P.is_gen.assign((size_t)P.n + 2, 0); P.gen_p_pos.assign((size_t)P.n + 2, 0.0);
+  {
+    double sum = P.vroot;                          // the mean over ext_grid and gen rows, in table order (numpy's order for a handful of rows)
+    for (int g = 0; g < P.n_gen; ++g) sum += net.gen_vm_pu[g];
+    const bool given = std::isfinite(net.vm_init_pu) && net.vm_init_pu > 0.0;
+    P.vm_init = given ? net.vm_init_pu : (P.n_gen ? sum / (double)(P.n_gen + 1) : P.vroot);
+  }
+  P.v0.assign((size_t)P.n + 2, P.vm_init);
+  P.v0[P.n] = P.vroot; P.v0[(size_t)P.n + 1] = P.vroot;   // the slack; the trash node of idle steps hangs off the slack with mismatch 0
+  P.gq_ptr.assign(1, 0); P.gq_col.clear(); P.gq_val.clear();
+  for (int g = 0; g < P.n_gen; ++g) {
+    const int k = P.pos_of_bus[net.gen_bus[g]];
+    P.gen_pos[g] = k; P.gen_of_pos[k] = g; P.is_gen[k] = 1;
+    P.gen_p[g] = net.gen_p_mw[g] * (net.gen_scaling ? net.gen_scaling[g] : 1.0);
+    P.gen_vm[g] = net.gen_vm_pu[g];
+    P.gen_p_pos[k] = P.gen_p[g]; P.v0[k] = P.gen_vm[g];
+    for (int q = P.gy_ptr[k]; q < P.gy_ptr[k + 1]; ++q) { P.gq_col.push_back(P.gy_col[q]); P.gq_val.push_back(P.gy_val[2 * q]); P.gq_val.push_back(P.gy_val[2 * q + 1]); }
+    P.gq_ptr.push_back((int32_t)P.gq_col.size());
+  }
+  P.gen_start = P.n_gen > 0 || P.vm_init != P.vroot;
+  if (P.gen_start && P.zip) {                    // (with gens: build_plan refused already; this is the start-only case)
+    err = "vm_init_pu other than ext_grid_vm_pu (out-of-service net.gen rows move runpp's start) together with voltage-dependent loads "
+          "(load_const_z / load_const_i) is not supported";
+    return MAPDN_E_INVALID; }
 
   // ---- get_obs (distributed mode) — voltage_control_env.py:245-274 --------------------------------
   const int ss = cfg.state_space;
@@ -537,7 +590,8 @@ void sparse_program(const Plan& P, int S, SparseProg& G) {
     for (int q = P.gy_ptr[i]; q < P.gy_ptr[i + 1]; ++q) {
       const int j = P.gy_col[q];
       SpNz& z = G.nz[r * G.max_nnz + (q - P.gy_ptr[i])];
-      z.col = (uint32_t)j; z.y[0] = P.gy_val[2 * q]; z.y[1] = P.gy_val[2 * q + 1];
+      z.col = (uint32_t)j | ((!P.is_gen.empty() && P.is_gen[j]) ? SP_COL_GEN : 0u);   // (the column's node is a gen bus: its |V| column is struck out)
+      z.y[0] = P.gy_val[2 * q]; z.y[1] = P.gy_val[2 * q + 1];
       z.slot = (j < n && j != i) ? Y.slot.at({i, j}) : -1;
       if (!P.gy_dc.empty()) z.bdc = P.gy_dc[q];
     }
@@ -598,6 +652,8 @@ void build_schedule(const Plan& P, int W, Schedule& S, int min_cslots, int Sw, i
   std::vector<int> depth(n + 1, 0);
   for (int k = n - 1; k >= 0; --k) depth[k] = depth[P.par[k]] + 1;  // parents have larger positions
   auto chain_child = [&](int k) { return (k > 0 && (P.flags[k - 1] & F_PARENT_NEXT)) ? k - 1 : -1; };
+  auto gen_at = [&](int k) { return !P.is_gen.empty() && P.is_gen[k] != 0; };                     // (a plan without the generator tables: none)
+  auto v0_at = [&](int k) { return P.v0.empty() ? P.vroot : P.v0[k]; };
   std::vector<int> pending(n, 0), row_of(n, -1), wave_of(n, -1);
   for (int k = 0; k < n; ++k) pending[k] = (int)children[k].size();
   std::vector<int> ready;
@@ -708,7 +764,7 @@ void build_schedule(const Plan& P, int W, Schedule& S, int min_cslots, int Sw, i
       T.cks[0] = c[6]; T.cks[1] = c[7];
       const int p = P.par[k];
       T.kp = (uint32_t)k | ((uint32_t)p << 16);
-      uint32_t f = S_LIVE, os = c_trash, xsl = x_trash, pxs = x_zero;
+      uint32_t f = S_LIVE | (gen_at(k) ? (uint32_t)S_GEN : 0u), os = c_trash, xsl = x_trash, pxs = x_zero;
       if (p == n) f |= S_PARENT_ROOT;
       else if (carry_out[k]) f |= S_CARRY_OUT;
       else { f |= S_SCRATCH_OUT; os = (uint32_t)oslot[k]; pxs = (uint32_t)xslot[p]; }
@@ -760,29 +816,34 @@ void build_schedule(const Plan& P, int W, Schedule& S, int min_cslots, int Sw, i
       const int k = live ? kx : n - 1;               // (a repeated node rewrites the same value; its verdict is masked)
       const int c_lo = S.mm_ptr[k], nch = live ? S.mm_ptr[k + 1] - c_lo : 0;
       auto child = [&](int q) { return (uint32_t)(q < nch ? S.mm_child[c_lo + q] : n + 1); };   // absent: the trash node
-      T.flags = (live ? 1u : 0u) | ((uint32_t)std::min(nch, 255) << 8);
+      T.flags = (live ? 1u : 0u) | ((live && gen_at(k)) ? (uint32_t)MM_GEN : 0u) | ((uint32_t)std::min(nch, 255) << 8);
       T.slots = child(0) | (child(1) << 16);
       T.chs = child(2);
       T.kp = (uint32_t)k | ((uint32_t)P.par[k] << 16);
       const double* c = &P.yc[(size_t)k * 8];
       T.ykk[0] = c[0]; T.ykk[1] = c[1]; T.ykp[0] = c[2]; T.ykp[1] = c[3]; T.ypk[0] = c[4]; T.ypk[1] = c[5]; T.cks[0] = c[6]; T.cks[1] = c[7];
     }
-  // ---- flat-start factorisation (same formulas as k_nr_tree's forward step with V == vroot everywhere)
+  // ---- flat-start factorisation (same formulas as k_nr_tree's forward step at the start of runpp's init="auto": every angle 0, the
+  // magnitudes of Plan::v0 — vroot everywhere on a net without generators; the block of a gen bus masked, gen_mask.hpp)
   {
-    const double v = P.vroot, v2 = v * v;
     std::vector<double> aS((size_t)n * 2, 0.0), aD((size_t)n * 4, 0.0), node((size_t)n * FLAT_N, 0.0);
     for (int k = 0; k < n; ++k) {                 // children have smaller positions than their parents
       const double* c = &P.yc[(size_t)k * 8];
+      const double v = v0_at(k), v2 = v * v, vkp = v * v0_at(P.par[k]);   // |V_k|, |V_k|^2, |V_k| |V_parent| (an elimination root's parent: the slack, Y = 0)
+      const bool gen = gen_at(k);
       const double gkk = c[0], bkk = c[1], gkp = c[2], bkp = c[3], gpk = c[4], bpk = c[5];
-      const double akp_r = v2 * gkp, akp_i = -v2 * bkp, apk_r = v2 * gpk, apk_i = -v2 * bpk;
+      const double akp_r = vkp * gkp, akp_i = -vkp * bkp, apk_r = vkp * gpk, apk_i = -vkp * bpk;
       const double akk_r = v2 * gkk, akk_i = -v2 * bkk, aks_r = v * c[6], aks_i = -v * c[7];
       const double sr = (akk_r + aks_r) + akp_r + aS[2 * k], si = (akk_i + aks_i) + akp_i + aS[2 * k + 1];
-      const double D0 = -(si - akk_i) - aD[4 * k], D1 = (sr + akk_r) - aD[4 * k + 1];
-      const double D2 = (sr - akk_r) - aD[4 * k + 2], D3 = (si + akk_i) - aD[4 * k + 3];
+      const double D0 = -(si - akk_i) - aD[4 * k];
+      double D1 = (sr + akk_r) - aD[4 * k + 1], D2 = (sr - akk_r) - aD[4 * k + 2], D3 = (si + akk_i) - aD[4 * k + 3], r1_unused = 0.0;
+      gen_mask_pivot(gen, D1, D2, D3, r1_unused);
       const double idet = 1.0 / (D0 * D3 - D1 * D2);
-      const double I0 = D3 * idet, I1 = -D1 * idet, I2 = -D2 * idet, I3 = D0 * idet;
+      double I0, I1, I2, I3;
+      gen_pivot_inverse(gen, D0, D1, D2, D3, idet, I0, I1, I2, I3);
       const double G0 = I0 * akp_i - I1 * akp_r, G1 = I0 * akp_r + I1 * akp_i;
-      const double G2 = I2 * akp_i - I3 * akp_r, G3 = I2 * akp_r + I3 * akp_i;
+      double G2 = I2 * akp_i - I3 * akp_r, G3 = I2 * akp_r + I3 * akp_i;
+      gen_mask_factor(gen, G2, G3);
       double* o = &node[(size_t)k * FLAT_N];
       o[FL_SR] = sr; o[FL_SI] = si; o[FL_I0] = I0; o[FL_I1] = I1; o[FL_I2] = I2; o[FL_I3] = I3;
       o[FL_APR] = apk_r; o[FL_API] = apk_i; o[FL_G0] = G0; o[FL_G1] = G1; o[FL_G2] = G2; o[FL_G3] = G3;

@@ -37,7 +37,7 @@ enum : int32_t {
 // by the kernel two rows ahead with no dependent address (5 x buffer_load_dwordx4, the 16 lanes of a worker read the
 // same record).  Every slot / node index is always valid: the host substitutes a ZERO slot for absent children /
 // parents and a TRASH slot or node for outputs nobody reads, so the kernel's step body is branch-free per lane.
-//   flags : S_* bits 0-5 | wave-uniform hints bits 6-10 (see SU_*) | number of slot children << 16 | cptr bits 0-7 << 24
+//   flags : S_* bits 0-5 | wave-uniform hints bits 6-11 (see SU_*) | S_GEN bit 12 | number of slot children << 16 | cptr bits 0-7 << 24
 //   slots : oslot | xslot << 10 | pxslot << 20 (contribution / x slots this node writes, parent's x slot) | cptr bits 8-9 << 30
 //   chs   : ch0 | ch1 << 10 | ch2 << 20 (contribution slots of the first three slot children, canonical order) | cptr bits 10-11 << 30
 //   kp    : node position | parent position << 16   (idle step: trash node n+1; no parent: slack position n with Y = 0)
@@ -70,6 +70,8 @@ enum : uint32_t {
   S_SCRATCH_OUT = 8u,    // own contribution goes to a real LDS slot (parent gathers it)
   S_X_OUT = 16u,         // backward sweep: x_k goes to a real LDS slot (some child reads it)
   S_LIVE = 32u,          // not an idle step
+  S_GEN = 4096u,         // the node is a gen bus (gen_mask.hpp): bit 12, between the hints and the child count; differs from lane to lane
+  MM_GEN = 2u,           // ... and the same in a record of the mismatch pass (Schedule::mm_recs: flags = live | MM_GEN | children << 8)
   // wave-uniform hints: the same value in the records of all workers of one wavefront in one row, so the kernel can
   // skip LDS traffic that would only move zeros / trash (it reads them with readfirstlane)
   SU_GMAX_SHIFT = 6u,    // bits 6-7: max number of slot children over the wave's workers, saturated at 3
@@ -162,6 +164,18 @@ struct Plan {
   // zip_c [n + 2][2] by position = (ci, cz) of the bus's loads (all loads of a bus carry the same fractions; slack and trash rows 0)
   bool zip = false;
   std::vector<double> zip_c;
+  // generators (mapdn_netspec.gen_*; gen_mask.hpp): a gen's bus is a GEN BUS — |V| held, P given, Q free.  gen_start: the solvers run their
+  // GEN form (some gen bus, or a PQ start other than the slack set-point: out-of-service gen rows move runpp's mean); false = the path of before.
+  int32_t n_gen = 0;
+  bool gen_start = false;
+  double vm_init = 1.0;                         // |V| every PQ bus starts from (runpp init_vm_pu="auto")
+  std::vector<int32_t> gen_pos, gen_of_pos;     // [n_gen] position of the gen's bus; [n + 2] gen at a position, or -1
+  std::vector<double> gen_p, gen_vm;            // [n_gen] p_mw x scaling (MW), vm_pu
+  std::vector<uint8_t> is_gen;                  // [n + 2] by position (slack and trash rows 0)
+  std::vector<double> gen_p_pos;                // [n + 2] by position: the gen's P (MW), 0 elsewhere — what the bus injection subtracts from the demand
+  std::vector<double> v0;                       // [n + 2] by position: the start magnitudes (gen bus: its vm_pu; slack and trash: vroot; else vm_init)
+  std::vector<int32_t> gq_ptr, gq_col;          // the Ybus rows of the gen nodes, CSR over the gens (columns: positions, n == slack): the commit
+  std::vector<double> gq_val;                   // forms Q_gen = Im(V_k conj((Ybus V)_k)) sn + QD_k from them; (re, im) per entry
 
   // get_obs / get_state tables
   int32_t n_agents = 0, obs_size = 0, state_size = 0, max_zone = 0;
@@ -178,7 +192,8 @@ struct Plan {
 // block array as [b | 0] blocks, so substitution uses the same three operations.  What pandapower leaves to SuperLU
 // at run time (pypower newtonpf.py: dx = -spsolve(J, F)) is thus decided here, off the hot path.
 struct SpOp { uint32_t type, c, a, b; };                                  // type: 0 NOP, 1 INV, 2 MUL, 3 UPD; block slots
-struct SpNz { uint32_t col; int32_t slot; double y[2]; double bdc; };   // Ybus entry of a row: column position (n = slack), block slot (-1: none), Y;
+enum : uint32_t { SP_COL_GEN = 0x80000000u };                             // bit 31 of SpNz::col: the column's node is a gen bus (gen_mask.hpp)
+struct SpNz { uint32_t col; int32_t slot; double y[2]; double bdc; };   // Ybus entry of a row: column position (n = slack) | SP_COL_GEN, block slot (-1: none), Y;
                                                                     // bdc: the Bbus entry (the DC-angle start assembles it instead of the Jacobian)
 struct SpRow { uint32_t node, nnz, sb, live; };                           // assembly row: position, entries, Sbus entry, 1 if a real node
 static_assert(sizeof(SpOp) == 16 && sizeof(SpNz) == 32 && sizeof(SpRow) == 16, "sparse program records");

@@ -19,11 +19,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gen_mask.hpp"
 #include "kernels.hpp"
 #include "nr_common.hpp"
 
 namespace mapdn {
 
+// Generators (d.gen_start, a run-time branch like ZIP): every node starts at its own magnitude d.v0; at block assembly the Q row of every
+// block in a gen node's block row and the |V| column of every block in its block column are zeroed, its diagonal block's (2, 2) is 1 and
+// the Q entry of its right-hand side 0 (gen_mask.hpp) — the program is untouched, fill blocks inherit the zeros; the verdict skips its Fq.
 // DC: runpp init="dc" (mapdn_env_config.nr_init = 2) — before the first iteration the same program solves Bbus theta = Pbus per env
 // (the DC power flow of pandapower run_dc_pf) and the solve starts from V0 = vroot e^{j theta}; DC = false: the flat start.
 template <int L, bool DC = false>
@@ -38,7 +42,10 @@ k_nr_sparse(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ 
   d2* sV = lds2 + el;                                              // sV[k * L] = (e, f); k = n slack, n + 1 trash
   d2* sB = lds2 + (size_t)(n + 2) * L + 2u * el;                   // block b: sB[b * 2L], sB[b * 2L + 1] = rows (a00 a01), (a10 a11)
   double* s_epi = (double*)(lds2 + (size_t)(n + 2) * L + (size_t)d.sp_blocks * 2u * L) + el;   // 10 * S * L doubles (epilogue), also the verdict scratch
-  for (unsigned k = s; k < (unsigned)n + 2u; k += S) sV[(size_t)k * L] = d2{vroot, 0.0};        // runpp init="auto": flat start
+  const bool gens = d.gen_start != 0;            // generators (run-time branch, wave-uniform): per-node start magnitudes, masked gen blocks
+  auto v0_of = [&](unsigned k) { return gens ? d.v0[k] : vroot; };
+  auto gen_at = [&](unsigned k) { return gens && d.is_gen[k] != 0; };
+  for (unsigned k = s; k < (unsigned)n + 2u; k += S) sV[(size_t)k * L] = d2{v0_of(k), 0.0};     // runpp init="auto": flat start
   const bool act = d.active[e] != 0;
   const int bk_steps = d.steps[e];
   const uint32_t bk_draw = d.draw[e];
@@ -101,7 +108,7 @@ k_nr_sparse(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ 
         double bii = 0.0;
         for (int q = 0; q < MNZ; ++q) {
           const SpNz zq = z[q];
-          if (zq.col == i) bii = zq.bdc;
+          if ((zq.col & ~SP_COL_GEN) == i) bii = zq.bdc;
           else if (zq.slot >= 0) { d2* o = blk((unsigned)zq.slot); o[0] = d2{zq.bdc, 0.0}; o[1] = d2{0.0, 0.0}; }
         }
         d2* dg = blk(i);
@@ -115,7 +122,8 @@ k_nr_sparse(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ 
         if (i < (unsigned)n && !done) {
           double sn, cs;
           sincos(blk((unsigned)n + i)[0].x, &sn, &cs);
-          sV[(size_t)i * L] = d2{vroot * cs, vroot * sn};
+          const double v0 = v0_of(i);
+          sV[(size_t)i * L] = d2{v0 * cs, v0 * sn};
         }
       }
     }
@@ -147,6 +155,7 @@ k_nr_sparse(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ 
       bool live = i < (unsigned)n;
       double2 sb = gsb[(size_t)(live ? i : 0u) * d.Bp + e];
       d2 vi = sV[(size_t)(live ? i : (unsigned)n + 1u) * L];
+      bool gi = live && gen_at(i);               // this row's node is a gen bus
       double sr = 0.0, si = 0.0, aii_r = 0.0, aii_i = 0.0;
       for (int t0 = 0; t0 < T; t0 += PF) {
 #pragma unroll
@@ -156,7 +165,7 @@ k_nr_sparse(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ 
           const u32x4 z0 = zq0[u]; const u32x2 z1 = zq1[u];
           zload(t + PF, zq0[u], zq1[u]);
           const double g = __hiloint2double((int)z0.w, (int)z0.z), b = __hiloint2double((int)z1.y, (int)z1.x);
-          const unsigned col = z0.x;
+          const unsigned col = z0.x & ~SP_COL_GEN;               // (bit 31: the column's node is a gen bus — rides in the prefetched record)
           const int slot = (int)z0.y;
           const d2 vj = sV[(size_t)col * L];
           const double ei = vi.x, fi = vi.y;
@@ -164,7 +173,13 @@ k_nr_sparse(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ 
           const double ar = ei * tr + fi * ti, ai = fi * tr - ei * ti;           // A_ij = V_i conj(Y_ij V_j)
           sr += ar; si += ai;
           if (col == i) { aii_r = ar; aii_i = ai; }
-          if (slot >= 0) { d2* o = blk((unsigned)slot); o[0] = d2{ai, ar}; o[1] = d2{-ar, ai}; }
+          if (slot >= 0) {
+            d2* o = blk((unsigned)slot);
+            if (gens) {                          // gen buses (gen_mask.hpp): no Q row in the block row of one, no |V| column in its block column
+              const bool gj = (z0.x & SP_COL_GEN) != 0;
+              o[0] = d2{ai, gj ? 0.0 : ar}; o[1] = gi ? d2{0.0, 0.0} : d2{-ar, gj ? 0.0 : ai};
+            } else { o[0] = d2{ai, ar}; o[1] = d2{-ar, ai}; }
+          }
           if (++q == MNZ) {                      // (uniform) end of the row: diagonal block, right-hand side, verdict; next row
             double sbr = sb.x, sbi = sb.y;
             if (d.zip && it > 0) {               // voltage-dependent loads: makeSbus(vm = |V|) after the first voltage update (as k_nr_tree)
@@ -173,17 +188,20 @@ k_nr_sparse(Dev d, int mode, double* __restrict__ reward, uint8_t* __restrict__ 
               const double vd = fma(zc.y, v2, fma(zc.x, sqrt(v2), 1.0 - (zc.x + zc.y)));
               sbr *= vd; sbi *= vd;
             }
-            const double Fp = sr - sbr, Fq = si - sbi;
+            const double Fp = sr - sbr, Fq = gen_mask_fq(gi, si - sbi);
             if (live) {
               d2* dg = blk(i);
-              dg[0] = d2{-(si - aii_i), sr + aii_r}; dg[1] = d2{sr - aii_r, si + aii_i};
+              double D1 = sr + aii_r, D2 = sr - aii_r, D3 = si + aii_i, r1 = Fq;
+              gen_mask_pivot(gi, D1, D2, D3, r1);
+              dg[0] = d2{-(si - aii_i), D1}; dg[1] = d2{D2, D3};
               d2* rh = blk((unsigned)n + i);
-              rh[0] = d2{Fp, 0.0}; rh[1] = d2{Fq, 0.0};
+              rh[0] = d2{Fp, 0.0}; rh[1] = d2{r1, 0.0};
               ok = ok && (fabs(Fp) < tol) && (fabs(Fq) < tol);
             }
             q = 0; ++r;
             i = (unsigned)r * S + s;
             live = i < (unsigned)n && r < RPS;
+            gi = live && gen_at(i);
             sb = gsb[(size_t)(live ? i : 0u) * d.Bp + e];
             vi = sV[(size_t)(live ? i : (unsigned)n + 1u) * L];
             sr = si = aii_r = aii_i = 0.0;

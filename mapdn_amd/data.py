@@ -153,13 +153,13 @@ def trafo_to_pi(trafo, bus_vn_kv: np.ndarray, net_sn_mva: float, calculate_volta
                 br_vn_lv_kv=vn_lv_kv, br_rating_mva=_rating(sn_t * parallel * _col(t, "df", 1.0)))
 
 
-def from_pandapower(net, hv_init: str = "refuse", zip_loads: str = "refuse") -> NetSpec:
+def from_pandapower(net, hv_init: str = "refuse", zip_loads: str = "refuse", gens: str = "refuse") -> NetSpec:
     """pandapowerNet (`pp.from_pickle(model.p)`, voltage_control_env.py:400-405) -> NetSpec: what pd2ppc would build for
     runpp's defaults.  Converted: buses (0..n-1, all in service), lines (an open line / trafo switch takes the branch out
     when that is exact — no shunt terms, or open at both ends — and is refused otherwise), two-winding transformers (trafo_to_pi), loads / sgens with `scaling` and `in_service`,
     non-consecutive bus indices (mapped to the positions of the sorted index, pd2ppc's bus lookup),
     shunts (step, in_service), one ext_grid, closed bus-bus switches (bus fusion -> NetSpec.bus_alias).  Refused loudly, never guessed: voltage-dependent loads
-    (const_z_percent / const_i_percent != 0) unless zip_loads="runpp", generators, three-winding transformers, impedances, wards, dc lines, storage,
+    (const_z_percent / const_i_percent != 0) unless zip_loads="runpp", generators (net.gen) unless gens="runpp", three-winding transformers, impedances, wards, dc lines, storage,
     closed bus-bus switches with z_ohm > 0 (pandapower models them as impedance branches, not as fused buses), fused buses of different vn_kv, and
     — by default (hv_init="refuse") — nets with a line at a bus above 70 kV: runpp's defaults then turn calculate_voltage_angles on AND start
     the Newton iteration from a DC power flow's angles (init="auto" -> "dc").
@@ -170,7 +170,15 @@ def from_pandapower(net, hv_init: str = "refuse", zip_loads: str = "refuse") -> 
     zip_loads="runpp" converts voltage-dependent loads as runpp's voltage_depend_loads=True solves them (NetSpec.load_const_z /
     load_const_i = percent / 100).  Still refused with it: loads of different fractions on one bus (runpp solves
     with their row-count mean but reports each load with its own), a voltage-dependent load on the ext_grid bus, and voltage-dependent
-    loads on a net with fused buses."""
+    loads on a net with fused buses.
+    gens="runpp" converts the in-service rows of net.gen as runpp's defaults solve them (NetSpec.gen_bus / gen_p_mw / gen_vm_pu /
+    gen_scaling): the gen's bus holds |V| = vm_pu and injects p_mw * scaling, its Q is free (enforce_q_lims=False:
+    min_q_mvar / max_q_mvar are not read), and every bus without a set-point starts the Newton iteration at the mean of the vm_pu of the
+    ext_grid and of ALL net.gen rows, in service or not (NetSpec.vm_init_pu; init_vm_pu="auto").  Gens are not agents.  Still refused with
+    it, by name: two in-service gens on one bus, a gen on the ext_grid's bus or with slack=True, gens on a net with fused buses, gens
+    together with voltage-dependent loads."""
+    if gens not in ("refuse", "runpp"):
+        raise ValueError("gens must be 'refuse' or 'runpp'")
     if hv_init not in ("refuse", "flat", "auto"):
         raise ValueError("hv_init must be 'refuse', 'flat' or 'auto'")
     if zip_loads not in ("refuse", "runpp"):
@@ -178,7 +186,7 @@ def from_pandapower(net, hv_init: str = "refuse", zip_loads: str = "refuse") -> 
     def table(name):
         t = net[name] if name in net else None
         return t if t is not None and len(t) else None
-    for name in ("gen", "trafo3w", "impedance", "ward", "xward", "dcline", "storage", "motor", "asymmetric_load", "asymmetric_sgen"):
+    for name in (("gen",) if gens == "refuse" else ()) + ("trafo3w", "impedance", "ward", "xward", "dcline", "storage", "motor", "asymmetric_load", "asymmetric_sgen"):
         t = table(name)
         if t is not None and (("in_service" not in t) or t["in_service"].to_numpy(bool).any()):
             raise NotImplementedError(f"net.{name} has in-service rows: not part of the MAPDN hot path, not converted")
@@ -306,6 +314,36 @@ def from_pandapower(net, hv_init: str = "refuse", zip_loads: str = "refuse") -> 
                                           "const_i_percent: runpp solves with their row-count mean and reports each load with its own "
                                           "polynomial, which is not converted")
         kw.update(load_const_z=cz, load_const_i=ci)
+    gen = table("gen")
+    if gen is not None and gens == "runpp":
+        gen = gen.sort_index()
+        g_on = gen["in_service"].to_numpy(bool) if "in_service" in gen else np.ones(len(gen), bool)
+        g_bus = rb(gen["bus"].to_numpy())
+        g_vm = gen["vm_pu"].to_numpy(np.float64)
+        # init_vm_pu="auto" (_init_runpp_options): the mean over the ext_grid and EVERY gen row, in service or not
+        kw["vm_init_pu"] = float(np.mean(np.r_[kw["ext_grid_vm_pu"], g_vm]))
+        if not g_on.any() and kw["vm_init_pu"] != kw["ext_grid_vm_pu"]:
+            # no gen bus, but the out-of-service rows still move the start of every bus: the solvers' start-only form
+            if fused_alias is not None:
+                raise NotImplementedError("out-of-service net.gen rows (they move the start of runpp's Newton iteration: init_vm_pu='auto') on a "
+                                          "net with fused buses (closed bus-bus switches) are not converted")
+            if zip_cols:
+                raise NotImplementedError("out-of-service net.gen rows (they move the start of runpp's Newton iteration: init_vm_pu='auto') "
+                                          "together with voltage-dependent loads are not converted")
+        if g_on.any():
+            if "slack" in gen and gen["slack"].fillna(False).to_numpy(bool)[g_on].any():
+                raise NotImplementedError("an in-service net.gen row has slack=True (a second reference bus): not converted")
+            if np.any(g_bus[g_on] == kw["ext_grid_bus"]):
+                raise NotImplementedError("an in-service gen sits on the ext_grid bus (the slack bus already holds that voltage): not converted")
+            if np.unique(g_bus[g_on]).shape[0] != int(g_on.sum()):
+                raise NotImplementedError("two in-service gens on one bus (runpp merges them into one voltage-controlled bus and splits Q "
+                                          "between them): not converted")
+            if fused_alias is not None:
+                raise NotImplementedError("gens on a net with fused buses (closed bus-bus switches) are not converted")
+            if zip_cols:
+                raise NotImplementedError("gens together with voltage-dependent loads (const_z_percent / const_i_percent) are not converted")
+            kw.update(gen_bus=g_bus[g_on], gen_p_mw=gen["p_mw"].to_numpy(np.float64)[g_on], gen_vm_pu=g_vm[g_on],
+                      gen_scaling=_col(gen, "scaling", 1.0)[g_on])
     # runpp calculate_voltage_angles="auto": True only if a line touches a bus above 70 kV — and then init="auto" means init_va_degree="dc"
     hv_buses = set(np.nonzero(vn > 70.0)[0].tolist())
     touched = set(rb(line["from_bus"].to_numpy()).tolist()) | set(rb(line["to_bus"].to_numpy()).tolist())
@@ -498,23 +536,29 @@ def read_pandapower_pickle(path: str) -> InertNet:
     return net
 
 
-def load_scenario(data_path: str, pv_scale: float = 1.0, demand_scale: float = 1.0, hv_init: str = None, zip_loads: str = None):
+def load_scenario(data_path: str, pv_scale: float = 1.0, demand_scale: float = 1.0, hv_init: str = None, zip_loads: str = None,
+                  gens: str = None):
     """(NetSpec, Profiles) of a scenario directory: netspec.npz or the reference's model.p (read as data by the restricted
     unpickler above — pandapower is not needed) + the three CSVs.  hv_init ("refuse" | "flat" | "auto", see from_pandapower; default:
     the MAPDN_HV_INIT environment variable, else "refuse") decides what happens to a model.p with a line at a bus above 70 kV — runpp
     starts such a net from a DC power flow's angles, which "auto" records for the solvers (NetSpec.va_init = "dc").  zip_loads
     ("refuse" | "runpp", see from_pandapower; default: the MAPDN_ZIP_LOADS environment variable, else "refuse") decides what happens
-    to a model.p with voltage-dependent loads (const_z_percent / const_i_percent)."""
+    to a model.p with voltage-dependent loads (const_z_percent / const_i_percent), gens ("refuse" | "runpp"; default: the MAPDN_GENS
+    environment variable, else "refuse") what happens to one with in-service net.gen rows."""
     npz = os.path.join(data_path, "netspec.npz")
     if hv_init is None:
         hv_init = os.environ.get("MAPDN_HV_INIT", "refuse")
     if zip_loads is None:
         zip_loads = os.environ.get("MAPDN_ZIP_LOADS", "refuse")
+    if gens is None:
+        gens = os.environ.get("MAPDN_GENS", "refuse")
     if os.path.exists(npz):
         net = load_netspec(npz)
     elif os.path.exists(os.path.join(data_path, "model.p")):
         # (zip_loads is passed only when it is not the default: a from_pandapower stand-in written before it existed keeps working)
         more = {} if zip_loads == "refuse" else dict(zip_loads=zip_loads)
+        if gens != "refuse":
+            more["gens"] = gens
         net = from_pandapower(read_pandapower_pickle(os.path.join(data_path, "model.p")), hv_init=hv_init, **more)
     else:
         raise FileNotFoundError(f"no netspec.npz / model.p in {data_path}")

@@ -110,6 +110,7 @@ class VoltageControlBatch:
         self.max_zone_size = dims.max_zone_size
         self.is_radial = bool(dims.is_radial)                   # False: meshed net, general-topology solver (k_nr_dense)
         self.n_trafo = net.n_branch_pu                          # rows of res_trafo: the per-unit pi branches
+        self.n_gen = dims.n_gen                                 # generators (gen buses): the columns of res_gen; not agents
         rat = [getattr(net, k) for k in ("line_max_i_ka", "line_df", "br_vn_hv_kv", "br_vn_lv_kv", "br_rating_mva")]
         if any(r.size for r in rat):                            # thermal ratings of res_line / res_trafo (none: loading_percent is NaN)
             _lib.check(self._lib.mapdn_set_branch_ratings(self._h, *[_lib._p(r, _lib._pd) for r in rat]), self._h)
@@ -405,6 +406,22 @@ class VoltageControlBatch:
                                                            self._stream()), self._h)
         return mx, wb, no
 
+    _RES_GEN_KEYS = ("p_mw", "q_mvar", "vm_pu", "va_degree")
+
+    def res_gen(self, keys=None):
+        """pandapower's res_gen of the env's committed state (mapdn_get_res_gen, include/mapdn.h): a dict of float64 [B, n_gen] tensors —
+        p_mw (= gen p_mw * scaling), q_mvar (what the generator supplies to hold its bus at vm_pu), vm_pu, va_degree (those of its bus).
+        `keys`: a subset (default all).  A net without generators returns [B, 0] tensors."""
+        keys = self._RES_GEN_KEYS if keys is None else tuple(keys)
+        unknown = set(keys) - set(self._RES_GEN_KEYS)
+        if unknown:
+            raise KeyError(f"res_gen has no column {sorted(unknown)}")
+        out = {k: torch.empty(self.n_envs, self.n_gen, dtype=torch.float64, device=self.device) for k in keys}
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mapdn_get_res_gen(self._h, *[(out[k].data_ptr() if k in out else None) for k in self._RES_GEN_KEYS],
+                                                   self._stream()), self._h)
+        return out
+
     def loads(self):
         lp = torch.empty(self.n_envs, self.n_load, dtype=torch.float64, device=self.device)
         lq = torch.empty_like(lp)
@@ -598,8 +615,9 @@ def _resolve_data(args):
     ps, ds = float(args.get("pv_scale", 1.0)), float(args.get("demand_scale", 1.0))       # :415,426,437
     if os.path.isdir(dp) and (os.path.exists(os.path.join(dp, "netspec.npz")) or os.path.exists(os.path.join(dp, "model.p"))):
         from .data import load_scenario
-        return load_scenario(dp, ps, ds, hv_init=args.get("hv_init"),                     # real scenario directory (hv_init, zip_loads:
-                             zip_loads=args.get("zip_loads"))                              # see load_scenario)
+        more = {} if args.get("gens") is None else dict(gens=args.get("gens"))             # (the env key `gens`; else MAPDN_GENS decides)
+        return load_scenario(dp, ps, ds, hv_init=args.get("hv_init"),                     # real scenario directory (hv_init, zip_loads, gens:
+                             zip_loads=args.get("zip_loads"), **more)                      # see load_scenario)
     name = os.path.basename(os.path.normpath(dp))
     if name not in _SCENARIOS:
         raise FileNotFoundError(f"unknown scenario {name!r}: pass net=/profiles=, a directory with netspec.npz + the three "
@@ -824,6 +842,10 @@ class VoltageControl(MultiAgentEnv):
     def _get_res_trafo_loading(self):
         """res_trafo.loading_percent [n_branch_pu] (pf_res_plot.py:161-163)"""
         return self._b.res_trafo(("loading_percent",))["loading_percent"][0].cpu().numpy()
+
+    def _get_res_gen(self):
+        """res_gen of the net's generators: a dict of float64 [1, n_gen] tensors (VoltageControlBatch.res_gen)"""
+        return self._b.res_gen()
 
     def _get_sgen_active(self):
         return self._res("sgen_p")

@@ -90,6 +90,15 @@ class NetSpec:
     br_vn_hv_kv: np.ndarray = field(default_factory=lambda: np.zeros(0))
     br_vn_lv_kv: np.ndarray = field(default_factory=lambda: np.zeros(0))
     br_rating_mva: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    # generators (in-service rows of pandapower's net.gen; data.from_pandapower(gens="runpp") fills them).  A gen's
+    # bus is a GEN BUS: |V| held at gen_vm_pu, P = gen_p_mw * gen_scaling injected (constant: no profile column), Q free.  Gens are not
+    # agents.  empty = none.  vm_init_pu: |V| every other non-slack bus starts from — runpp's init_vm_pu="auto", the mean of the vm_pu of
+    # the ext_grid and of ALL net.gen rows, in service or not; 0 (or NaN, stored as 0) = the mean over ext_grid_vm_pu and gen_vm_pu (these rows are all there is).
+    gen_bus: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    gen_p_mw: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    gen_vm_pu: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    gen_scaling: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    vm_init_pu: float = 0.0
 
     def __post_init__(self):
         f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
@@ -123,6 +132,26 @@ class NetSpec:
             setattr(self, k, v)
             if v.shape[0] and v.shape != (n,):
                 raise ValueError(f"{k} must be empty or have one entry per row ({n}), got shape {v.shape}")
+        ng = np.shape(self.gen_bus)[0]
+        for k in ("gen_p_mw", "gen_vm_pu", "gen_scaling"):
+            v = f64(getattr(self, k))
+            if k == "gen_scaling" and v.shape[0] == 0:
+                v = np.ones(ng)
+            if v.shape != (ng,):
+                raise ValueError(f"{k} must have one entry per gen ({ng}), got shape {v.shape}")
+            if not np.all(np.isfinite(v)):
+                raise ValueError(f"{k} must be finite for every gen")
+            setattr(self, k, v)
+        if ng and not np.all(self.gen_vm_pu > 0.0):
+            raise ValueError("gen_vm_pu must be > 0 for every gen")
+        self.gen_bus = i32(self.gen_bus)
+        nb_ = np.shape(self.bus_vn_kv)[0]
+        if ng and (self.gen_bus.min() < 0 or self.gen_bus.max() >= nb_):
+            raise ValueError("gen_bus out of range")
+        # (two gens on one bus, a gen on the ext_grid bus, gens with fused buses / ZIP loads: refused by name by the converter and by mapdn_create)
+        self.vm_init_pu = 0.0 if np.isnan(float(self.vm_init_pu)) else float(self.vm_init_pu)
+        if not (np.isfinite(self.vm_init_pu) and self.vm_init_pu >= 0.0):
+            raise ValueError("vm_init_pu must be > 0 (0 or NaN = the mean of ext_grid_vm_pu and gen_vm_pu)")
         if np.shape(self.bus_alias)[0] == 0:
             self.bus_alias = np.arange(np.shape(self.bus_vn_kv)[0])
         for k in ("bus_zone", "line_from_bus", "line_to_bus", "line_parallel", "load_bus",
@@ -160,6 +189,22 @@ class NetSpec:
     def has_zip_loads(self) -> bool:
         """True when some load is voltage-dependent (load_const_z / load_const_i not all zero)"""
         return bool(np.any(self.load_const_z != 0.0) or np.any(self.load_const_i != 0.0))
+
+    @property
+    def n_gen(self) -> int:
+        return int(self.gen_bus.shape[0])
+
+    @property
+    def has_gens(self) -> bool:
+        """True when the net holds a generator (a gen bus)"""
+        return self.n_gen > 0
+
+    @property
+    def start_vm_pu(self) -> float:
+        """|V| the PQ buses start from (runpp init_vm_pu="auto"): vm_init_pu, or the mean over the ext_grid and the gens when that is 0"""
+        if self.vm_init_pu > 0.0:
+            return self.vm_init_pu
+        return float(np.mean(np.r_[self.ext_grid_vm_pu, self.gen_vm_pu])) if self.n_gen else float(self.ext_grid_vm_pu)
 
     @property
     def has_fused_buses(self) -> bool:
