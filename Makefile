@@ -5,7 +5,7 @@ FLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
 LIB   := mapdn_amd/libmapdn_hip.so
 CSRC  := mapdn_amd/csrc
 SRC   := plan.cpp kernels.hip dense.hip sparse.hip policy.hip policy_bwd.hip critic.hip rollout.hip capi.hip
-HDR   := $(CSRC)/plan.hpp $(CSRC)/branch.hpp $(CSRC)/branch.hip $(CSRC)/ppo.hip $(CSRC)/colstats.hpp $(CSRC)/rowtile.hpp $(CSRC)/headtile.hpp $(CSRC)/kernels.hpp $(CSRC)/inject.hpp $(CSRC)/philox.hpp $(CSRC)/nrmath.hpp $(CSRC)/ctlloop.hpp $(CSRC)/droop.hpp $(CSRC)/droop.hip $(CSRC)/opf.hpp $(CSRC)/opf.hip $(CSRC)/baselines_host.hpp $(CSRC)/whatif.hpp $(CSRC)/whatif.hip $(CSRC)/critic_twin.hip $(CSRC)/critic_cf.hip $(CSRC)/critic_attn.hip $(CSRC)/critic_shap.hip $(CSRC)/nr_common.hpp $(CSRC)/gen_mask.hpp $(CSRC)/nr_tree.hpp $(CSRC)/nr_inst_list.hpp include/mapdn.h
+HDR   := $(CSRC)/plan.hpp $(CSRC)/branch.hpp $(CSRC)/branch.hip $(CSRC)/ppo.hip $(CSRC)/colstats.hpp $(CSRC)/rowtile.hpp $(CSRC)/headtile.hpp $(CSRC)/kernels.hpp $(CSRC)/inject.hpp $(CSRC)/philox.hpp $(CSRC)/nrmath.hpp $(CSRC)/ctlloop.hpp $(CSRC)/droop.hpp $(CSRC)/droop.hip $(CSRC)/opf.hpp $(CSRC)/opf.hip $(CSRC)/baselines_host.hpp $(CSRC)/whatif.hpp $(CSRC)/whatif.hip $(CSRC)/grad.hpp $(CSRC)/grad.hip $(CSRC)/critic_twin.hip $(CSRC)/critic_cf.hip $(CSRC)/critic_attn.hip $(CSRC)/critic_shap.hip $(CSRC)/nr_common.hpp $(CSRC)/gen_mask.hpp $(CSRC)/nr_tree.hpp $(CSRC)/nr_inst_list.hpp include/mapdn.h
 OBJ   := $(addprefix build/,$(addsuffix .o,$(basename $(SRC)))) build/nr_inst_0.o build/nr_inst_1.o build/nr_inst_2.o build/nr_inst_3.o
 
 lib: $(LIB)

@@ -790,6 +790,27 @@ int mapdn_opf_probe(mapdn_handle* h, const mapdn_opf_config* cfg, const double* 
 int mapdn_evaluate_actions(mapdn_handle* h, const void* actions, int32_t actions_dtype, int32_t n_candidates,
                            double* reward, double* info, uint8_t* status, int32_t* iterations, double* vm_pu, void* stream);
 
+/* ---- Action gradients: d reward / d action of candidate actions by an adjoint tree solve.
+ * mapdn_evaluate_actions, and beside every row (e, k) of it
+ *   grad       f64 [B, K, ns]: grad[e][k][j] = d reward[e][k] / d actions[e][k][j], every other entry of the candidate and the env's state
+ *              held fixed.  reward = -(voltage_weight mean_b barrier(|V_b|) + q_weight mean_j |q_j scaling_j|), or with line_weight set
+ *              -(voltage_weight mean_b barrier(|V_b|) + line_weight mean_l pl_mw_l) over net.line; q_j = sqrt(s_max_j^2 - p_j^2) a_j.
+ *              The power-flow part is exact at the converged V: J' lambda = (d reward / d(theta, |V|))' with the polar Jacobian's
+ *              block LU on the elimination tree, then one read per sgen.  At a kink the derivative is that of the branch the forward
+ *              evaluation takes (bowl: |v - 1| > 0.05; courant_beltrami: max(0, .); bump: its three ranges); sign(0) = 0 for l1 at
+ *              v == 1 and for |q_j| at q_j == 0.  An sgen on the ext_grid bus gets the direct q term alone.
+ *              Rows of status 2 (the power flow did not converge) and 3 (not evaluated) are NaN.
+ * reward, info, status, iterations and vm_pu are bit for bit what mapdn_evaluate_actions writes for the same candidates and state, and
+ * the call leaves the env's state and its next mapdn_step alone in the same way.  Only enqueues (four launches per candidate); the
+ * workspace (18 doubles per node and env, allocated on the first call) does not grow with K; a row has the same bits whatever B, K,
+ * the env's place in the batch and the other candidates are.
+ * Refused, by name in mapdn_last_error and with nothing launched, on host-only handles too: MAPDN_E_INVALID for meshed nets and
+ * handles on another solver than the tree solver, voltage-dependent (ZIP) loads, generators, fused buses, a NULL actions / grad /
+ * reward / info / status, a bad dtype, n_candidates < 1 or > MAPDN_WHATIF_MAX_CANDIDATES; MAPDN_E_STATE before mapdn_reset and on a
+ * host-only handle.  nr_init = 2 (DC start) is accepted: the gradient depends on the converged V alone. */
+int mapdn_action_gradients(mapdn_handle* h, const void* actions, int32_t actions_dtype, int32_t n_candidates, double* grad,
+                           double* reward, double* info, uint8_t* status, int32_t* iterations, double* vm_pu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,12 +127,13 @@ static const char* opf_resolve(const mapdn_handle* h, const mapdn_opf_config* in
   return nullptr;
 }
 
-// the tables and the workspace of the OPF loop (OpfState), once per handle
-static int opf_prepare(mapdn_handle* h) {
-  if (h->opf_ready) return MAPDN_OK;
+// the topology tables of the tree elimination (OpfState: par, cptr, cidx, sg_node, yt, loss_slack), once per handle; grad_prepare
+// takes them as well
+static int opf_tables(mapdn_handle* h) {
+  if (h->opf_tables_ready) return MAPDN_OK;
   const Plan& P = h->plan;
   OpfState& s = h->opf;
-  const size_t Bp = h->d.Bp, ns = (size_t)P.ns, n = (size_t)P.n;
+  const size_t ns = (size_t)P.ns, n = (size_t)P.n;
   // children of every node in the canonical order of the sweeps: the chain child k - 1 first, then ascending positions
   std::vector<int32_t> cptr(n + 1, 0), cidx;
   {
@@ -165,6 +166,18 @@ static int opf_prepare(mapdn_handle* h) {
       (rc = dupload(h, &s.sg_node, sgn)) || (rc = dupload(h, &s.yt, yt)))
     return rc;
   s.loss_slack = P.yrr[0] * P.vroot * P.vroot;
+  h->opf_tables_ready = true;
+  return MAPDN_OK;
+}
+
+// the tables and the workspace of the OPF loop (OpfState), once per handle
+static int opf_prepare(mapdn_handle* h) {
+  if (h->opf_ready) return MAPDN_OK;
+  int rc;
+  if ((rc = opf_tables(h))) return rc;
+  const Plan& P = h->plan;
+  OpfState& s = h->opf;
+  const size_t Bp = h->d.Bp, ns = (size_t)P.ns, n = (size_t)P.n;
   s.vm_row = h->vm_row;
   int32_t *nr_iters = nullptr; uint8_t* nr_conv = nullptr;
   if ((rc = dalloc(h, &s.fac, n * OPF_FAC * Bp)) || (rc = dalloc(h, &s.mv, n * 2 * Bp)) || (rc = dalloc(h, &s.X, n * ns * 2 * Bp)) ||
@@ -284,6 +297,54 @@ static int whatif_run(mapdn_handle* h, const void* actions, int dtype, int K, do
   for (int k = 0; k < K; ++k) {
     launch_whatif_start(d, s, actions, dtype, k, st);
     nr_launch(h, MODE_SOLVE, nullptr, nullptr, nullptr, st, nullptr, 0, &dd);
+    launch_whatif_score(d, s, k, st);
+  }
+  HIPCHK(h, hipGetLastError());
+  return MAPDN_OK;
+}
+
+// ---- mapdn_action_gradients (grad.hip, grad.hpp): what the adjoint tree solve does not cover, by name
+static const char* grad_refusal(const mapdn_handle* h) {
+  const Plan& P = h->plan;
+  if (!P.radial || h->solver != 0) return "action_gradients: meshed nets and handles on another solver than the tree solver are not supported";
+  if (P.zip) return "action_gradients: voltage-dependent (ZIP) loads are not supported";
+  if (P.n_gen) return "action_gradients: nets with generators (net.gen, gen buses) are not supported (k_action_grad takes every non-slack bus as a PQ bus)";
+  if (P.nbo != P.nb || !P.fused_obus.empty() || !P.alias_pos.empty()) return "action_gradients: fused buses are not supported";
+  return nullptr;
+}
+
+// the tree tables (opf_tables) and the workspace of k_action_grad, once per handle: the factors and lambda of ONE candidate, env-minor.
+// Nothing in it grows with the number of candidates.
+static int grad_prepare(mapdn_handle* h) {
+  if (h->grad_ready) return MAPDN_OK;
+  int rc;
+  if ((rc = opf_tables(h)) || (rc = whatif_prepare(h))) return rc;
+  GradState& g = h->grad;
+  const size_t Bp = h->d.Bp, n = (size_t)h->plan.n;
+  if ((rc = dalloc(h, &g.fac, n * OPF_FAC * Bp)) || (rc = dalloc(h, &g.lam, n * 2 * Bp))) return rc;
+  const OpfState& o = h->opf;
+  g.par = o.par; g.cptr = o.cptr; g.cidx = o.cidx; g.sg_node = o.sg_node; g.yt = o.yt;
+  g.act = h->whatif.act; g.nr_conv = h->whatif.nr_conv; g.a = h->whatif.a;
+  h->grad_ready = true;
+  return MAPDN_OK;
+}
+
+// whatif_run with k_action_grad between the solve and the scoring of every candidate.  Only enqueues; writes what whatif_run writes,
+// the gradient workspace and the caller's grad.
+static int grad_run(mapdn_handle* h, const void* actions, int dtype, int K, double* grad, double* reward, double* info, uint8_t* status,
+                    int32_t* iterations, double* vm_pu, hipStream_t st) {
+  if (const int rc = grad_prepare(h)) return rc;
+  const Dev& d = h->d;
+  WhatifState s = h->whatif;
+  s.K = K; s.reward = reward; s.info = info; s.status_out = status; s.iters_out = iterations; s.vm_out = vm_pu;
+  GradState g = h->grad;
+  g.K = K; g.grad = grad;
+  Dev dd;
+  if (const int rc = ctl_begin(h, s, 0, st, &dd)) return rc;
+  for (int k = 0; k < K; ++k) {
+    launch_whatif_start(d, s, actions, dtype, k, st);
+    nr_launch(h, MODE_SOLVE, nullptr, nullptr, nullptr, st, nullptr, 0, &dd);
+    launch_action_grad(d, g, k, st);
     launch_whatif_score(d, s, k, st);
   }
   HIPCHK(h, hipGetLastError());

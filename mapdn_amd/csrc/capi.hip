@@ -98,10 +98,13 @@ struct mapdn_handle {
   bool droop_ready = false;
   // OPF baseline (mapdn_opf_actions): likewise
   OpfState opf{};
-  bool opf_ready = false;
+  bool opf_ready = false, opf_tables_ready = false;
   // mapdn_evaluate_actions: the frame's workspace, likewise
   WhatifState whatif{};
   bool whatif_ready = false;
+  // mapdn_action_gradients: the workspace of k_action_grad, likewise
+  GradState grad{};
+  bool grad_ready = false;
   // res_line / res_trafo (mapdn_get_branch_results, mapdn_get_loading_summary): the plan's branch records with the ratings of
   // mapdn_set_branch_ratings folded in, and their device copy
   std::vector<BranchRec> branches;
@@ -1323,6 +1326,23 @@ int mapdn_evaluate_actions(mapdn_handle* h, const void* actions, int32_t actions
   if (!h->was_reset) { h->err = "evaluate_actions before reset"; return MAPDN_E_STATE; }
   HIPCHK(h, hipSetDevice(h->device));
   return whatif_run(h, actions, actions_dtype, n_candidates, reward, info, status, iterations, vm_pu, (hipStream_t)stream);
+} MAPDN_CATCH(h)
+
+// mapdn_evaluate_actions with d reward / d action of every candidate beside it (grad.hip; grad_run).  The refusals come first, so that a
+// host-only handle names them too; nothing is launched on a refusal.
+int mapdn_action_gradients(mapdn_handle* h, const void* actions, int32_t actions_dtype, int32_t n_candidates, double* grad, double* reward,
+                           double* info, uint8_t* status, int32_t* iterations, double* vm_pu, void* stream) try {
+  if (!h) return MAPDN_E_INVALID;
+  if (const char* why = grad_refusal(h)) return api_fail(h, MAPDN_E_INVALID, why);
+  if (!actions || !grad || !reward || !info || !status)
+    return api_fail(h, MAPDN_E_INVALID, "action_gradients: null buffer (actions, grad, reward, info and status are required)");
+  if (actions_dtype != MAPDN_F32 && actions_dtype != MAPDN_F64) return api_fail(h, MAPDN_E_INVALID, "action_gradients: bad actions dtype");
+  if (n_candidates < 1 || n_candidates > MAPDN_WHATIF_MAX_CANDIDATES)
+    return api_fail(h, MAPDN_E_INVALID, "action_gradients: n_candidates must lie in 1 ... 1024 (MAPDN_WHATIF_MAX_CANDIDATES)");
+  NEEDDEV(h);
+  if (!h->was_reset) { h->err = "action_gradients before reset"; return MAPDN_E_STATE; }
+  HIPCHK(h, hipSetDevice(h->device));
+  return grad_run(h, actions, actions_dtype, n_candidates, grad, reward, info, status, iterations, vm_pu, (hipStream_t)stream);
 } MAPDN_CATCH(h)
 
 // ---- the PPO half of MAPPO / IPPO's update (csrc/ppo.hip): argument checks here, nothing is launched on a refusal

@@ -579,3 +579,5 @@ void launch_stats(const Dev& d, long long* out, hipStream_t st) { hipLaunchKerne
 #include "opf.hip"
 // ... and the candidate scoring of mapdn_evaluate_actions (whatif.hip), which runs in the same frame
 #include "whatif.hip"
+// ... and the adjoint solve of mapdn_action_gradients (grad.hip), between the solve and the scoring of that frame
+#include "grad.hip"

@@ -220,6 +220,19 @@ struct WhatifState : CtlLoop {       // (vm_out here: [B][K][nbo], or nullptr; a
 void launch_whatif_start(const Dev& d, const WhatifState& s, const void* actions, int dtype, int k, hipStream_t st);
 void launch_whatif_score(const Dev& d, const WhatifState& s, int k, hipStream_t st);
 
+// ---- mapdn_action_gradients (grad.hip, grad.hpp; baselines_host.hpp grad_run): d reward / d action of every candidate, in the what-if
+// frame.  Its own argument block: the tree tables of the OPF baseline, the frame's flags and action rows, its workspace and its output.
+struct GradState {
+  const int32_t *par, *cptr, *cidx, *sg_node;    // OpfState's topology tables (opf_tables)
+  const double* yt;
+  double *fac, *lam;                 // [n][OPF_FAC][Bp], [n][2][Bp] env-minor: the block-LU factors and c -> z -> lambda of one candidate
+  const uint8_t *act, *nr_conv;      // [Bp] the frame's active set and the verdicts of its last solve
+  const double* a;                   // [ns][Bp] the frame's action rows (the candidate k_whatif_start wrote)
+  int32_t K;
+  double* grad;                      // [B][K][ns] env-major
+};
+void launch_action_grad(const Dev& d, const GradState& s, int k, hipStream_t st);
+
 // ---- res_line / res_trafo (branch.hip, branch.hpp; mapdn_get_branch_results, mapdn_get_loading_summary).  Their own small argument
 // blocks: Dev stays what every other launch takes.
 enum { BR_TILE = 16, LS_WAVES = 8 };

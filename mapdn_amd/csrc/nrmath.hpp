@@ -71,4 +71,36 @@ NRMATH_FN double bowl_inside(double v) {
   return fma(-0.01 * 3.9894228040143270, ex, 0.04);       // 1 / sqrt(2 pi scale^2) = 3.98942280401432...
 }
 
+// ---- d barrier / dv of the five voltage barriers (nr_common.hpp barrier(), voltage_barrier/*.py), for the reward's gradient (grad.hpp,
+// DESIGN.md section 22).  At a kink the derivative is that of the branch the forward form takes there, by the forward form's own
+// predicate; sign(0) = 0.
+NRMATH_FN double sign0(double x) { return (x > 0.0) ? 1.0 : ((x < 0.0) ? -1.0 : 0.0); }
+NRMATH_FN double barrier_d_l1(double v) { return sign0(v - 1.0); }
+NRMATH_FN double barrier_d_l2(double v) { return 4.0 * (v - 1.0); }
+NRMATH_FN double barrier_d_courant_beltrami(double v) { return 2.0 * fmax(0.0, v - 1.05) - 2.0 * fmax(0.0, 0.95 - v); }
+// inside the band: -0.01 N'(v) = 0.01 N(v) (v - 1) / scale^2 = N(v) (v - 1), with N(v) = 100 (0.04 - bowl_inside(v))
+NRMATH_FN double barrier_d_bowl(double v) {
+  const double dv = fabs(v - 1.0);
+  return (dv > 0.05) ? 2.0 * sign0(v - 1.0) : (0.04 - bowl_inside(v)) * 100.0 * (v - 1.0);
+}
+// f = exp(-1 / (1 - w^4)):  f' = -4 w^3 f / (1 - w^4)^2, w = v on |v| < 1 and v - 2 on 1 < v < 3
+NRMATH_FN double barrier_d_bump(double v) {
+  double w;
+  if (fabs(v) < 1.0) w = v;
+  else if (v > 1.0 && v < 3.0) w = v - 2.0;
+  else return 0.0;
+  const double t = 1.0 - w * w * w * w;
+  return -4.0 * w * w * w * exp(-1.0 / t) / (t * t);
+}
+// by MAPDN_BARRIER_* (include/mapdn.h: l1 0, l2 1, courant_beltrami 2, bowl 3, bump 4; grad.hip asserts the numbers)
+NRMATH_FN double barrier_deriv(int type, double v) {
+  switch (type) {
+    case 0: return barrier_d_l1(v);
+    case 1: return barrier_d_l2(v);
+    case 2: return barrier_d_courant_beltrami(v);
+    case 3: return barrier_d_bowl(v);
+    default: return barrier_d_bump(v);
+  }
+}
+
 }  // namespace mapdn

@@ -515,6 +515,45 @@ class VoltageControlBatch:
                                                         self._stream()), self._h)
         return (reward, info, st, it, vm) if vm_pu else (reward, info, st, it)
 
+    def action_gradients(self, actions, vm_pu=False):
+        """evaluate_actions with the reward's gradient beside it (mapdn_action_gradients, include/mapdn.h): actions as
+        evaluate_actions takes them.  Returns (grad float64 [B, K, n_sgen] with grad[e, k, j] = d reward[e, k] / d actions[e, k, j],
+        reward, info, status, iterations) and vm_pu when vm_pu=True — everything after grad bit for bit what evaluate_actions returns.
+        The gradient is exact at the converged power flow (one adjoint solve on the elimination tree per row); at a kink of a barrier
+        or of |q| it is that of the branch the reward takes, with sign(0) = 0; rows of status 2 and 3 are NaN.  Radial nets on the tree
+        solver with constant-power loads, no generators and no fused buses; anything else raises NotImplementedError.  The env's state
+        and its next step() are not affected."""
+        a = actions
+        if not torch.is_tensor(a):
+            a = torch.as_tensor(np.asarray(a), device=self.device)
+        if a.device != self.device:
+            a = a.to(self.device)
+        if a.dtype not in (torch.float32, torch.float64):
+            a = a.to(torch.float64)
+        B, dv, f64 = self.n_envs, self.device, torch.float64
+        if a.dim() == 2:
+            a = a.reshape(B, 1, self.n_sgen)
+        if a.dim() != 3 or a.shape[0] != B or a.shape[2] != self.n_sgen or a.shape[1] < 1:
+            raise ValueError(f"action_gradients: actions must be [{B}, K, {self.n_sgen}] or [{B}, {self.n_sgen}], got {tuple(a.shape)}")
+        a = a.contiguous()
+        K = int(a.shape[1])
+        grad = torch.empty(B, K, self.n_sgen, dtype=f64, device=dv)
+        reward = torch.empty(B, K, dtype=f64, device=dv)
+        info = torch.empty(B, K, N_INFO, dtype=f64, device=dv)
+        st = torch.empty(B, K, dtype=torch.uint8, device=dv)
+        it = torch.empty(B, K, dtype=torch.int32, device=dv)
+        vm = torch.empty(B, K, self.n_bus, dtype=f64, device=dv) if vm_pu else None
+        with torch.cuda.device(self.device):
+            try:
+                _lib.check(self._lib.mapdn_action_gradients(self._h, a.data_ptr(), self._code(a.dtype), K, grad.data_ptr(), reward.data_ptr(),
+                                                            info.data_ptr(), st.data_ptr(), it.data_ptr(), vm.data_ptr() if vm_pu else None,
+                                                            self._stream()), self._h)
+            except _lib.MapdnError as err:
+                if "not supported" in str(err):
+                    raise NotImplementedError(str(err)) from None
+                raise
+        return (grad, reward, info, st, it, vm) if vm_pu else (grad, reward, info, st, it)
+
     def difference_rewards(self, actions, default=0.0):
         """Ground-truth difference rewards of a joint action [B, n_agents]: r(a) - r(a with agent i's entry replaced by `default`), by one
         evaluate_actions call on n_agents + 1 candidates (the joint action first).  Returns (reward float64 [B], difference float64
@@ -777,6 +816,14 @@ class VoltageControl(MultiAgentEnv):
         r, info, st, _ = self._b.evaluate_actions(torch.as_tensor(c))
         vals = info[0].cpu().numpy()
         return r[0].cpu().numpy(), [{k: float(v) for k, v in zip(INFO_KEYS, row)} for row in vals], st[0].cpu().numpy()
+
+    def action_gradients(self, candidates):
+        """VoltageControlBatch.action_gradients for this one env, as numpy: candidates [K, n_sgen] -> (gradients ndarray [K, n_sgen],
+        rewards ndarray [K], infos list of K dicts keyed by INFO_KEYS, status ndarray [K])"""
+        c = np.asarray(candidates, dtype=np.float64).reshape(1, -1, self._b.n_sgen)
+        g, r, info, st, _ = self._b.action_gradients(torch.as_tensor(c))
+        vals = info[0].cpu().numpy()
+        return g[0].cpu().numpy(), r[0].cpu().numpy(), [{k: float(v) for k, v in zip(INFO_KEYS, row)} for row in vals], st[0].cpu().numpy()
 
     def _obs_list(self, obs):
         o = obs[0].double().cpu().numpy()
