@@ -799,7 +799,10 @@ int mapdn_evaluate_actions(mapdn_handle* h, const void* actions, int32_t actions
  *              block LU on the elimination tree, then one read per sgen.  At a kink the derivative is that of the branch the forward
  *              evaluation takes (bowl: |v - 1| > 0.05; courant_beltrami: max(0, .); bump: its three ranges); sign(0) = 0 for l1 at
  *              v == 1 and for |q_j| at q_j == 0.  An sgen on the ext_grid bus gets the direct q term alone.
- *              Rows of status 2 (the power flow did not converge) and 3 (not evaluated) are NaN.
+ *              Rows of status 2 (the power flow did not converge) and 3 (not evaluated) are NaN.  So is a row of status 0 in which some
+ *              q_j is not finite — a NaN or infinite action on an sgen of the ext_grid bus, whose injection no power flow reads, or a
+ *              limit that is NaN because p_j exceeds s_max_j: the reward of such a row is not finite, and sign(NaN) = 0 would report a
+ *              stationary point.  Its reward, info, status, iterations and vm_pu are what mapdn_evaluate_actions writes.
  * reward, info, status, iterations and vm_pu are bit for bit what mapdn_evaluate_actions writes for the same candidates and state, and
  * the call leaves the env's state and its next mapdn_step alone in the same way.  Only enqueues (four launches per candidate); the
  * workspace (18 doubles per node and env, allocated on the first call) does not grow with K; a row has the same bits whatever B, K,

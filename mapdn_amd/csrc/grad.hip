@@ -33,6 +33,17 @@ __global__ void __launch_bounds__(GRAD_WG) k_action_grad(Dev d, GradState s, int
     for (int j = 0; j < ns; ++j) out[j] = __builtin_nan("");
     return;
   }
+  // A solved row whose q_j = lim_j a_j is not finite for some j (a NaN or infinite action on an sgen of the slack bus, whose injection
+  // no solve reads; a NaN lim where p exceeds s_max): its reward is not finite, and sign0(NaN) = 0 would report a stationary point.
+  bool q_finite = true;
+  for (int j = 0; j < ns; ++j) {
+    const size_t o = (size_t)j * Bp + e;
+    q_finite = q_finite && isfinite(q_limit(d.cur_pv[o], d.smax[j]) * s.a[o]);
+  }
+  if (!q_finite) {
+    for (int j = 0; j < ns; ++j) out[j] = __builtin_nan("");
+    return;
+  }
   const OpfVec E{d.nrbuf + ((size_t)d.r_vout + VO_E) * Bp + e, VOF * Bp}, F{d.nrbuf + ((size_t)d.r_vout + VO_F) * Bp + e, VOF * Bp},
       VM{d.nrbuf + ((size_t)d.r_vout + VO_VM) * Bp + e, VOF * Bp};
   const OpfVec fac{s.fac + e, Bp}, lam{s.lam + e, Bp};

@@ -520,7 +520,9 @@ class VoltageControlBatch:
         evaluate_actions takes them.  Returns (grad float64 [B, K, n_sgen] with grad[e, k, j] = d reward[e, k] / d actions[e, k, j],
         reward, info, status, iterations) and vm_pu when vm_pu=True — everything after grad bit for bit what evaluate_actions returns.
         The gradient is exact at the converged power flow (one adjoint solve on the elimination tree per row); at a kink of a barrier
-        or of |q| it is that of the branch the reward takes, with sign(0) = 0; rows of status 2 and 3 are NaN.  Radial nets on the tree
+        or of |q| it is that of the branch the reward takes, with sign(0) = 0; rows of status 2 and 3 are NaN, and so is a solved row in
+        which some q_j = lim_j * a_j is not finite (a NaN or infinite action on an sgen of the ext_grid bus, or p_j above s_max_j: the
+        row's reward is not finite either).  Radial nets on the tree
         solver with constant-power loads, no generators and no fused buses; anything else raises NotImplementedError.  The env's state
         and its next step() are not affected."""
         a = actions

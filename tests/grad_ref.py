@@ -6,10 +6,12 @@ written out term by term, its derivative by (theta, |V|) of the non-slack buses 
 oracle.pp_restated.jacobian, and  J' lambda = c  is numpy.linalg.solve.  An action a_j moves the scheduled Q of its bus by
 w_j = lim_j scaling_j / sn_mva, so  g_j = direct_j + w_j lambda_(Q row of the bus)  (0 for a bus that is the slack).
 ext=True carries the same evaluation above float64, as tests/opf_kernel_cases.linearise_ext does: numpy.longdouble assembly, the solve
-by a float64 LU refined with longdouble residuals; it is the yardstick for rounding.
+by a float64 LU refined with longdouble residuals (with exact residuals where those stall above the floor: case141); it is the yardstick
+for rounding.
 
 The scenario is that of tests/whatif_cases.py (reset, one random step, then candidates {0, random, UNSOLVABLE, random, ...}) on the
-nets of tests/opf_kernel_cases.py, tests/element_edge_nets.py and the shipped case33."""
+nets of tests/opf_kernel_cases.py, tests/element_edge_nets.py and the shipped case33; on the nets of tests/grad_edge_nets.py (B up to 130,
+K up to 4) every env starts at a daytime row of its own."""
 import functools
 
 import numpy as np
@@ -18,6 +20,7 @@ import scipy.linalg as sla
 from oracle.env_restated import VoltageControlOracle
 from oracle.pp_restated import build_branches, jacobian, make_ybus
 from tests import element_edge_nets as N
+from tests import grad_edge_nets as EN
 from tests import opf_kernel_cases as OK
 from tests import whatif_cases as W
 
@@ -31,6 +34,8 @@ LINE_ARGS = (("line_weight", 0.7), ("q_weight", None))
 # ---- nets and the scenario ---------------------------------------------------------------------------------------------------------------
 def make(name):
     """(NetSpec, Profiles, base env args)"""
+    if name in EN.NETS:
+        return EN.make(name)
     if name in OPF_NETS:
         return (*OK.make(name), W.CASE_ARGS)
     return W.make(name)
@@ -38,6 +43,8 @@ def make(name):
 
 def candidates(name, B, K=W.K_MAX):
     """tests/whatif_cases.candidates, also for the nets that module does not know (the same construction)"""
+    if name in EN.NETS:
+        return EN.candidates(name, B, K)
     if name not in OPF_NETS:
         return W.candidates(name, B, K)
     ns = make(name)[0].n_sgen
@@ -48,6 +55,8 @@ def candidates(name, B, K=W.K_MAX):
 
 
 def first_action(name, B):
+    if name in EN.NETS:
+        return EN.first_action(name, B)
     if name not in OPF_NETS:
         return W.first_action(name, B)
     ns = make(name)[0].n_sgen
@@ -66,6 +75,8 @@ def reference(name, envs, K, args=()):
     for e, o in zip(envs, os_):
         if name in N.NETS:
             N.first_draw_reset(o)
+        elif name in EN.NETS:
+            N.first_draw_reset(o, start=EN.start_of(name, e))
         else:
             o.reset()
         _, term, info = o.step(a0[e])
@@ -126,6 +137,25 @@ def barrier_derivative(kind, v):
     return out
 
 
+def _exact_residual(A, x, b):
+    """b - A x of longdouble arrays without a rounding but the last (rationals over the non-zeros of A; a longdouble is the sum of two
+    float64 values)"""
+    from fractions import Fraction
+
+    def up(v):
+        hi = float(v)
+        return Fraction(hi) + Fraction(float(v - LD(hi)))
+    xs = [up(v) for v in x]
+    acc = [up(v) for v in b]
+    for i, j in zip(*np.nonzero(A)):
+        acc[i] -= up(A[i, j]) * xs[j]
+    out = np.zeros(len(acc), LD)
+    for i, v in enumerate(acc):
+        hi = float(v)
+        out[i] = LD(hi) + LD(float(v - Fraction(hi)))
+    return out
+
+
 def reward_gradient(net, args, V, a, lim, ext=False):
     """g [ns] = d reward / d a at the converged V (complex128 [n_bus]) for the actions a and limits lim; args: the env's
     voltage_barrier_type, voltage_weight, q_weight, line_weight.  ext: module docstring.  Returns g in float64 (ext: longdouble)."""
@@ -161,12 +191,20 @@ def reward_gradient(net, args, V, a, lim, ext=False):
         last = np.inf
         scale = np.abs(c).max()
         if scale > 0:
-            for _ in range(12):
-                dx = sla.lu_solve(lu, (c - JT @ lam).astype(np.float64)).astype(LD)
+            exact = False
+            for _ in range(24):
+                res = _exact_residual(JT, lam, c) if exact else c - JT @ lam
+                dx = sla.lu_solve(lu, res.astype(np.float64)).astype(LD)
                 lam = lam + dx
                 step = float(np.abs(dx).max() / np.abs(lam).max())
-                if step <= 2.0 ** -62 or step > 0.25 * last:
+                if step <= 2.0 ** -62:
                     break
+                if step > 0.25 * last:
+                    # the correction has stopped shrinking.  Above the floor (case141: cond(J) 2^-64 reaches it) the rounding of the
+                    # longdouble residual is what holds it up: go on with residuals formed exactly
+                    if exact or step <= OK.REFINE_FLOOR:
+                        break
+                    exact = True
                 last = step
             assert step <= OK.REFINE_FLOOR, step
     else:
@@ -224,18 +262,29 @@ E64 = {
     ("crowded", (("voltage_barrier_type", "l1"),)): 1.88e-14, ("crowded", (("voltage_barrier_type", "l2"),)): 2.41e-14,
     ("crowded", (("voltage_barrier_type", "courant_beltrami"),)): 1.70e-16, ("crowded", (("voltage_barrier_type", "bump"),)): 7.51e-14,
     ("crowded", LINE_ARGS): 1.17e-12,
+    # tests/grad_edge_nets.py (B = 130, K = 4; case141 and the line_weight runs B = 65; the reference envs of EN.ref_envs64;
+    # tests/test_action_grad_edges_cpu.py recomputes them)
+    ("pair", ()): 4.51e-14, ("chain40", ()): 1.42e-13, ("star12", ()): 1.19e-14, ("feeders3", ()): 1.25e-14, ("comb10", ()): 2.21e-14,
+    ("ties", ()): 1.24e-14, ("case141", ()): 3.11e-13, ("ties", LINE_ARGS): 9.26e-14, ("feeders3", LINE_ARGS): 9.11e-14,
 }
 
 
-def shape_of(args):
+# the nets of tests/grad_edge_nets.py: B = 130 (case141 and the line_weight runs: 65), K = 4, the reference envs of EN.ref_envs64
+EDGE_B, EDGE_B_LINE = dict(case141=65), 65
+
+
+def shape_of(args, name=None):
+    if name in EN.NETS:
+        return (EDGE_B.get(name, EN.B_MAX) if not args else EDGE_B_LINE, EN.K_MAX)
     return (W.B_MAX, W.K_MAX) if not args else VARIANT_SHAPE
 
 
+@functools.lru_cache(maxsize=None)
 def e64(name, args=()):
-    B, K = shape_of(args)
+    B, K = shape_of(args, name)
     os_, ref, cand = reference(name, B, K, args)
     worst = 0.0
-    for e in OK.ref_envs(B):
+    for e in EN.ref_envs64(B) if name in EN.NETS else OK.ref_envs(B):
         o = os_[e]
         for k in range(K):
             if ref["solved"][e, k]:
