@@ -1,5 +1,5 @@
-"""CPU (-m "not gpu") tests of the droop baseline: the law of mapdn_amd/csrc/droop.hpp compiled for the host against the numpy
-restatement (tests/droop_ref.py) bit for bit, the restated loop against the fixed point a = f(v(a)) that a bisection finds on a
+"""CPU (-m "not gpu") tests of the droop baseline: the law, the damped update, the norm's terms and the reactive_ratio target of
+mapdn_amd/csrc/droop.hpp compiled for the host against the numpy restatement (tests/droop_ref.py) bit for bit, the restated loop against the fixed point a = f(v(a)) that a bisection finds on a
 3-bus feeder, and the config refusals of mapdn_droop_actions on a host-only handle."""
 import ctypes as C
 import os
@@ -13,7 +13,7 @@ from mapdn_amd import _lib
 from mapdn_amd.baselines import DroopConfig
 from mapdn_amd.netspec import NetSpec, make_case
 from oracle.pp_restated import runpp_restated
-from tests.droop_ref import damped, droop_ref, law
+from tests.droop_ref import damped, droop_ref, law, target
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT = (0.95, 1.0, 1.0, 1.05)
@@ -53,7 +53,7 @@ def host_law(tmp_path_factory):
         np.ascontiguousarray(rec, dtype=np.float64).tofile(fi)
         p = subprocess.run([exe, fi, fo], capture_output=True, text=True)
         assert p.returncode == 0, p.stderr
-        return np.fromfile(fo, dtype=np.float64).reshape(-1, 3)
+        return np.fromfile(fo, dtype=np.float64).reshape(-1, 4)
     return run
 
 
@@ -64,12 +64,35 @@ def test_device_header_matches_reference_bit_for_bit(host_law, bp):
     a = rng.uniform(-1.0, 1.0, v.size)
     damping = rng.choice([0.1, 0.25, 1.0], v.size)
     v_last = v + rng.normal(0.0, 1e-3, v.size)
-    rec = np.column_stack([v, np.tile(bp, (v.size, 1)), a, damping, v_last])
+    rec = np.column_stack([v, np.tile(bp, (v.size, 1)), a, damping, v_last, np.ones((v.size, 4))])
     out = host_law(rec)
     f = law(v, *bp)
     assert np.array_equal(out[:, 0].view(np.uint64), f.view(np.uint64))
     assert np.array_equal(out[:, 1].view(np.uint64), damped(a, f, damping).view(np.uint64))
     assert np.array_equal(out[:, 2].view(np.uint64), (0.25 + (v - v_last) * (v - v_last)).view(np.uint64))
+
+
+def test_device_target_matches_reference_bit_for_bit(host_law):
+    """droop_target = f * fmin(1, ratio * smax / lim) against droop_ref.target: ratio 0.3 / 1 / 2, lim from 0 (inf inside the fmin) through
+    denormal and tiny values to smax itself and its neighbours, f = +-1, +-0, slope values and the law's own output"""
+    rng = np.random.default_rng(2)
+    smax0 = np.array([1e-3, 0.37, 1.0, 2.4, 96.0])
+    lim_of = lambda sm: np.concatenate([[0.0, 5e-324, 1e-310, 1e-300, 1e-30, 1e-9, 0.3 * sm, np.nextafter(0.3 * sm, 0.0), np.nextafter(0.3 * sm, 9.0),
+                                         0.5 * sm, np.nextafter(sm, 0.0), sm], sm * np.sqrt(1.0 - rng.uniform(0.0, 1.0, 24) ** 2)])
+    fs = np.concatenate([[1.0, -1.0, 0.0, -0.0, 0.5, -0.5, 1.0 / 3.0, -2.0 / 3.0], law(rng.uniform(0.93, 1.07, 16), *DEADBAND)])
+    rows = [(f, ratio, sm, lim) for ratio in (0.3, 1.0, 2.0) for sm in smax0 for lim in lim_of(sm) for f in fs]
+    q = np.array(rows)
+    rec = np.column_stack([np.ones((q.shape[0], 8)), q])
+    rec[:, 1:5] = DEFAULT
+    out = host_law(rec)
+    want = target(q[:, 0], q[:, 1], q[:, 2], q[:, 3])
+    assert np.array_equal(out[:, 3].view(np.uint64), want.view(np.uint64))
+    assert np.isfinite(want).all() and (np.abs(want) <= np.abs(q[:, 0])).all()
+    with np.errstate(divide="ignore", over="ignore"):
+        binds = q[:, 1] * q[:, 2] / q[:, 3] < 1.0
+    assert binds[q[:, 1] == 0.3].any() and not binds[q[:, 1] >= 1.0].any()      # the min binds under ratio 0.3 alone
+    one = (q[:, 1] >= 1.0)
+    assert np.array_equal(want[one].view(np.uint64), q[one, 0].view(np.uint64))  # ratio >= 1: the factor is exactly 1
 
 
 def three_bus():
