@@ -144,6 +144,21 @@ def gen_residual_inf(net, v, p_load, q_load, p_sgen, q_sgen):
     return float(np.abs(_fx(ybus, v, make_sbus(net, pd_ - gen_p_bus(net), qd), np.r_[pv, pq], pq)).max())
 
 
+def q_bars(net, V, Vref):
+    """per gen bus: bar (i) 4 (m + 2) 2^-52 sn sum_j |V_k| |Y_kj| |V_j| — the forward-error bound of the m-term dot product with a factor 4
+    for the complex products — and the first-order propagation of a voltage difference, sn sum_j |Y_kj| (|V_k| d_j + |V_j| d_k)"""
+    ybus = _cached_ybus(net)[0]
+    bar_i, prop = [], []
+    d = np.abs(V - Vref)
+    for k in net.gen_bus:
+        row = ybus.getrow(int(k))
+        cols, ay = row.indices, np.abs(row.data)
+        m = cols.shape[0]
+        bar_i.append(4.0 * (m + 2) * 2.0 ** -52 * net.sn_mva * np.sum(np.abs(V[k]) * ay * np.abs(V[cols])))
+        prop.append(net.sn_mva * np.sum(ay * (np.abs(V[k]) * d[cols] + np.abs(V[cols]) * d[k])))
+    return np.array(bar_i), np.array(prop)
+
+
 def inputs(net, prof, B, seed):
     """random profile rows, q from U(-0.8, 0.8) x limit (the inputs of tests/test_zip_loads_gpu.py)"""
     rng = np.random.default_rng(seed)

@@ -1,11 +1,8 @@
 """GPU (-m gpu) tests of generators (net.gen: gen buses, NetSpec.gen_*) against tests/gen_nets.py::runpp_gen: solve() on the tree and the
-sparse solver with the flat and the DC start, every compiled GEN geometry of csrc/nr_inst_list.hpp against the automatic one, Q_gen and
+sparse solver with the flat and the DC start (every compiled GEN kernel: tests/test_kernel_matrix_gpu.py), Q_gen and
 the commit of res_bus / res_gen against bars derived from the dot product's error bound, an auto-reset episode with an unsolvable step
 replayed on the oracle env, the three injection paths against each other, evaluate_actions / res_line on such a handle, and the
 refusals."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -17,15 +14,13 @@ from mapdn_amd.env import VoltageControl, VoltageControlBatch
 from oracle.env_restated import INFO_KEYS, VoltageControlOracle
 from oracle.pp_restated import _cached_ybus, bus_demand
 from tests.dc_nets import hv_front
-from tests.gen_nets import RADIAL, flat_profiles, gen_case, gen_oracle, gen_substation, inputs, runpp_gen, tiny_case
+from tests.gen_nets import RADIAL, flat_profiles, gen_case, gen_oracle, gen_substation, inputs, q_bars, runpp_gen, tiny_case
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 V_TOL = 1e-9
-EPS = 2.0 ** -52
 ARGS = dict(episode_limit=240, action_scale=0.8, action_bias=0.0, voltage_barrier_type="bowl", seed=0)
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _REF = {}                                                       # (net name, seed, B, init) -> the oracle's results, computed once
 
 
@@ -120,52 +115,7 @@ def test_gens_with_the_dc_start_match_runpp(name, solver):
     assert check_against_oracle((name + "_hv", 7, B, "dc"), net, ins, out) == 0
 
 
-# ---- 3. every compiled GEN instantiation ----------------------------------------------------------------------------------------------
-def gen_geometries():
-    """(W, L, HL, GL, RES) of every X(...) of NR_INSTS_GEN_<p> in csrc/nr_inst_list.hpp"""
-    src = open(os.path.join(ROOT, "mapdn_amd", "csrc", "nr_inst_list.hpp")).read()
-    out = []
-    for p in sorted(set(re.findall(r"#define\s+NR_INSTS_GEN_(\d+)\(X\)", src))):
-        body = re.search(r"#define\s+NR_INSTS_GEN_" + p + r"\(X\)((?:[^\n]*\\\n)*[^\n]*)", src).group(1)
-        for w, l, hl, gl, res in re.findall(r"X\(\s*(\d+)\s*,\s*(\d+)\s*,\s*(true|false)\s*,\s*(true|false)\s*,\s*(\d+)\s*\)", body):
-            out.append((int(w), int(l), hl == "true", gl == "true", int(res)))
-    assert len(out) >= 8 and len(set(out)) == len(out)
-    return out
-
-
-def pin(W, L, HL, GL, RES):
-    """the tuning that makes mapdn_create settle on this instantiation: residency flags 1 = resident, 2 = not"""
-    t = dict(nr_waves=W, nr_lanes=L, nr_lean=2 if HL else 1, nr_h_lds=1 if HL else 2, nr_g_lds=1 if GL else 2)
-    if RES:
-        t.update(nr_rec_lds=1 if RES in (1, 3) else 2, nr_flat_lds=1 if RES == 1 else 2)
-    return t
-
-
-@pytest.mark.parametrize("name", ["mixed", "c141"])
-@pytest.mark.parametrize("dc", [False, True])
-def test_every_compiled_gen_geometry_gives_the_bits_of_the_automatic_one(name, dc):
-    net, prof = gen_case(name)
-    if dc:
-        net = hv_front(net, 150.0)
-    B = 96
-    ins = inputs(net, prof, B, 13)
-    out0, g0 = solve(net, prof, B, None, ins)
-    assert g0["solver"] == 0 and g0["nr_init"] == (2 if dc else 0) and out0[3].all()
-    ran = 0
-    for geo in gen_geometries():
-        t = pin(*geo)
-        try:
-            out, g = solve(net, prof, B, t, ins)
-        except RuntimeError as ex:                              # the only accepted failure: the layout does not fit the LDS with this net
-            assert "LDS" in str(ex), (t, str(ex))
-            continue
-        k = g["kernel"]                                         # the pinned instantiation is the one that ran
-        assert (k["W"], k["L"], bool(k["HL"]), bool(k["GL"]), k["DC"], k["ZIP"], k["GEN"]) == geo[:4] + (int(dc), 0, 1), (geo, k)
-        assert all(np.array_equal(a, b) for a, b in zip(out, out0)), t
-        ran += 1
-    assert ran >= 4, ran
-
-
+# ---- 3. every compiled GEN instantiation: tests/kernel_matrix.py has a row per kernel, tests/test_kernel_matrix_gpu.py holds each to the oracle
 def test_a_gen_geometry_that_is_not_compiled_is_refused():
     net, prof = gen_case("mixed")
     with pytest.raises(RuntimeError, match="not compiled in"):
@@ -173,21 +123,6 @@ def test_a_gen_geometry_that_is_not_compiled_is_refused():
 
 
 # ---- 4. Q_gen and the commit ----------------------------------------------------------------------------------------------------------
-def q_bars(net, V, Vref):
-    """per gen bus: bar (i) 4 (m + 2) 2^-52 sn sum_j |V_k| |Y_kj| |V_j| — the forward-error bound of the m-term dot product with a factor 4
-    for the complex products — and the first-order propagation of a voltage difference, sn sum_j |Y_kj| (|V_k| d_j + |V_j| d_k)"""
-    ybus = _cached_ybus(net)[0]
-    bar_i, prop = [], []
-    d = np.abs(V - Vref)
-    for k in net.gen_bus:
-        row = ybus.getrow(int(k))
-        cols, ay = row.indices, np.abs(row.data)
-        m = cols.shape[0]
-        bar_i.append(4.0 * (m + 2) * EPS * net.sn_mva * np.sum(np.abs(V[k]) * ay * np.abs(V[cols])))
-        prop.append(net.sn_mva * np.sum(ay * (np.abs(V[k]) * d[cols] + np.abs(V[cols]) * d[k])))
-    return np.array(bar_i), np.array(prop)
-
-
 @pytest.mark.parametrize("name", ["mixed", "all", "c141"])
 @pytest.mark.parametrize("solver", ["tree", "sparse"])
 def test_q_gen_and_the_commit_after_a_step(name, solver):
@@ -196,8 +131,11 @@ def test_q_gen_and_the_commit_after_a_step(name, solver):
     (i) at the kernel's own committed V: res_bus.q = -Im(V conj(Ybus V)) sn and Q_gen = Im(V conj(Ybus V)) sn + QD, i.e.
         res_bus.q + Q_gen = QD, each within 4 (m + 2) 2^-52 sn sum_j |V_k| |Y_kj| |V_j|;
     (ii) against runpp_gen: (i) plus the first-order propagation of the measured voltage difference."""
-    net, prof = gen_case(name)
-    B = 6
+    check_q_gen_and_the_commit(*gen_case(name), solver, name)
+
+
+def check_q_gen_and_the_commit(net, prof, solver, name, B=6):
+    """the body of the test above on any net with generators"""
     env = make_env(net, prof, B, dict(nr_solver=solver))
     try:
         env.reset()
