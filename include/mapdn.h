@@ -222,6 +222,11 @@ typedef struct mapdn_env_config {
                                        2 always its own launch (k_inject_sgen)                        env: MAPDN_FUSE_INJECT=1/0 */
   int32_t overlap_advance;          /* removed, must be 0 (MAPDN_E_INVALID otherwise); the field keeps the layout               */
   int32_t xcd_map;                  /* removed, must be 0 (MAPDN_E_INVALID otherwise); the field keeps the layout               */
+  int32_t grad_meshed;              /* mapdn_action_gradients on handles of the general sparse solver (a meshed net, or a radial one
+                                       with nr_solver = 1): 0 refused by name, as before | 1 answered — the adjoint system is solved
+                                       by the handle's own elimination program on transposed blocks (k_action_grad_sparse, DESIGN.md
+                                       section 24).  On a tree-solver handle 1 changes nothing (same launches, same bits).  Other
+                                       values: MAPDN_E_INVALID.                                        env: MAPDN_GRAD_MESHED */
 } mapdn_env_config;
 
 typedef struct mapdn_dims_t {
@@ -807,8 +812,11 @@ int mapdn_evaluate_actions(mapdn_handle* h, const void* actions, int32_t actions
  * the call leaves the env's state and its next mapdn_step alone in the same way.  Only enqueues (four launches per candidate); the
  * workspace (18 doubles per node and env, allocated on the first call) does not grow with K; a row has the same bits whatever B, K,
  * the env's place in the batch and the other candidates are.
+ * With mapdn_env_config.grad_meshed = 1 a handle of the general sparse solver (a meshed net) answers too: k_action_grad_sparse solves
+ * the same adjoint system with the handle's elimination program on transposed blocks, in LDS, without a workspace.
  * Refused, by name in mapdn_last_error and with nothing launched, on host-only handles too: MAPDN_E_INVALID for meshed nets and
- * handles on another solver than the tree solver, voltage-dependent (ZIP) loads, generators, fused buses, a NULL actions / grad /
+ * handles on another solver than the tree solver (grad_meshed = 1: for handles on the dense solver, and on the sparse solver for a
+ * start other than ext_grid_vm_pu), voltage-dependent (ZIP) loads, generators, fused buses, a NULL actions / grad /
  * reward / info / status, a bad dtype, n_candidates < 1 or > MAPDN_WHATIF_MAX_CANDIDATES; MAPDN_E_STATE before mapdn_reset and on a
  * host-only handle.  nr_init = 2 (DC start) is accepted: the gradient depends on the converged V alone. */
 int mapdn_action_gradients(mapdn_handle* h, const void* actions, int32_t actions_dtype, int32_t n_candidates, double* grad,

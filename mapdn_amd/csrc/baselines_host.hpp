@@ -303,20 +303,49 @@ static int whatif_run(mapdn_handle* h, const void* actions, int dtype, int K, do
   return MAPDN_OK;
 }
 
-// ---- mapdn_action_gradients (grad.hip, grad.hpp): what the adjoint tree solve does not cover, by name
+// ---- mapdn_action_gradients (grad.hip, grad.hpp; grad_sparse.hip): what the adjoint solve does not cover, by name.  grad_meshed = 1
+// (mapdn_env_config) lets a k_nr_sparse handle answer by the elimination program on transposed blocks; 0 keeps the tree solver alone.
+static bool grad_on_sparse(const mapdn_handle* h) { return h->knobs.grad_meshed == 1 && h->solver == 1; }
 static const char* grad_refusal(const mapdn_handle* h) {
   const Plan& P = h->plan;
-  if (!P.radial || h->solver != 0) return "action_gradients: meshed nets and handles on another solver than the tree solver are not supported";
+  if ((!P.radial || h->solver != 0) && !grad_on_sparse(h))
+    return h->knobs.grad_meshed == 1
+               ? "action_gradients: meshed nets and radial ones on the dense solver (nr_solver = dense, k_nr_dense) are not supported (grad_meshed = 1 covers "
+                 "the sparse solver)"
+               : "action_gradients: meshed nets and handles on another solver than the tree solver are not supported";
   if (P.zip) return "action_gradients: voltage-dependent (ZIP) loads are not supported";
   if (P.n_gen) return "action_gradients: nets with generators (net.gen, gen buses) are not supported (k_action_grad takes every non-slack bus as a PQ bus)";
+  if (P.gen_start && grad_on_sparse(h))
+    return "action_gradients: a start other than ext_grid_vm_pu (vm_init_pu: out-of-service net.gen rows) is not supported on the sparse solver";
   if (P.nbo != P.nb || !P.fused_obus.empty() || !P.alias_pos.empty()) return "action_gradients: fused buses are not supported";
   return nullptr;
+}
+
+// k_action_grad_sparse (grad_sparse.hip), once per handle: the node of every sgen and the transposed assembly stream beside Dev::sp_nz
+// (plan.cpp grad_sparse_table).  No workspace: fac and lam stay unallocated, every block of an env lives in LDS.
+static int grad_prepare_sparse(mapdn_handle* h) {
+  int rc;
+  if ((rc = whatif_prepare(h))) return rc;
+  const Plan& P = h->plan;
+  GradState& g = h->grad;
+  GradSparseState& t = h->grad_sparse;
+  std::vector<int32_t> sgn(std::max<size_t>((size_t)P.ns, 1), 0);
+  for (size_t j = 0; j < (size_t)P.ns; ++j) sgn[j] = P.pos_of_obus[P.sgen_bus[j]];
+  std::vector<GsNz> nz;
+  grad_sparse_table(P, h->sprog, nz, t.rows_per_sub, t.max_nnz);
+  if ((rc = dupload(h, &g.sg_node, sgn)) || (rc = dupload(h, &t.nz, nz))) return rc;
+  t.nz_bytes = (uint32_t)(nz.size() * sizeof(GsNz));
+  if (grad_sparse_prepare(h->sp_lanes) != 0) { (void)hipGetLastError(); h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for k_action_grad_sparse"; return MAPDN_E_HIP; }
+  g.act = h->whatif.act; g.nr_conv = h->whatif.nr_conv; g.a = h->whatif.a;
+  h->grad_ready = true;
+  return MAPDN_OK;
 }
 
 // the tree tables (opf_tables) and the workspace of k_action_grad, once per handle: the factors and lambda of ONE candidate, env-minor.
 // Nothing in it grows with the number of candidates.
 static int grad_prepare(mapdn_handle* h) {
   if (h->grad_ready) return MAPDN_OK;
+  if (h->solver == 1) return grad_prepare_sparse(h);
   int rc;
   if ((rc = opf_tables(h)) || (rc = whatif_prepare(h))) return rc;
   GradState& g = h->grad;
@@ -329,7 +358,7 @@ static int grad_prepare(mapdn_handle* h) {
   return MAPDN_OK;
 }
 
-// whatif_run with k_action_grad between the solve and the scoring of every candidate.  Only enqueues; writes what whatif_run writes,
+// whatif_run with k_action_grad (a k_nr_sparse handle: k_action_grad_sparse) between the solve and the scoring of every candidate.  Only enqueues; writes what whatif_run writes,
 // the gradient workspace and the caller's grad.
 static int grad_run(mapdn_handle* h, const void* actions, int dtype, int K, double* grad, double* reward, double* info, uint8_t* status,
                     int32_t* iterations, double* vm_pu, hipStream_t st) {
@@ -344,7 +373,8 @@ static int grad_run(mapdn_handle* h, const void* actions, int dtype, int K, doub
   for (int k = 0; k < K; ++k) {
     launch_whatif_start(d, s, actions, dtype, k, st);
     nr_launch(h, MODE_SOLVE, nullptr, nullptr, nullptr, st, nullptr, 0, &dd);
-    launch_action_grad(d, g, k, st);
+    if (h->solver == 1) launch_action_grad_sparse(d, g, h->grad_sparse, k, st);
+    else launch_action_grad(d, g, k, st);
     launch_whatif_score(d, s, k, st);
   }
   HIPCHK(h, hipGetLastError());

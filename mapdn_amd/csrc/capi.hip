@@ -32,6 +32,7 @@ struct Knobs {
   // tri-state residency / mode switches: 0 auto | 1 on | 2 off (nr_lean: 1 lean | 2 fat)
   int lean, h_lds, g_lds, rec_lds, flat_lds, line_lds, mm_pass, fuse_inject;
   int sp_lanes;
+  int grad_meshed;                               // mapdn_action_gradients on k_nr_sparse handles: 0 refused (as before) | 1 answered
   bool inject_full, debug_geometry;
   double check_dx, check_quad;
 };
@@ -48,6 +49,7 @@ static Knobs resolve_knobs(const mapdn_env_config& c) {
   k.mm_pass = tri(c.nr_mm_pass, "MAPDN_NR_MM_PASS");
   k.fuse_inject = tri(c.fuse_inject, "MAPDN_FUSE_INJECT");
   k.sp_lanes = num(c.sp_lanes, "MAPDN_SP_LANES");
+  k.grad_meshed = num(c.grad_meshed, "MAPDN_GRAD_MESHED");
   k.inject_full = num(c.inject_full, "MAPDN_INJECT_FULL") != 0;
   k.debug_geometry = num(c.debug_geometry, "MAPDN_DEBUG_GEOMETRY") != 0;
   // 1e-7: with quadratic convergence the mismatch after such a step is ~|Y| dx^2 << tol, so a wrong prediction
@@ -105,6 +107,7 @@ struct mapdn_handle {
   // mapdn_action_gradients: the workspace of k_action_grad, likewise
   GradState grad{};
   bool grad_ready = false;
+  GradSparseState grad_sparse{};                 // ... of k_action_grad_sparse (grad_meshed = 1, k_nr_sparse handles): the transposed assembly stream
   // res_line / res_trafo (mapdn_get_branch_results, mapdn_get_loading_summary): the plan's branch records with the ratings of
   // mapdn_set_branch_ratings folded in, and their device copy
   std::vector<BranchRec> branches;
@@ -336,6 +339,8 @@ static int validate(mapdn_handle* h, const mapdn_env_config& c) {
     return api_fail(h, MAPDN_E_INVALID, "fuse_inject = 1 exists on the tree solver only (this handle runs the general sparse / dense solver)");
   if (k.fuse_inject == 1 && (c.auto_reset || k.inject_full))
     return api_fail(h, MAPDN_E_INVALID, "fuse_inject = 1 needs a handle without auto_reset and without inject_full");
+  if (k.grad_meshed != 0 && k.grad_meshed != 1)
+    return api_fail(h, MAPDN_E_INVALID, "grad_meshed (MAPDN_GRAD_MESHED) must be 0 (action_gradients on the tree solver only) or 1 (also on the sparse solver)");
   if (h->solver == 1 && k.sp_lanes != 0 && k.sp_lanes != 16 && k.sp_lanes != 8 && k.sp_lanes != 4 && k.sp_lanes != 2)
     return api_fail(h, MAPDN_E_INVALID, "sp_lanes (MAPDN_SP_LANES) must be 16, 8, 4 or 2 (0 = automatic)");
   return MAPDN_OK;

@@ -581,3 +581,5 @@ void launch_stats(const Dev& d, long long* out, hipStream_t st) { hipLaunchKerne
 #include "whatif.hip"
 // ... and the adjoint solve of mapdn_action_gradients (grad.hip), between the solve and the scoring of that frame
 #include "grad.hip"
+// ... and the same adjoint system on a k_nr_sparse handle, by the elimination program on transposed blocks (grad_sparse.hip)
+#include "grad_sparse.hip"

@@ -233,6 +233,17 @@ struct GradState {
 };
 void launch_action_grad(const Dev& d, const GradState& s, int k, hipStream_t st);
 
+// ---- mapdn_action_gradients on a k_nr_sparse handle (grad_sparse.hip, grad_sparse.hpp; mapdn_env_config.grad_meshed = 1): the same
+// adjoint system solved by the handle's elimination program on transposed blocks.  Its own argument block beside GradState (whose act,
+// nr_conv, a, sg_node, K and grad it reads): the transposed assembly stream, [S][rows_per_sub][max_nnz] like Dev::sp_nz with sizes of
+// its own.  No workspace: the blocks, the right-hand side and lambda of an env live in LDS (nr_sparse_lds_bytes).
+struct GradSparseState {
+  const GsNz* nz; uint32_t nz_bytes;
+  int32_t rows_per_sub, max_nnz;
+};
+int grad_sparse_prepare(int L);      // -2: L is not instantiated
+void launch_action_grad_sparse(const Dev& d, const GradState& s, const GradSparseState& t, int k, hipStream_t st);
+
 // ---- res_line / res_trafo (branch.hip, branch.hpp; mapdn_get_branch_results, mapdn_get_loading_summary).  Their own small argument
 // blocks: Dev stays what every other launch takes.
 enum { BR_TILE = 16, LS_WAVES = 8 };

@@ -643,6 +643,40 @@ void sparse_program(const Plan& P, int S, SparseProg& G) {
   }
 }
 
+void grad_sparse_table(const Plan& P, const SparseProg& G, std::vector<GsNz>& nz, int32_t& rows_per_sub, int32_t& max_nnz) {
+  const int n = P.n, S = G.S;
+  std::map<std::pair<int, int>, int> slot;
+  for (size_t q = 0; q + 2 < G.slots_ij.size(); q += 3) slot[{G.slots_ij[q], G.slots_ij[q + 1]}] = G.slots_ij[q + 2];
+  auto y_at = [&](int i, int j, double* y) {      // Y_ij of the CSR rows by position, 0 where absent
+    y[0] = y[1] = 0.0;
+    for (int q = P.gy_ptr[i]; q < P.gy_ptr[i + 1]; ++q) if (P.gy_col[q] == j) { y[0] = P.gy_val[2 * q]; y[1] = P.gy_val[2 * q + 1]; return true; }
+    return false;
+  };
+  // columns of row i: its CSR entries in their order (the order of the row sum S_i), then the nodes j whose row holds i and i's does not
+  std::vector<std::vector<int>> cols((size_t)n);
+  for (int i = 0; i < n; ++i) for (int q = P.gy_ptr[i]; q < P.gy_ptr[i + 1]; ++q) cols[(size_t)i].push_back(P.gy_col[q]);
+  for (int j = 0; j < n; ++j)
+    for (int q = P.gy_ptr[j]; q < P.gy_ptr[j + 1]; ++q) {
+      const int i = P.gy_col[q];
+      double y[2];
+      if (i < n && i != j && !y_at(i, j, y)) cols[(size_t)i].push_back(j);
+    }
+  rows_per_sub = (n + S - 1) / S;
+  max_nnz = 1;
+  for (int i = 0; i < n; ++i) max_nnz = std::max<int32_t>(max_nnz, (int32_t)cols[(size_t)i].size());
+  nz.assign((size_t)S * rows_per_sub * max_nnz, GsNz{(uint32_t)(n + 1), -1, {0.0, 0.0}, {0.0, 0.0}, 0.0});
+  for (int i = 0; i < n; ++i) {
+    const size_t r = (size_t)(i % S) * rows_per_sub + i / S;
+    for (size_t q = 0; q < cols[(size_t)i].size(); ++q) {
+      const int j = cols[(size_t)i][q];
+      GsNz& z = nz[r * max_nnz + q];
+      z.col = (uint32_t)j;
+      y_at(i, j, z.y);
+      if (j < n && j != i) { z.slot = slot.at({i, j}); y_at(j, i, z.yt); }
+    }
+  }
+}
+
 void build_schedule(const Plan& P, int W, Schedule& S, int min_cslots, int Sw, int min_rows) {
   const int n = P.n;
   if (Sw < 1 || W % Sw) Sw = 1;

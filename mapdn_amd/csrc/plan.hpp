@@ -212,6 +212,15 @@ struct SparseProg {
 void sparse_symbolic(const Plan& P, SparseProg& out);
 void sparse_program(const Plan& P, int S, SparseProg& out);
 
+// The transposed assembly stream of k_action_grad_sparse (grad_sparse.hip): row i holds one entry per structural non-zero (i, j) of
+// the SYMMETRISED pattern (the one the program's slots cover): the column, the slot of block (i, j), Y_ij and Y_ji — the block
+// (J')_ij = (J_ji)' is formed from Y_ji, and Ybus need not be symmetric (a phase-shifting transformer).  An entry the CSR row of i does
+// not have (Y_ij structurally absent, Y_ji present) carries Y_ij = 0.  Packed like SparseProg::nz for G.S sub-lanes: [S][rows_per_sub]
+// [max_nnz], row i at sub-lane i % S, rows padded to max_nnz with (column n + 1, slot -1, Y = 0) entries; max_nnz is the table's own.
+struct GsNz { uint32_t col; int32_t slot; double y[2]; double yt[2]; double pad; };   // column position (n = slack), block slot (-1: none), Y_ij, Y_ji
+static_assert(sizeof(GsNz) == 48, "transposed assembly record");
+void grad_sparse_table(const Plan& P, const SparseProg& G, std::vector<GsNz>& nz, int32_t& rows_per_sub, int32_t& max_nnz);
+
 // returns MAPDN_OK or an error code, filling `err`
 int build_plan(const mapdn_netspec& net, const mapdn_env_config& cfg, Plan& out, std::string& err);
 

@@ -523,7 +523,9 @@ class VoltageControlBatch:
         or of |q| it is that of the branch the reward takes, with sign(0) = 0; rows of status 2 and 3 are NaN, and so is a solved row in
         which some q_j = lim_j * a_j is not finite (a NaN or infinite action on an sgen of the ext_grid bus, or p_j above s_max_j: the
         row's reward is not finite either).  Radial nets on the tree
-        solver with constant-power loads, no generators and no fused buses; anything else raises NotImplementedError.  The env's state
+        solver with constant-power loads, no generators and no fused buses, and with tuning=dict(grad_meshed=1) meshed nets (handles of
+        the sparse solver: the same adjoint system by the elimination program on transposed blocks); anything
+        else raises NotImplementedError.  The env's state
         and its next step() are not affected."""
         a = actions
         if not torch.is_tensor(a):
