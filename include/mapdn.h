@@ -727,10 +727,15 @@ typedef struct mapdn_opf_config {
   double step_tol;                  /* stop when |d|inf < step_tol (and feasible): 1e-6; > 0                                        */
   int32_t max_iter;                 /* power flows per env at most: 50; 1 ... 1000                                                  */
   int32_t max_backtrack;            /* halvings of the step in a row when the trial point's power flow fails: 8; 1 ... 60          */
+  int32_t meshed;                   /* 0: handles of the tree solver only.  1: handles of the sparse solver (k_nr_sparse: a meshed
+                                       net, or a radial one with nr_solver = sparse) answer too: the sensitivities by the handle's
+                                       elimination program, two columns a run; on a tree-solver handle 1
+                                       changes nothing.  Other values: MAPDN_E_INVALID                                            */
 } mapdn_opf_config;
 
 /* a = 0, then for i = 1 ... max_iter: power flow at a; S = d|V|/da, g = dloss/da and the Gauss-Newton Hessian H from the converged V
- * (exact sensitivities: the Jacobian's block LU on the tree); d = argmin g'd + d'Hd/2 s.t. -1 - a <= d <= 1 - a, v_lower <= |V| + S d
+ * (exact sensitivities: the Jacobian's block LU on the tree; with meshed = 1 on a sparse-solver handle, the handle's elimination
+ * program); d = argmin g'd + d'Hd/2 s.t. -1 - a <= d <= 1 - a, v_lower <= |V| + S d
  * <= v_upper; stop when |d|inf < step_tol and the violation is <= v_tol, else a <- clip(a + d).  A trial point whose power flow fails
  * is retried at a + d/2, a + d/4, ...
  *   actions    f64 [B, ns]: a of the last solved power flow (step() takes it unclipped)
@@ -743,18 +748,20 @@ typedef struct mapdn_opf_config {
  *              3 not solved (terminated / frozen / waiting for its auto-reset restart; a = 0)
  * Device pointers on `stream`.  Not a step-path call (it polls the count of envs still iterating; the workspace is allocated on the
  * first call).  The obs, state, results, returns, counters and the next mapdn_step are what they would have been without the call.
- * MAPDN_E_INVALID, on host-only handles too, for a config outside the ranges above and for what the tree sweeps do not cover:
- * meshed nets and handles on another solver than the tree solver, voltage-dependent (ZIP) loads, fused buses, more than 64 sgens. */
+ * MAPDN_E_INVALID, on host-only handles too, for a config outside the ranges above and for what the linearisation does not cover:
+ * meshed nets and handles on another solver than the tree solver (with meshed = 1: handles of the dense solver only),
+ * voltage-dependent (ZIP) loads, generators, a start other than ext_grid_vm_pu, fused buses, more than 64 sgens. */
 int mapdn_opf_actions(mapdn_handle* h, const mapdn_opf_config* cfg, double* actions, double* vm_pu, double* loss_mw, double* violation,
                       int32_t* iterations, uint8_t* status, void* stream);
 
 /* Diagnostic entry for the kernel tests of the OPF baseline (tests/test_opf_kernels_gpu.py): ONE linearisation and ONE QP at the caller's
  * set-points, by the launches of mapdn_opf_actions' first iteration and nothing else — the start launch, which here begins from `a`
  * (clipped to [-1, 1]) instead of 0 and writes the Sbus of that a; one power flow in MODE_SOLVE with the OPF's own active set;
- * k_opf_linearise; k_opf_qp from zero multipliers — and then the workspace as those launches left it.  Device pointers on `stream`:
+ * k_opf_linearise (a sparse-solver handle with meshed = 1: k_opf_sens_sparse and k_opf_reduce_sparse); k_opf_qp from zero multipliers —
+ * and then the workspace as those launches left it.  Device pointers on `stream`:
  *   a          f64 [B, ns] in: the set-points;  ns: the row length of a, must be the handle's number of sgens
  * and, each may be NULL, env-major, by NODE k = 0 .. n - 1 (the elimination position; bus_of_pos of mapdn_get_flat_factors maps it to its
- * bus, n = n_bus - 1, the slack is no node):
+ * bus on a radial plan, a meshed plan takes the non-slack buses in ascending order; n = n_bus - 1, the slack is no node):
  *   v_re, v_im, vm f64 [B, n]: the converged V and the |V| the kernels read;   S f64 [B, n, ns] = d|V_k| / da_j;   g f64 [B, ns] = dloss / da (p.u.);   H f64 [B, ns, ns]
  *   loss_mw    f64 [B] (MW) and violation f64 [B] (p.u., against the config's bounds) at that V
  *   d          f64 [B, ns] the QP's step;   y f64 [B, ns + n] its multipliers: the box rows, then one row per node (> 0: upper bound)

@@ -124,7 +124,7 @@ def make_droop_config(cfg=None) -> CDroopConfig:
 class COPFConfig(C.Structure):
     """mapdn_opf_config: a field left 0 takes its default; v_lower / v_upper the env's (include/mapdn.h)"""
     _fields_ = [("v_lower", C.c_double), ("v_upper", C.c_double), ("v_tol", C.c_double), ("step_tol", C.c_double),
-                ("max_iter", C.c_int32), ("max_backtrack", C.c_int32)]
+                ("max_iter", C.c_int32), ("max_backtrack", C.c_int32), ("meshed", C.c_int32)]
 
 
 OPF_STATUS = ("converged", "max_iter", "pf_failed", "not_solved")      # mapdn_opf_actions status codes 0 .. 3

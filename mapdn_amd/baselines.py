@@ -5,7 +5,7 @@ the batched env:
 
 ``DroopConfig``     the droop script's parameters (breakpoints va < vb <= vc < vd, damping, max_iter, v_tol, reactive_ratio)
 ``DroopControl``    the droop controller: per env step, VoltageControlBatch.droop_actions (the fixed-point loop runs on the GPU)
-``OPFConfig``       the OPF's parameters (voltage bounds, v_tol, step_tol, max_iter, max_backtrack; None / 0 = the default)
+``OPFConfig``       the OPF's parameters (voltage bounds, v_tol, step_tol, max_iter, max_backtrack, meshed; None / 0 = the default)
 ``OPFControl``      the OPF baseline: per env step, VoltageControlBatch.opf_actions (a reduced-space SQP on the GPU)
 ``NoControl``       a = 0 (the script's "pf" run)
 ``BaselineTester``  PGTester's `run` / `batch_run` with a baseline in place of the policy: the same record and `mean_test_*`
@@ -62,6 +62,7 @@ class OPFConfig:
     step_tol: float = 1e-6
     max_iter: int = 50
     max_backtrack: int = 8
+    meshed: int = 0          # 1: handles of the sparse solver (meshed nets, nr_solver = "sparse") answer too
 
     def as_dict(self):
         return asdict(self)

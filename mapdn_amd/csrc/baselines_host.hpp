@@ -103,7 +103,9 @@ static int droop_run(mapdn_handle* h, const mapdn_droop_config& c, double* actio
   return ctl_drive(h, s, DROOP_POLL, actions, iterations, status, st, [&](const Dev&, int iter) { launch_droop_update(d, s, iter, st); });
 }
 
-// ---- OPF baseline (opf.hip, opf.hpp): the defaults for the fields left 0, the config's ranges and what the tree sweeps do not cover
+// ---- OPF baseline (opf.hip, opf.hpp; opf_sparse.hip): the defaults for the fields left 0, the config's ranges and what the
+// linearisation does not cover.  meshed = 1 lets a k_nr_sparse handle answer (the elimination program in place of the tree sweeps);
+// 0 keeps the tree solver alone.
 static const char* opf_resolve(const mapdn_handle* h, const mapdn_opf_config* in, mapdn_opf_config& c) {
   if (in) c = *in; else std::memset(&c, 0, sizeof(c));
   if (c.v_lower == 0.0) c.v_lower = h->cfg.v_lower;
@@ -117,8 +119,13 @@ static const char* opf_resolve(const mapdn_handle* h, const mapdn_opf_config* in
   if (!(c.step_tol > 0.0)) return "opf: step_tol must be > 0";
   if (c.max_iter < 1 || c.max_iter > OPF_MAX_ITER_CAP) return "opf: max_iter must lie in 1 ... 1000";
   if (c.max_backtrack < 1 || c.max_backtrack > 60) return "opf: max_backtrack must lie in 1 ... 60";
+  if (c.meshed != 0 && c.meshed != 1) return "opf: meshed must be 0 or 1";
   const Plan& P = h->plan;
-  if (!P.radial || h->solver != 0) return "opf: meshed nets and handles on another solver than the tree solver are not supported";
+  if ((!P.radial || h->solver != 0) && !(c.meshed == 1 && h->solver == 1))
+    return c.meshed == 1
+               ? "opf: meshed nets and radial ones on the dense solver (nr_solver = dense, k_nr_dense) are not supported (meshed = 1 covers the sparse "
+                 "solver)"
+               : "opf: meshed nets and handles on another solver than the tree solver are not supported";
   if (P.zip) return "opf: voltage-dependent (ZIP) loads are not supported";
   if (P.n_gen) return "opf_actions: nets with generators (net.gen, gen buses) are not supported (k_opf_linearise takes every non-slack bus as a PQ bus)";
   if (P.gen_start) return "opf_actions: a start other than ext_grid_vm_pu (vm_init_pu: out-of-service net.gen rows) is not supported (the loop's solves start at the ext_grid set-point)";
@@ -170,17 +177,38 @@ static int opf_tables(mapdn_handle* h) {
   return MAPDN_OK;
 }
 
-// the tables and the workspace of the OPF loop (OpfState), once per handle
+// the tables of the sparse path (opf_sparse.hip), once per handle: the node of every sgen, the rows of M (plan.cpp opf_sparse_table),
+// the slack's own term of the loss
+static int opf_tables_sparse(mapdn_handle* h) {
+  const Plan& P = h->plan;
+  OpfState& s = h->opf;
+  OsM& m = h->opf_m;
+  std::vector<int32_t> sgn(std::max<size_t>((size_t)P.ns, 1), 0), ptr, col;
+  for (size_t j = 0; j < (size_t)P.ns; ++j) sgn[j] = P.pos_of_obus[P.sgen_bus[j]];
+  std::vector<double> val, msv;
+  opf_sparse_table(P, ptr, col, val, msv);
+  if (col.empty()) { col.push_back(0); val.assign(2, 0.0); }
+  int rc;
+  if ((rc = dupload(h, &s.sg_node, sgn)) || (rc = dupload(h, &m.ptr, ptr)) || (rc = dupload(h, &m.col, col)) || (rc = dupload(h, &m.val, val)) ||
+      (rc = dupload(h, &m.msv, msv)))
+    return rc;
+  s.loss_slack = P.yrr[0] * P.vroot * P.vroot;
+  if (opf_sparse_prepare(h->sp_lanes) != 0) { (void)hipGetLastError(); h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for k_opf_sens_sparse"; return MAPDN_E_HIP; }
+  return MAPDN_OK;
+}
+
+// the tables and the workspace of the OPF loop (OpfState), once per handle; a k_nr_sparse handle has no factors in global memory
 static int opf_prepare(mapdn_handle* h) {
   if (h->opf_ready) return MAPDN_OK;
   int rc;
-  if ((rc = opf_tables(h))) return rc;
+  const bool sparse = h->solver == 1;
+  if ((rc = sparse ? opf_tables_sparse(h) : opf_tables(h))) return rc;
   const Plan& P = h->plan;
   OpfState& s = h->opf;
   const size_t Bp = h->d.Bp, ns = (size_t)P.ns, n = (size_t)P.n;
   s.vm_row = h->vm_row;
   int32_t *nr_iters = nullptr; uint8_t* nr_conv = nullptr;
-  if ((rc = dalloc(h, &s.fac, n * OPF_FAC * Bp)) || (rc = dalloc(h, &s.mv, n * 2 * Bp)) || (rc = dalloc(h, &s.X, n * ns * 2 * Bp)) ||
+  if ((rc = sparse ? MAPDN_OK : dalloc(h, &s.fac, n * OPF_FAC * Bp)) || (rc = dalloc(h, &s.mv, n * 2 * Bp)) || (rc = dalloc(h, &s.X, n * ns * 2 * Bp)) ||
       (rc = dalloc(h, &s.W, n * ns * 2 * Bp)) || (rc = dalloc(h, &s.S, n * ns * Bp)) || (rc = dalloc(h, &s.H, ns * ns * Bp)) ||
       (rc = dalloc(h, &s.g, ns * Bp)) || (rc = dalloc(h, &s.qd, ns * Bp)) || (rc = dalloc(h, &s.qy, (ns + n) * Bp)) ||
       (rc = dalloc(h, &s.qw, opf_qp_work((int)ns, (int)n) * Bp)) || (rc = dalloc(h, &s.a, ns * Bp)) || (rc = dalloc(h, &s.a_sol, ns * Bp)) ||
@@ -203,7 +231,13 @@ static OpfState opf_state(const mapdn_handle* h, const mapdn_opf_config& c, doub
   return s;
 }
 
-// The SQP loop: after every solve k_opf_linearise and k_opf_qp on the solver's Dev (the OPF's own active set), then k_opf_update.
+// The linearisation launch of the handle's solver: k_opf_linearise on the tree, k_opf_sens_sparse and k_opf_reduce_sparse on k_nr_sparse.
+static void opf_linearise(const mapdn_handle* h, const Dev& dd, const OpfState& s, hipStream_t st) {
+  if (h->solver == 1) launch_opf_linearise_sparse(dd, s, h->opf_m, st);
+  else launch_opf_linearise(dd, s, st);
+}
+
+// The SQP loop: after every solve the linearisation and k_opf_qp on the solver's Dev (the OPF's own active set), then k_opf_update.
 static int opf_run(mapdn_handle* h, const mapdn_opf_config& c, double* actions, double* vm_pu, double* loss_mw, double* violation,
                    int32_t* iterations, uint8_t* status, hipStream_t st) {
   constexpr int OPF_POLL = 2;
@@ -211,7 +245,7 @@ static int opf_run(mapdn_handle* h, const mapdn_opf_config& c, double* actions, 
   const Dev& d = h->d;
   const OpfState s = opf_state(h, c, vm_pu, nullptr);
   const int rc = ctl_drive(h, s, OPF_POLL, actions, iterations, status, st, [&](const Dev& dd, int iter) {
-    if (iter > 0) { launch_opf_linearise(dd, s, st); launch_opf_qp(dd, s, st); }
+    if (iter > 0) { opf_linearise(h, dd, s, st); launch_opf_qp(dd, s, st); }
     launch_opf_update(d, s, iter, st);
   });
   if (rc) return rc;
@@ -248,7 +282,7 @@ static int opf_probe(mapdn_handle* h, const mapdn_opf_config& c, const double* a
   if (const int rc = ctl_begin(h, s, 0, st, &dd)) return rc;
   launch_opf_update(dv, s, 0, st);
   nr_launch(h, MODE_SOLVE, nullptr, nullptr, nullptr, st, nullptr, 0, &dd);
-  launch_opf_linearise(dd, s, st);
+  opf_linearise(h, dd, s, st);
   launch_opf_qp(dd, s, st);
   if (v_re) transpose_out(h, dv.nrbuf, 1.0, erow, v_re, n, st);
   if (v_im) transpose_out(h, dv.nrbuf, 1.0, erow + n, v_im, n, st);

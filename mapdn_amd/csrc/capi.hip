@@ -101,6 +101,7 @@ struct mapdn_handle {
   // OPF baseline (mapdn_opf_actions): likewise
   OpfState opf{};
   bool opf_ready = false, opf_tables_ready = false;
+  OsM opf_m{};                                   // ... of k_opf_reduce_sparse (meshed = 1, k_nr_sparse handles): the rows of M
   // mapdn_evaluate_actions: the frame's workspace, likewise
   WhatifState whatif{};
   bool whatif_ready = false;

@@ -13,6 +13,7 @@
 #include "nr_common.hpp"
 #include "grad.hpp"
 #include "grad_sparse.hpp"
+#include "sparse_prog.hpp"
 
 namespace mapdn {
 
@@ -22,7 +23,6 @@ namespace mapdn {
 // whatever its own slots hold and differs in the read-out alone.  A stage that reads what other lanes of the wave wrote to LDS waits
 // for those writes (gs_handoff: a wait, no barrier — there is one wavefront).  Every sum of an env runs in one lane in an order the
 // net fixes (the assembly row, the program, the lines of net.line walked by sub-lane 0), whatever B, K and the env's place are.
-__device__ __forceinline__ void gs_handoff() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
 
 template <int L>
 __global__ void __launch_bounds__(64)
@@ -133,40 +133,9 @@ k_action_grad_sparse(Dev d, GradState g, GradSparseState t, int k) {
     rh[0] = d2{lam[(size_t)p * 2], 0.0}; rh[1] = d2{lam[(size_t)p * 2 + 1], 0.0};
   }
   gs_handoff();
-  // ---- 4. the program (plan.cpp::sparse_program), all phases: sub-lane s executes operation s of every phase for its L envs.  The
-  //      interpreter of k_nr_sparse without its per-env `done` mask (a later refactor may share the loop).
-  {
-    constexpr int PF = 8;                        // operation records run PF phases ahead (constant table in L2)
-    u32x4 oq[PF];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) oq[u] = __builtin_amdgcn_raw_buffer_load_b128(rsO, voO, __builtin_amdgcn_readfirstlane((unsigned)min(u, NPH - 1) * S * 16u), 0);
-    for (int p0 = 0; p0 < NPH; p0 += PF) {
-#pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        const int p = p0 + u;
-        if (p < NPH) {                           // (uniform)
-        const u32x4 op = oq[u];
-        oq[u] = __builtin_amdgcn_raw_buffer_load_b128(rsO, voO, __builtin_amdgcn_readfirstlane((unsigned)min(p + PF, NPH - 1) * S * 16u), 0);
-        const unsigned type = op.x & 255u;
-        const unsigned hint = __builtin_amdgcn_readfirstlane(op.x);     // bits 8 / 9: the phase holds an INV / an UPD (wave-uniform)
-        const d2* A = blk(op.z); const d2* B = blk(op.w); d2* C = blk(op.y);
-        const d2 a0 = A[0], a1 = A[1], b0 = B[0], b1 = B[1];
-        d2 c0 = d2{0.0, 0.0}, c1 = d2{0.0, 0.0};
-        if (hint & 512u) { c0 = C[0]; c1 = C[1]; }
-        const double p00 = a0.x * b0.x + a0.y * b1.x, p01 = a0.x * b0.y + a0.y * b1.y;
-        const double p10 = a1.x * b0.x + a1.y * b1.x, p11 = a1.x * b0.y + a1.y * b1.y;
-        d2 n0, n1;
-        if (type == 2u) { n0 = d2{p00, p01}; n1 = d2{p10, p11}; }
-        else { n0 = d2{c0.x - p00, c0.y - p01}; n1 = d2{c1.x - p10, c1.y - p11}; }
-        if (hint & 256u) {
-          const double idet = rcp_nr(a0.x * a1.y - a0.y * a1.x);
-          if (type == 1u) { n0 = d2{a1.y * idet, -a0.y * idet}; n1 = d2{-a1.x * idet, a0.x * idet}; }
-        }
-        if (type != 0u) { C[0] = n0; C[1] = n1; }
-        }
-      }
-    }
-  }
+  // ---- 4. the program (plan.cpp::sparse_program), all phases: sub-lane s executes operation s of every phase for its L envs
+  //      (sparse_prog.hpp: the interpreter of k_nr_sparse without its per-env `done` mask)
+  sp_run_program<L>(sB, rsO, voO, NPH);
   gs_handoff();
   // ---- 5. the read-out: lambda of the slots n + i where grad_entry indexes it, then entry j = dr/da_j (an sgen on the slack: node == n,
   //      the direct term alone)

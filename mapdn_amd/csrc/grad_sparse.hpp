@@ -20,6 +20,9 @@ OPF_FN void gs_a(double ea, double fa, double yr, double yi, double eb, double f
   const double tr = yr * eb - yi * fb, ti = yr * fb + yi * eb;
   *ar = ea * tr + fa * ti; *ai = fa * tr - ea * ti;
 }
+// slot (i, j) of J itself, from A_ij, and slot (i, i) from S_i and A_ii: what k_nr_sparse assembles and k_opf_sens_sparse (opf_sparse.hip) as well
+OPF_FN Opf2x2 gs_offdiag(double aij_r, double aij_i) { return {aij_i, aij_r, -aij_r, aij_i}; }
+OPF_FN Opf2x2 gs_diag(double sr, double si, double aii_r, double aii_i) { return {-(si - aii_i), sr + aii_r, sr - aii_r, si + aii_i}; }
 // slot (i, j) of J': (J_ji)' from A_ji
 OPF_FN Opf2x2 gs_offdiag_t(double aji_r, double aji_i) { return {aji_i, -aji_r, aji_r, aji_i}; }
 // slot (i, i) of J': (J_ii)' from S_i and A_ii

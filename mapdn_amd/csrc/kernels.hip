@@ -583,3 +583,5 @@ void launch_stats(const Dev& d, long long* out, hipStream_t st) { hipLaunchKerne
 #include "grad.hip"
 // ... and the same adjoint system on a k_nr_sparse handle, by the elimination program on transposed blocks (grad_sparse.hip)
 #include "grad_sparse.hip"
+// ... and the OPF baseline's linearisation on such a handle, by the same program on the blocks of J itself (opf_sparse.hip)
+#include "opf_sparse.hip"

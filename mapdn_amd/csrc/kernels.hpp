@@ -177,6 +177,7 @@ void launch_stats(const Dev& d, long long* out, hipStream_t st);
 // ---- the traditional baselines: one control-loop frame (ctlloop.hpp: CtlLoop, the fields both loops keep) around the handle's solves
 }  // namespace mapdn
 #include "ctlloop.hpp"
+#include "opf_sparse.hpp"   // OsM: the row table of k_opf_reduce_sparse
 namespace mapdn {
 
 // ---- droop baseline (droop.hip; mapdn_droop_actions, baselines_host.hpp).  Per-env status as in include/mapdn.h.
@@ -207,6 +208,12 @@ struct OpfState : CtlLoop {
 void launch_opf_update(const Dev& d, const OpfState& s, int iter, hipStream_t st);
 void launch_opf_linearise(const Dev& d, const OpfState& s, hipStream_t st);
 void launch_opf_qp(const Dev& d, const OpfState& s, hipStream_t st);
+// ... on a k_nr_sparse handle (opf_sparse.hip, opf_sparse.hpp; mapdn_opf_config.meshed = 1), in place of launch_opf_linearise:
+// k_opf_sens_sparse<sp_lanes> (S and dV by the handle's elimination program, two columns a run; the blocks of an env live in LDS,
+// nr_sparse_lds_bytes) and k_opf_reduce_sparse (M V, loss, violation, lin, W, g, H with M from the row table OsM).  Of OpfState's tables
+// they read sg_node and loss_slack; fac stays unallocated.
+int opf_sparse_prepare(int L);       // -2: L is not instantiated
+void launch_opf_linearise_sparse(const Dev& d, const OpfState& s, const OsM& m, hipStream_t st);
 
 // ---- mapdn_evaluate_actions (whatif.hip, whatif.hpp; baselines_host.hpp whatif_run): K candidate actions per env scored in the frame.
 // Per-(env, candidate) status as in include/mapdn.h: the values of the droop / OPF codes that apply.

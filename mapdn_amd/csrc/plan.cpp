@@ -677,6 +677,27 @@ void grad_sparse_table(const Plan& P, const SparseProg& G, std::vector<GsNz>& nz
   }
 }
 
+void opf_sparse_table(const Plan& P, std::vector<int32_t>& ptr, std::vector<int32_t>& col, std::vector<double>& val, std::vector<double>& msv) {
+  const int n = P.n;
+  std::vector<std::map<int, cplx>> rows((size_t)n);
+  std::vector<cplx> ms((size_t)n, cplx(0, 0));
+  for (int i = 0; i < n; ++i)
+    for (int q = P.gy_ptr[i]; q < P.gy_ptr[i + 1]; ++q) {
+      const int j = P.gy_col[q];
+      const cplx y(P.gy_val[2 * q], P.gy_val[2 * q + 1]);
+      if (j < n) { rows[(size_t)i][j] += 0.5 * y; rows[(size_t)j][i] += 0.5 * std::conj(y); }
+      else ms[(size_t)i] += 0.5 * y * P.vroot;
+    }
+  for (size_t q = 0; q < P.root_children.size(); ++q)
+    ms[(size_t)P.root_children[q]] += 0.5 * std::conj(cplx(P.root_y[2 * q], P.root_y[2 * q + 1])) * P.vroot;
+  ptr.assign(1, 0); col.clear(); val.clear(); msv.assign((size_t)std::max(n, 1) * 2, 0.0);
+  for (int i = 0; i < n; ++i) {
+    for (const auto& kv : rows[(size_t)i]) { col.push_back(kv.first); val.push_back(kv.second.real()); val.push_back(kv.second.imag()); }
+    ptr.push_back((int32_t)col.size());
+    msv[2 * (size_t)i] = ms[(size_t)i].real(); msv[2 * (size_t)i + 1] = ms[(size_t)i].imag();
+  }
+}
+
 void build_schedule(const Plan& P, int W, Schedule& S, int min_cslots, int Sw, int min_rows) {
   const int n = P.n;
   if (Sw < 1 || W % Sw) Sw = 1;

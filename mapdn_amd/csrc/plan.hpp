@@ -221,6 +221,11 @@ struct GsNz { uint32_t col; int32_t slot; double y[2]; double yt[2]; double pad;
 static_assert(sizeof(GsNz) == 48, "transposed assembly record");
 void grad_sparse_table(const Plan& P, const SparseProg& G, std::vector<GsNz>& nz, int32_t& rows_per_sub, int32_t& max_nnz);
 
+// The rows of M = (Ybus + Ybus^H) / 2 over the non-slack nodes for k_opf_reduce_sparse (opf_sparse.hip, opf_sparse.hpp OsM): a CSR by
+// position over the symmetrised pattern, columns ascending (the diagonal among them), (re, im) per entry; the slack's column apart as
+// msv[k] = M_k,slack V_slack (Y_k,slack from the CSR rows, Y_slack,k from root_children / root_y).
+void opf_sparse_table(const Plan& P, std::vector<int32_t>& ptr, std::vector<int32_t>& col, std::vector<double>& val, std::vector<double>& msv);
+
 // returns MAPDN_OK or an error code, filling `err`
 int build_plan(const mapdn_netspec& net, const mapdn_env_config& cfg, Plan& out, std::string& err);
 

@@ -468,7 +468,9 @@ class VoltageControlBatch:
         [B, n_sgen], loss_mw float64 [B], violation float64 [B] p.u., iterations int32 [B] power flows solved, status uint8 [B]:
         0 converged and feasible, 1 max_iter or a QP cap reached, 2 a power flow failed even after backtracking, 3 not solved — done /
         waiting for its restart), and vm_pu float64 [B, n_bus] when vm_pu=True.  Radial nets on the tree solver with constant-power
-        loads, no fused buses and at most 64 sgens; anything else raises.  The env's state and its next step() are not affected."""
+        loads, no generators, no fused buses and at most 64 sgens, and with config meshed=1 also handles of the sparse solver (a meshed
+        net, or tuning=dict(nr_solver="sparse"): the sensitivities by the handle's elimination program); anything
+        else raises.  The env's state and its next step() are not affected."""
         cc = _lib.make_opf_config(config)
         B, dv, f64 = self.n_envs, self.device, torch.float64
         act = torch.empty(B, self.n_sgen, dtype=f64, device=dv)
@@ -580,15 +582,19 @@ class VoltageControlBatch:
         in [-1, 1], by the launches of opf_actions' first iteration.  Returns a dict of tensors by NODE (elimination position; `bus_of_node`
         [n] maps it to its bus): v (complex128 [B, n]), vm [B, n], S [B, n, ns], g [B, ns], H [B, ns, ns], loss_mw [B], violation [B], d [B, ns],
         y [B, ns + n], linearised and qp_capped (bool [B]).  Rows of envs that were not linearised hold d = y = 0 and are unspecified
-        otherwise.  The env's state and its next step() are not affected."""
+        otherwise.  With config meshed=1 also on a handle of the sparse solver (opf_actions); bus_of_node is then the plan's order of
+        that handle as well.  The env's state and its next step() are not affected."""
         cc = _lib.make_opf_config(config)
         B, dv, f64, ns = self.n_envs, self.device, torch.float64, self.n_sgen
         a = torch.as_tensor(a, dtype=f64, device=dv).contiguous()
         assert a.shape == (B, ns)
-        bop = np.zeros(self.n_bus, np.int32)
-        fac = np.zeros((self.n_bus - 1) * 12)
-        _lib.check(self._lib.mapdn_get_flat_factors(self._h, _lib._p(fac, _lib._pd), _lib._p(bop, _lib._pi)), self._h)
         n = self.n_bus - 1
+        if self.is_radial:
+            bop = np.zeros(self.n_bus, np.int32)
+            fac = np.zeros((self.n_bus - 1) * 12)
+            _lib.check(self._lib.mapdn_get_flat_factors(self._h, _lib._p(fac, _lib._pd), _lib._p(bop, _lib._pi)), self._h)
+        else:                                   # a meshed plan takes the non-slack buses in ascending order
+            bop = np.array([b for b in range(self.n_bus) if b != int(self.net.ext_grid_bus)], np.int32)
         new = lambda *shape, dtype=f64: torch.zeros(*shape, dtype=dtype, device=dv)
         out = dict(v_re=new(B, n), v_im=new(B, n), vm=new(B, n), S=new(B, n, ns), g=new(B, ns), H=new(B, ns, ns), loss_mw=new(B), violation=new(B),
                    d=new(B, ns), y=new(B, ns + n), linearised=new(B, dtype=torch.uint8), qp_capped=new(B, dtype=torch.uint8))

@@ -9,6 +9,7 @@ OPFControl and with NoControl over N episodes of --steps steps and prints
   wall time, env-steps/s and power flows/s (the OPF's solves plus the step's own).
 
     python tools/opf_baseline.py --cases case33 case141 case322 --episodes 4096 --steps 8 --json out.json
+    python tools/opf_baseline.py --cases case33 --ties 5          # the feeder with five tie lines closed (OPFConfig(meshed=1))
 """
 from __future__ import annotations
 
@@ -27,6 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from mapdn_amd.baselines import BaselineTester, NoControl, OPFConfig, OPFControl   # noqa: E402
 from mapdn_amd.env import VoltageControlBatch                                     # noqa: E402
+from mapdn_amd import netspec                                                     # noqa: E402
 from mapdn_amd.netspec import make_case                                           # noqa: E402
 
 ARGS = dict(episode_limit=240, action_scale=0.8, action_bias=0.0, voltage_barrier_type="bowl")
@@ -48,8 +50,13 @@ class TimedOPF(OPFControl):
         return a
 
 
-def run_case(case, episodes, steps, seed, cfg, device, controllers=("opf", "no_control"), loading=False, max_i_ka=None):
+def run_case(case, episodes, steps, seed, cfg, device, controllers=("opf", "no_control"), loading=False, max_i_ka=None, ties=0):
     net, prof = make_case(case)
+    if ties:                                                   # netspec.case33_meshed and its like: both controllers run on the meshed net
+        close = getattr(netspec, f"{case}_meshed", None)
+        if close is None:
+            raise SystemExit(f"--ties: netspec has no {case}_meshed")
+        net = close(net, ties)
     if max_i_ka is not None:                                   # the built-in cases carry no ratings: one for every line
         net = dataclasses.replace(net, line_max_i_ka=np.full(net.n_line, float(max_i_ka)))
     out = {}
@@ -100,12 +107,14 @@ def main():
     ap.add_argument("--loading", action="store_true", help="also print the mean of the largest branch loading_percent per step and the "
                     "share of steps with a branch above 100 %% (BaselineTester(record_loading=True); NaN on a net without ratings)")
     ap.add_argument("--max-i-ka", type=float, default=None, help="with --loading: rate every line at this max_i_ka (the built-in cases carry no ratings)")
+    ap.add_argument("--ties", type=int, default=0, help="close this many tie lines (cases for which netspec has <case>_meshed: case33) and "
+                    "run the OPF with meshed = 1, on the handle's sparse solver")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
-    cfg = OPFConfig(max_iter=a.max_iter)
-    res = dict(config=cfg.as_dict(), episodes=a.episodes, steps=a.steps, seed=a.seed, cases={})
+    cfg = OPFConfig(max_iter=a.max_iter, meshed=1 if a.ties else 0)
+    res = dict(config=cfg.as_dict(), episodes=a.episodes, steps=a.steps, seed=a.seed, ties=a.ties, cases={})
     for case in a.cases:
-        r = res["cases"][case] = run_case(case, a.episodes, a.steps, a.seed, cfg, a.device, a.controllers, a.loading, a.max_i_ka)
+        r = res["cases"][case] = run_case(case, a.episodes, a.steps, a.seed, cfg, a.device, a.controllers, a.loading, a.max_i_ka, a.ties)
         for name, x in r.items():
             line = (f"{case:8s} {name:10s} CR {x['CR']:.4f}  QL {x['QL']:.4f}  PL {x['PL']:.4f}  | {x['wall_s']:.2f} s  "
                     f"{x['env_steps_per_s']:.3e} env-steps/s  {x['power_flows_per_s']:.3e} power flows/s")
