@@ -103,6 +103,32 @@ static int droop_run(mapdn_handle* h, const mapdn_droop_config& c, double* actio
   return ctl_drive(h, s, DROOP_POLL, actions, iterations, status, st, [&](const Dev&, int iter) { launch_droop_update(d, s, iter, st); });
 }
 
+// ---- shared by the OPF baseline and mapdn_action_gradients.
+// The solver gate: the tree solver on a radial net answers; with the entry point's knob at 1 a k_nr_sparse handle answers too; nothing
+// else does.  nullptr, or the refusal under the entry point's prefix.
+static const char* solver_gate(const mapdn_handle* h, const char* prefix, const char* knob, bool knob_on) {
+  if ((h->plan.radial && h->solver == 0) || (knob_on && h->solver == 1)) return nullptr;
+  static thread_local std::string why;
+  why = std::string(prefix) +
+        (knob_on ? ": meshed nets and radial ones on the dense solver (nr_solver = dense, k_nr_dense) are not supported (" + std::string(knob) +
+                       " = 1 covers the sparse solver)"
+                 : std::string(": meshed nets and handles on another solver than the tree solver are not supported"));
+  return why.c_str();
+}
+// the node of every sgen (position; n: the slack)
+static std::vector<int32_t> sgen_nodes(const Plan& P) {
+  std::vector<int32_t> sgn(std::max<size_t>((size_t)P.ns, 1), 0);
+  for (size_t j = 0; j < (size_t)P.ns; ++j) sgn[j] = P.pos_of_obus[P.sgen_bus[j]];
+  return sgn;
+}
+// the result of a *_sparse_prepare(sp_lanes) of sparse_prog.hpp's sp_prepare as a return code
+static int sparse_prepared(mapdn_handle* h, int rc, const char* kernel) {
+  if (rc == 0) return MAPDN_OK;
+  (void)hipGetLastError();
+  h->err = std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for ") + kernel;
+  return MAPDN_E_HIP;
+}
+
 // ---- OPF baseline (opf.hip, opf.hpp; opf_sparse.hip): the defaults for the fields left 0, the config's ranges and what the
 // linearisation does not cover.  meshed = 1 lets a k_nr_sparse handle answer (the elimination program in place of the tree sweeps);
 // 0 keeps the tree solver alone.
@@ -121,11 +147,7 @@ static const char* opf_resolve(const mapdn_handle* h, const mapdn_opf_config* in
   if (c.max_backtrack < 1 || c.max_backtrack > 60) return "opf: max_backtrack must lie in 1 ... 60";
   if (c.meshed != 0 && c.meshed != 1) return "opf: meshed must be 0 or 1";
   const Plan& P = h->plan;
-  if ((!P.radial || h->solver != 0) && !(c.meshed == 1 && h->solver == 1))
-    return c.meshed == 1
-               ? "opf: meshed nets and radial ones on the dense solver (nr_solver = dense, k_nr_dense) are not supported (meshed = 1 covers the sparse "
-                 "solver)"
-               : "opf: meshed nets and handles on another solver than the tree solver are not supported";
+  if (const char* why = solver_gate(h, "opf", "meshed", c.meshed == 1)) return why;
   if (P.zip) return "opf: voltage-dependent (ZIP) loads are not supported";
   if (P.n_gen) return "opf_actions: nets with generators (net.gen, gen buses) are not supported (k_opf_linearise takes every non-slack bus as a PQ bus)";
   if (P.gen_start) return "opf_actions: a start other than ext_grid_vm_pu (vm_init_pu: out-of-service net.gen rows) is not supported (the loop's solves start at the ext_grid set-point)";
@@ -140,7 +162,7 @@ static int opf_tables(mapdn_handle* h) {
   if (h->opf_tables_ready) return MAPDN_OK;
   const Plan& P = h->plan;
   OpfState& s = h->opf;
-  const size_t ns = (size_t)P.ns, n = (size_t)P.n;
+  const size_t n = (size_t)P.n;
   // children of every node in the canonical order of the sweeps: the chain child k - 1 first, then ascending positions
   std::vector<int32_t> cptr(n + 1, 0), cidx;
   {
@@ -165,12 +187,11 @@ static int opf_tables(mapdn_handle* h) {
     const cplx msv = 0.5 * (cplx(c[6], c[7]) + std::conj(ysk[k]) * P.vroot);
     y[OY_MKP] = mkp.real(); y[OY_MKP + 1] = mkp.imag(); y[OY_MSV] = msv.real(); y[OY_MSV + 1] = msv.imag();
   }
-  std::vector<int32_t> sgn(std::max<size_t>(ns, 1), 0), par(std::max<size_t>(n, 1), 0);
-  for (size_t j = 0; j < ns; ++j) sgn[j] = P.pos_of_obus[P.sgen_bus[j]];
+  std::vector<int32_t> par(std::max<size_t>(n, 1), 0);
   for (size_t k = 0; k < n; ++k) par[k] = P.par[k];
   int rc;
   if ((rc = dupload(h, &s.par, par)) || (rc = dupload(h, &s.cptr, cptr)) || (rc = dupload(h, &s.cidx, cidx)) ||
-      (rc = dupload(h, &s.sg_node, sgn)) || (rc = dupload(h, &s.yt, yt)))
+      (rc = dupload(h, &s.sg_node, sgen_nodes(P))) || (rc = dupload(h, &s.yt, yt)))
     return rc;
   s.loss_slack = P.yrr[0] * P.vroot * P.vroot;
   h->opf_tables_ready = true;
@@ -183,18 +204,16 @@ static int opf_tables_sparse(mapdn_handle* h) {
   const Plan& P = h->plan;
   OpfState& s = h->opf;
   OsM& m = h->opf_m;
-  std::vector<int32_t> sgn(std::max<size_t>((size_t)P.ns, 1), 0), ptr, col;
-  for (size_t j = 0; j < (size_t)P.ns; ++j) sgn[j] = P.pos_of_obus[P.sgen_bus[j]];
+  std::vector<int32_t> ptr, col;
   std::vector<double> val, msv;
   opf_sparse_table(P, ptr, col, val, msv);
   if (col.empty()) { col.push_back(0); val.assign(2, 0.0); }
   int rc;
-  if ((rc = dupload(h, &s.sg_node, sgn)) || (rc = dupload(h, &m.ptr, ptr)) || (rc = dupload(h, &m.col, col)) || (rc = dupload(h, &m.val, val)) ||
-      (rc = dupload(h, &m.msv, msv)))
+  if ((rc = dupload(h, &s.sg_node, sgen_nodes(P))) || (rc = dupload(h, &m.ptr, ptr)) || (rc = dupload(h, &m.col, col)) ||
+      (rc = dupload(h, &m.val, val)) || (rc = dupload(h, &m.msv, msv)))
     return rc;
   s.loss_slack = P.yrr[0] * P.vroot * P.vroot;
-  if (opf_sparse_prepare(h->sp_lanes) != 0) { (void)hipGetLastError(); h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for k_opf_sens_sparse"; return MAPDN_E_HIP; }
-  return MAPDN_OK;
+  return sparse_prepared(h, opf_sparse_prepare(h->sp_lanes), "k_opf_sens_sparse");
 }
 
 // the tables and the workspace of the OPF loop (OpfState), once per handle; a k_nr_sparse handle has no factors in global memory
@@ -318,11 +337,12 @@ static int whatif_prepare(mapdn_handle* h) {
 }
 
 // The frame without a stop test, so without a poll: ctl_begin, then per candidate the start launch (the candidate's Sbus rows), the
-// solve on the frame's active set and k_whatif_score.  Only enqueues.  Writes what ctl_drive writes (the PV-bus and several-load-bus
-// entries of the Sbus buffer the next solve reads, all of it when Sbus is stale; the solver's Vout rows) and the caller's outputs.
-static int whatif_run(mapdn_handle* h, const void* actions, int dtype, int K, double* reward, double* info, uint8_t* status,
-                      int32_t* iterations, double* vm_pu, hipStream_t st) {
-  if (const int rc = whatif_prepare(h)) return rc;
+// solve on the frame's active set, between(k) — what the caller reads off the solved candidate — and k_whatif_score.  Only enqueues.
+// Writes what ctl_drive writes (the PV-bus and several-load-bus entries of the Sbus buffer the next solve reads, all of it when Sbus is
+// stale; the solver's Vout rows) and the caller's outputs.  After whatif_prepare.
+template <class Between>
+static int whatif_drive(mapdn_handle* h, const void* actions, int dtype, int K, double* reward, double* info, uint8_t* status,
+                        int32_t* iterations, double* vm_pu, hipStream_t st, Between between) {
   const Dev& d = h->d;
   WhatifState s = h->whatif;
   s.K = K; s.reward = reward; s.info = info; s.status_out = status; s.iters_out = iterations; s.vm_out = vm_pu;
@@ -331,10 +351,16 @@ static int whatif_run(mapdn_handle* h, const void* actions, int dtype, int K, do
   for (int k = 0; k < K; ++k) {
     launch_whatif_start(d, s, actions, dtype, k, st);
     nr_launch(h, MODE_SOLVE, nullptr, nullptr, nullptr, st, nullptr, 0, &dd);
+    between(k);
     launch_whatif_score(d, s, k, st);
   }
   HIPCHK(h, hipGetLastError());
   return MAPDN_OK;
+}
+static int whatif_run(mapdn_handle* h, const void* actions, int dtype, int K, double* reward, double* info, uint8_t* status,
+                      int32_t* iterations, double* vm_pu, hipStream_t st) {
+  if (const int rc = whatif_prepare(h)) return rc;
+  return whatif_drive(h, actions, dtype, K, reward, info, status, iterations, vm_pu, st, [](int) {});
 }
 
 // ---- mapdn_action_gradients (grad.hip, grad.hpp; grad_sparse.hip): what the adjoint solve does not cover, by name.  grad_meshed = 1
@@ -342,11 +368,7 @@ static int whatif_run(mapdn_handle* h, const void* actions, int dtype, int K, do
 static bool grad_on_sparse(const mapdn_handle* h) { return h->knobs.grad_meshed == 1 && h->solver == 1; }
 static const char* grad_refusal(const mapdn_handle* h) {
   const Plan& P = h->plan;
-  if ((!P.radial || h->solver != 0) && !grad_on_sparse(h))
-    return h->knobs.grad_meshed == 1
-               ? "action_gradients: meshed nets and radial ones on the dense solver (nr_solver = dense, k_nr_dense) are not supported (grad_meshed = 1 covers "
-                 "the sparse solver)"
-               : "action_gradients: meshed nets and handles on another solver than the tree solver are not supported";
+  if (const char* why = solver_gate(h, "action_gradients", "grad_meshed", h->knobs.grad_meshed == 1)) return why;
   if (P.zip) return "action_gradients: voltage-dependent (ZIP) loads are not supported";
   if (P.n_gen) return "action_gradients: nets with generators (net.gen, gen buses) are not supported (k_action_grad takes every non-slack bus as a PQ bus)";
   if (P.gen_start && grad_on_sparse(h))
@@ -363,13 +385,11 @@ static int grad_prepare_sparse(mapdn_handle* h) {
   const Plan& P = h->plan;
   GradState& g = h->grad;
   GradSparseState& t = h->grad_sparse;
-  std::vector<int32_t> sgn(std::max<size_t>((size_t)P.ns, 1), 0);
-  for (size_t j = 0; j < (size_t)P.ns; ++j) sgn[j] = P.pos_of_obus[P.sgen_bus[j]];
   std::vector<GsNz> nz;
   grad_sparse_table(P, h->sprog, nz, t.rows_per_sub, t.max_nnz);
-  if ((rc = dupload(h, &g.sg_node, sgn)) || (rc = dupload(h, &t.nz, nz))) return rc;
+  if ((rc = dupload(h, &g.sg_node, sgen_nodes(P))) || (rc = dupload(h, &t.nz, nz))) return rc;
   t.nz_bytes = (uint32_t)(nz.size() * sizeof(GsNz));
-  if (grad_sparse_prepare(h->sp_lanes) != 0) { (void)hipGetLastError(); h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for k_action_grad_sparse"; return MAPDN_E_HIP; }
+  if ((rc = sparse_prepared(h, grad_sparse_prepare(h->sp_lanes), "k_action_grad_sparse"))) return rc;
   g.act = h->whatif.act; g.nr_conv = h->whatif.nr_conv; g.a = h->whatif.a;
   h->grad_ready = true;
   return MAPDN_OK;
@@ -392,25 +412,16 @@ static int grad_prepare(mapdn_handle* h) {
   return MAPDN_OK;
 }
 
-// whatif_run with k_action_grad (a k_nr_sparse handle: k_action_grad_sparse) between the solve and the scoring of every candidate.  Only enqueues; writes what whatif_run writes,
-// the gradient workspace and the caller's grad.
+// whatif_drive with k_action_grad (a k_nr_sparse handle: k_action_grad_sparse) between the solve and the scoring of every candidate.
+// Only enqueues; writes what whatif_run writes, the gradient workspace and the caller's grad.
 static int grad_run(mapdn_handle* h, const void* actions, int dtype, int K, double* grad, double* reward, double* info, uint8_t* status,
                     int32_t* iterations, double* vm_pu, hipStream_t st) {
   if (const int rc = grad_prepare(h)) return rc;
   const Dev& d = h->d;
-  WhatifState s = h->whatif;
-  s.K = K; s.reward = reward; s.info = info; s.status_out = status; s.iters_out = iterations; s.vm_out = vm_pu;
   GradState g = h->grad;
   g.K = K; g.grad = grad;
-  Dev dd;
-  if (const int rc = ctl_begin(h, s, 0, st, &dd)) return rc;
-  for (int k = 0; k < K; ++k) {
-    launch_whatif_start(d, s, actions, dtype, k, st);
-    nr_launch(h, MODE_SOLVE, nullptr, nullptr, nullptr, st, nullptr, 0, &dd);
+  return whatif_drive(h, actions, dtype, K, reward, info, status, iterations, vm_pu, st, [&](int k) {
     if (h->solver == 1) launch_action_grad_sparse(d, g, h->grad_sparse, k, st);
     else launch_action_grad(d, g, k, st);
-    launch_whatif_score(d, s, k, st);
-  }
-  HIPCHK(h, hipGetLastError());
-  return MAPDN_OK;
+  });
 }

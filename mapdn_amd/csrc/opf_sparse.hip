@@ -3,7 +3,8 @@
 //   the solve (MODE_SOLVE)  ->  k_opf_sens_sparse (S and dV, by the handle's elimination program)  ->  k_opf_reduce_sparse (M V, loss,
 //   violation, W = M dV, g, H)  ->  k_opf_qp  ->  k_opf_update
 // with OpfState's workspace in the tree's layouts (no fac), so that k_opf_qp and k_opf_update run as they are.  The arithmetic is in
-// opf_sparse.hpp.  Included at the end of kernels.hip (one translation unit) like grad_sparse.hip.
+// opf_sparse.hpp; the wave frame, the assembly ring and the program's interpreter are sparse_prog.hpp's.  Included at the end of
+// kernels.hip (one translation unit) like grad_sparse.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,7 +17,7 @@
 
 namespace mapdn {
 
-// Layout: k_nr_sparse's and k_action_grad_sparse's.  One wavefront per workgroup serves L envs with S = 64 / L sub-lanes each (lane =
+// Layout: sparse_prog.hpp's (SpWave).  One wavefront per workgroup serves L envs with S = 64 / L sub-lanes each (lane =
 // sub * L + env); the blocks live in LDS as [slot][env][2x2] behind the [n + 2] voltages, nr_sparse_lds_bytes in all.  Control flow is
 // wave-uniform: an env that is not linearised (stopped, or its power flow failed) runs the program on whatever its own slots hold and
 // writes nothing.  The program factorises in place, so every PAIR of columns (j, j + 1) assembles the blocks again; the two columns
@@ -27,112 +28,62 @@ __global__ void __launch_bounds__(64)
 k_opf_sens_sparse(Dev d, OpfState o) {
   extern __shared__ d2 lds2[];
   constexpr unsigned S = 64u / L;
-  const unsigned lane = threadIdx.x, s = lane / L, el = lane % L;
-  const unsigned e = blockIdx.x * L + el;                          // < Bp: every per-env array has a row for it
+  const SpWave<L> w(d, lds2);
+  const unsigned s = w.s, e = w.e;
   const int n = d.n, ns = d.ns;
   const size_t Bp = (size_t)d.Bp;
-  d2* sV = lds2 + el;                                              // sV[k * L] = (e, f); k = n slack, n + 1 trash
-  d2* sB = lds2 + (size_t)(n + 2) * L + 2u * el;                   // block b: sB[b * 2L], sB[b * 2L + 1] = rows (a00 a01), (a10 a11)
-  auto blk = [&](unsigned b) { return sB + (size_t)b * (2u * L); };
-  const OpfVec E{d.nrbuf + ((size_t)d.r_vout + VO_E) * Bp + e, VOF * Bp}, F{d.nrbuf + ((size_t)d.r_vout + VO_F) * Bp + e, VOF * Bp},
-      VM{d.nrbuf + ((size_t)d.r_vout + VO_VM) * Bp + e, VOF * Bp};
+  const OpfVec VM{d.nrbuf + ((size_t)d.r_vout + VO_VM) * Bp + e, VOF * Bp};
   const bool go = e < (unsigned)d.B && o.act[e] != 0 && o.nr_conv[e] != 0;
-  const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(const_cast<SpOp*>(d.sp_ops), 0, d.sp_ops_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsZ = __builtin_amdgcn_make_buffer_rsrc(const_cast<SpNz*>(d.sp_nz), 0, d.sp_nz_bytes, 0x00020000);
-  const int RPS = d.sp_rows_per_sub, MNZ = d.sp_max_nnz, NPH = d.sp_phases;
-  const unsigned voO = s * 16u;                                    // this sub-lane's op of phase p: + p * S * 16
-  const unsigned voZ = s * (unsigned)RPS * (unsigned)MNZ * 32u;    // the Ybus entries of its assembly rows
-  // ---- the converged voltage (the frame's Vout rows, the slack's included); the trash node of the padding entries
-  for (unsigned p = s; p < (unsigned)n + 2u; p += S) sV[(size_t)p * L] = p <= (unsigned)n ? d2{E[p], F[p]} : d2{0.0, 0.0};
+  const auto nz = sp_stream(d.sp_nz, d.sp_nz_bytes, d.sp_rows_per_sub, d.sp_max_nnz);   // the stream k_nr_sparse assembles from
+  // ---- the converged voltage and the trash node of the padding entries
+  sp_load_voltages(w, d);
   for (int j = 0; j < ns; j += 2) {                                // (uniform)
     // ---- 1. the fill slots and ALL right-hand-side slots: zero
     gs_handoff();                                                  // (the read-out of the pair before; the voltages)
-    for (unsigned q = s; q < (unsigned)d.sp_fill; q += S) {
-      d2* f = blk((unsigned)d.sp_fill_slots[q]);
-      f[0] = d2{0.0, 0.0}; f[1] = d2{0.0, 0.0};
-    }
+    sp_zero_fill(w, d);
     for (unsigned p = s; p < (unsigned)n; p += S) {
-      d2* rh = blk((unsigned)n + p);
+      d2* rh = w.blk((unsigned)n + p);
       rh[0] = d2{0.0, 0.0}; rh[1] = d2{0.0, 0.0};
     }
     gs_handoff();
-    // ---- 2. the blocks of J, row by row (sub-lane s owns rows s, s + S, ...), from the stream k_nr_sparse assembles from (Dev::sp_nz),
-    //      read through a ring that runs PF entries ahead of the arithmetic
-    {
-      constexpr int PF = 8;
-      const int T = RPS * MNZ;
-      u32x4 zq0[PF]; u32x2 zq1[PF];
-      auto zload = [&](int tt, u32x4& z0, u32x2& z1) {
-        const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)min(tt, T - 1) * 32u);
-        z0 = __builtin_amdgcn_raw_buffer_load_b128(rsZ, voZ, so, 0);               // col, slot, Re Y_ij
-        z1 = __builtin_amdgcn_raw_buffer_load_b64(rsZ, voZ + 16u, so, 0);          // Im Y_ij
-      };
-#pragma unroll
-      for (int u = 0; u < PF; ++u) zload(u, zq0[u], zq1[u]);
-      int r = 0, q = 0;
-      unsigned i = s;
-      bool live = i < (unsigned)n;
-      d2 vi = sV[(size_t)(live ? i : (unsigned)n + 1u) * L];
-      double sr = 0.0, si = 0.0, aii_r = 0.0, aii_i = 0.0;
-      for (int t0 = 0; t0 < T; t0 += PF) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-          const int tt = t0 + u;
-          if (tt < T) {                          // (uniform; no `break`: the loop must unroll for the ring to stay in registers)
-          const u32x4 z0 = zq0[u]; const u32x2 z1 = zq1[u];
-          zload(tt + PF, zq0[u], zq1[u]);
-          const double yr = __hiloint2double((int)z0.w, (int)z0.z), yi = __hiloint2double((int)z1.y, (int)z1.x);
-          const unsigned col = z0.x & ~SP_COL_GEN;               // (no gen buses here: opf_resolve refuses them)
-          const int slot = (int)z0.y;
-          const d2 vj = sV[(size_t)col * L];
-          double ar, ai;
-          gs_a(vi.x, vi.y, yr, yi, vj.x, vj.y, &ar, &ai);                          // A_ij: the row sum S_i, A_ii and the block (i, j)
-          sr += ar; si += ai;
-          if (col == i) { aii_r = ar; aii_i = ai; }
-          if (slot >= 0) {
-            const Opf2x2 m = gs_offdiag(ar, ai);
-            d2* ob = blk((unsigned)slot);
-            ob[0] = d2{m.m00, m.m01}; ob[1] = d2{m.m10, m.m11};
+    // ---- 2. the blocks of J, row by row (sub-lane s owns rows s, s + S, ...).  (No gen buses here: opf_resolve refuses them.)
+    sp_assemble(
+        w, nz, [](unsigned, bool) {},
+        [&](const SpRec<sizeof(SpNz)>&, unsigned slot, d2, d2, double ar, double ai) {
+          const Opf2x2 m = gs_offdiag(ar, ai);
+          d2* ob = w.blk(slot);
+          ob[0] = d2{m.m00, m.m01}; ob[1] = d2{m.m10, m.m11};
+        },
+        [&](unsigned i, bool live, d2, double sr, double si, double aii_r, double aii_i) {
+          if (live) {
+            const Opf2x2 m = gs_diag(sr, si, aii_r, aii_i);
+            d2* dg = w.blk(i);
+            dg[0] = d2{m.m00, m.m01}; dg[1] = d2{m.m10, m.m11};
           }
-          if (++q == MNZ) {                      // (uniform) end of the row: the diagonal block; next row
-            if (live) {
-              const Opf2x2 m = gs_diag(sr, si, aii_r, aii_i);
-              d2* dg = blk(i);
-              dg[0] = d2{m.m00, m.m01}; dg[1] = d2{m.m10, m.m11};
-            }
-            q = 0; ++r;
-            i = (unsigned)r * S + s;
-            live = i < (unsigned)n && r < RPS;
-            vi = sV[(size_t)(live ? i : (unsigned)n + 1u) * L];
-            sr = si = aii_r = aii_i = 0.0;
-          }
-          }
-        }
-      }
-    }
+        });
     // ---- 3. the two columns: w e_Q of sgen j in column 0 of the slot of its node, of sgen j + 1 in column 1 of the slot of its (an sgen
     //      on the slack, node == n: a zero column; two sgens of one node share a slot).  One sub-lane, after the zeroing above.
     if (s == 0) {
       for (int c = 0; c < 2 && j + c < ns; ++c) {
         const int node = o.sg_node[j + c];
         const size_t oo = (size_t)(j + c) * Bp + e;
-        const double w = q_limit(d.cur_pv[oo], d.smax[j + c]) * d.sgen_scale[j + c] / d.sn;
+        const double wq = q_limit(d.cur_pv[oo], d.smax[j + c]) * d.sgen_scale[j + c] / d.sn;
         if (node < n) {
-          d2* rh = blk((unsigned)(n + node));
-          if (c == 0) rh[1].x = w; else rh[1].y = w;
+          d2* rh = w.blk((unsigned)(n + node));
+          if (c == 0) rh[1].x = wq; else rh[1].y = wq;
         }
       }
     }
     gs_handoff();
-    // ---- 4. the program, all phases (sparse_prog.hpp)
-    sp_run_program<L>(sB, rsO, voO, NPH);
+    // ---- 4. the program, all phases
+    sp_run_program(w);
     gs_handoff();
     // ---- 5. (dtheta, u) of both columns from the slots n + i: S = u |V| and dV = (u + j dtheta) V, in k_opf_linearise's layouts
     if (go) {
       const size_t xs = (size_t)ns * 2;
       for (unsigned p = s; p < (unsigned)n; p += S) {
-        const d2* x = blk((unsigned)n + p);
-        const d2 th = x[0], u = x[1], v = sV[(size_t)p * L];
+        const d2* x = w.blk((unsigned)n + p);
+        const d2 th = x[0], u = x[1], v = w.sV[(size_t)p * L];
         const double vm = VM[p];
         o.S[((size_t)p * ns + j) * Bp + e] = u.x * vm;
         double* X0 = o.X + ((size_t)j * 2 + (size_t)p * xs) * Bp + e;
@@ -191,21 +142,11 @@ __global__ void __launch_bounds__(DL * DS) k_opf_reduce_sparse(Dev d, OpfState s
     }
 }
 
-#define SP_FOR_EACH(X) X(16) X(8) X(4) X(2)
-int opf_sparse_prepare(int L) {
-#define X(l) if (L == l) return hipFuncSetAttribute((const void*)k_opf_sens_sparse<l>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess ? 0 : -1;
-  SP_FOR_EACH(X)
-#undef X
-  return -2;
-}
+int opf_sparse_prepare(int L) { return sp_prepare(L, [](auto l) { return k_opf_sens_sparse<decltype(l)::value>; }); }
 
 void launch_opf_linearise_sparse(const Dev& d, const OpfState& s, const OsM& m, hipStream_t st) {
-  const size_t lds = nr_sparse_lds_bytes(d.n, d.sp_blocks, d.sp_lanes);
-#define X(l) if (d.sp_lanes == l) hipLaunchKernelGGL((k_opf_sens_sparse<l>), dim3((d.B + l - 1) / l), dim3(64), lds, st, d, s);
-  SP_FOR_EACH(X)
-#undef X
+  sp_launch(d, d.B, st, [](auto l) { return k_opf_sens_sparse<decltype(l)::value>; }, d, s);
   hipLaunchKernelGGL(k_opf_reduce_sparse, dim3((d.B + DL - 1) / DL), dim3(DL * DS), 0, st, d, s, m);
 }
-#undef SP_FOR_EACH
 
 }  // namespace mapdn

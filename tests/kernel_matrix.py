@@ -2,7 +2,7 @@
 row's handle reports its kernel, the rows cover the compiled set) and tests/test_kernel_matrix_gpu.py (every row against the oracle).
 
 The compiled set is parsed from the sources, not restated: the k_nr_tree instantiations of csrc/nr_inst_list.hpp (NR_INSTS_*, NR_INSTS_DC_*,
-NR_INSTS_ZIP_* and NR_INSTS_GEN_*, the latter two once per start), k_nr_sparse<L, DC> for every L of SP_FOR_EACH (sparse.hip), and
+NR_INSTS_ZIP_* and NR_INSTS_GEN_*, the latter two once per start), k_nr_sparse<L, DC> for every L of SP_FOR_EACH (sparse_prog.hpp), and
 k_nr_dense<W, GA> for the LDS-resident pair of dense_fn and every W of DENSE_GA_W (dense.hip).  A kernel is a tuple:
     ("tree", W, L, HL, GL, RES, DC, ZIP, GEN)   ("sparse", L, DC, ZIP, GEN)   ("dense", W, GA)
 k_nr_sparse decides ZIP and GEN at run time, so its compiled kernel is ("sparse", L, DC) and its rows cover every (L, DC, ZIP) without
@@ -64,7 +64,7 @@ def tree_kernels():
 
 
 def sparse_kernels():
-    lanes = [int(x) for x in re.findall(r"X\((\d+)\)", _macro(_src("sparse.hip"), "SP_FOR_EACH"))]
+    lanes = [int(x) for x in re.findall(r"X\((\d+)\)", _macro(_src("sparse_prog.hpp"), "SP_FOR_EACH"))]
     return [("sparse", l, dc) for l in lanes for dc in (0, 1)]
 
 
