@@ -1,7 +1,8 @@
 """action_gradients on handles of the sparse solver (mapdn_env_config.grad_meshed = 1, k_action_grad_sparse): what
 tests/test_action_grad_sparse_cpu.py and tests/test_action_grad_sparse_gpu.py share.  Test infrastructure only, independent of the
 product code: the reference is tests/grad_ref.py (dense, topology-agnostic), the nets are those of tests/meshed_edge_nets.py,
-crowded_meshed of tests/element_edge_nets.py and the shipped case33 pinned to the sparse solver.
+crowded_meshed of tests/element_edge_nets.py and the shipped case33 pinned to the sparse solver; the keys of tests/sparse_table_cases.py
+ are handed on to that module's make(), fits() and UNSOLVABLE.
 
 The scenario is that of tests/grad_ref.py: reset, one random step, then the candidates {0, random, UNSOLVABLE, random, ...} of every env.
 The meshed shapes are stiff: their unsolvable action is meshed_edge_nets.STEP_UNSOLVABLE.  The k9_hv net starts every power flow from
@@ -17,6 +18,7 @@ from tests import element_edge_nets as N
 from tests import grad_ref as G
 from tests import meshed_edge_nets as M
 from tests import opf_kernel_cases as OK
+from tests import sparse_table_cases as ST
 from tests import whatif_cases as W
 
 B_MAX, K_MAX = 35, 4
@@ -31,17 +33,23 @@ VARIANT_SHAPE = (5, 4)
 
 def make(key):
     """(NetSpec, Profiles, base env args)"""
+    if key in ST.KEYS:
+        return ST.make(key)
     if key in MESHED:
         return (*M.make_net(key), M.ARGS)
     return W.make(key)
 
 
 def unsolvable(key):
+    if key in ST.KEYS:
+        return ST.UNSOLVABLE[key]
     return M.STEP_UNSOLVABLE if key in MESHED else W.UNSOLVABLE
 
 
 def fits(key):
     """the sp_lanes at which k_nr_sparse (so k_action_grad_sparse) fits the net"""
+    if key in ST.KEYS:
+        return ST.fits(key)
     if key in MESHED:
         return [L for L in M.SP_LANES if L not in M.LDS_REFUSED[M.base_of(key)]]
     return list(M.SP_LANES)                                   # crowded_meshed (15 nodes), case33 (32 nodes, no fill)
@@ -227,6 +235,10 @@ E64 = {
     ("wheel_rim", (("voltage_barrier_type", "l1"),)): 1.82e-15, ("wheel_rim", (("voltage_barrier_type", "l2"),)): 1.05e-14,
     ("wheel_rim", (("voltage_barrier_type", "courant_beltrami"),)): 1.47e-16, ("wheel_rim", (("voltage_barrier_type", "bump"),)): 2.54e-13,
     ("tail2x", G.LINE_ARGS): 7.78e-13,
+    # tests/sparse_table_cases.py
+    ("ring33_s16", ()): 2.68e-14, ("ring33_s17", ()): 2.96e-14, ("ladder66_s33", ()): 5.29e-14, ("ladder66_s64", ()): 1.20e-13,
+    ("ladder66_s65", ()): 1.39e-13, ("ladder65_s4", ()): 1.60e-13, ("special_meshed", ()): 1.99e-14, ("case141_ties", ()): 1.49e-13,
+    ("special_meshed", G.LINE_ARGS): 1.66e-12,
 }
 
 

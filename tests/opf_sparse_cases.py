@@ -2,7 +2,8 @@
 section 25): what tests/test_opf_sparse_cpu.py and tests/test_opf_sparse_gpu.py share.  Test infrastructure only, independent of the
 product code: the references are tests/opf_ref.py (dense, topology-agnostic) and tests/opf_kernel_cases.linearise_ext (the same
 definition above float64); the nets are those of tests/meshed_edge_nets.py, crowded_meshed of tests/element_edge_nets.py, and the
-shipped case33, pinned to the sparse solver and with five tie lines closed.
+shipped case33, pinned to the sparse solver and with five tie lines closed; the keys of tests/sparse_table_cases.py (DESIGN.md section 27:
+the edges of the sgen table, feeder size) are handed on to that module's make() and fits().
 
 States: env e stands at profile row rows_of(prof, B)[e] — noon (per_day / 2) and 03:00 (per_day / 8: no PV, the whole s_max is
 reactive headroom) of the first two days — with its loads times `scale` (1, or 8: scaled(prof, 8)); s_max = 1.2 x max pv.  The k9_hv net
@@ -21,6 +22,7 @@ from tests import grad_sparse_cases as GS
 from tests import meshed_edge_nets as M
 from tests import opf_kernel_cases as K
 from tests import opf_ref as R
+from tests import sparse_table_cases as ST
 
 B_MAX = 35
 BATCHES = (1, 5, 17, 35)                       # a partly filled last workgroup at every sp_lanes
@@ -40,6 +42,8 @@ runpp_of = GS.runpp_of
 @functools.lru_cache(maxsize=None)
 def make(key):
     """(NetSpec, Profiles, base env args); cached: read-only"""
+    if key in ST.KEYS:
+        return ST.make(key)
     if key in M.SHAPES:
         return (*M.make_net(key), M.ARGS)
     if key in ("case33", "case33_meshed"):
@@ -50,6 +54,8 @@ def make(key):
 
 def fits(key):
     """the sp_lanes at which k_nr_sparse (so k_opf_sens_sparse) fits the net"""
+    if key in ST.KEYS:
+        return ST.fits(key)
     if M.base_of(key) in M.SHAPES:
         return [L for L in M.SP_LANES if L not in M.LDS_REFUSED[M.base_of(key)]]
     return list(M.SP_LANES)                     # crowded_meshed (15 nodes), case33 (32 nodes, little fill)
@@ -166,6 +172,14 @@ E64 = {
     "k9_hv": dict(S=5.98e-14, g=1.47e-10, H=2.41e-13, loss=1.05e-08, violation=0.00e+00),
     "case33": dict(S=1.31e-14, g=4.22e-13, H=2.08e-14, loss=4.55e-12, violation=1.32e-15),
     "case33_meshed": dict(S=5.14e-15, g=1.00e-13, H=9.75e-15, loss=2.48e-12, violation=9.19e-15),
+    # tests/sparse_table_cases.py
+    "ring33_s16": dict(S=1.53e-14, g=1.32e-11, H=2.41e-14, loss=1.25e-08, violation=0.00e+00),
+    "ring33_s17": dict(S=2.22e-14, g=1.11e-11, H=2.69e-14, loss=5.89e-09, violation=0.00e+00),
+    "ladder66_s33": dict(S=1.21e-13, g=3.07e-11, H=8.92e-14, loss=1.45e-07, violation=0.00e+00),
+    "ladder66_s64": dict(S=1.74e-13, g=3.10e-11, H=1.08e-13, loss=1.64e-07, violation=0.00e+00),
+    "ladder65_s4": dict(S=1.36e-13, g=4.73e-11, H=6.32e-14, loss=5.45e-08, violation=0.00e+00),
+    "special_meshed": dict(S=2.08e-14, g=1.01e-12, H=1.84e-14, loss=6.62e-12, violation=1.09e-14),
+    "case141_ties": dict(S=1.41e-13, g=3.08e-12, H=1.40e-13, loss=4.44e-11, violation=0.00e+00),
 }
 
 
