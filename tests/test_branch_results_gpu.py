@@ -46,9 +46,11 @@ def make_env(net, prof, B, **kw):
     return VoltageControlBatch(net, prof, dict(ARGS), n_envs=B, device=DEV, obs_dtype=torch.float64, **kw)
 
 
-def c_tables(env, vm=None, va=None, line_cols=R.COLUMNS, trafo_cols=R.COLUMNS):
+def c_tables(env, vm=None, va=None, line_cols=R.COLUMNS, trafo_cols=R.COLUMNS, null=()):
     """mapdn_get_branch_results through ctypes; every column of the struct gets a guarded array, only the requested ones are handed over.
-    Returns (line, trafo): dicts of the requested columns; the others must still hold the sentinel."""
+    Returns (line, trafo): dicts of the requested columns; the others must still hold the sentinel.  null: the tables ("line", "trafo")
+    whose struct pointer itself is NULL (their columns must be empty)."""
+    assert not (("line" in null and line_cols) or ("trafo" in null and trafo_cols))
     B = env.n_envs
     tabs = []
     for cols, n in ((line_cols, env.n_line), (trafo_cols, env.n_trafo)):
@@ -59,7 +61,8 @@ def c_tables(env, vm=None, va=None, line_cols=R.COLUMNS, trafo_cols=R.COLUMNS):
         tabs.append((g, s, cols))
     with torch.cuda.device(env.device):
         rc = env._lib.mapdn_get_branch_results(env._h, None if vm is None else vm.data_ptr(), None if va is None else va.data_ptr(),
-                                               C.byref(tabs[0][1]), C.byref(tabs[1][1]), env._stream())
+                                               None if "line" in null else C.byref(tabs[0][1]), None if "trafo" in null else C.byref(tabs[1][1]),
+                                               env._stream())
     _lib.check(rc, env._h)
     torch.cuda.synchronize()
     out = []
