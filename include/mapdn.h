@@ -829,6 +829,35 @@ int mapdn_evaluate_actions(mapdn_handle* h, const void* actions, int32_t actions
 int mapdn_action_gradients(mapdn_handle* h, const void* actions, int32_t actions_dtype, int32_t n_candidates, double* grad,
                            double* reward, double* info, uint8_t* status, int32_t* iterations, double* vm_pu, void* stream);
 
+/* ---- Voltage VJP: the bus voltages of candidate actions differentiated by the actions, for any cotangent.
+ * For every env e and candidate k, with vm_pu[e][k][b] and va_degree[e][k][b] the bus voltages that mapdn_step with actions[e][k]
+ * (unclipped, as mapdn_evaluate_actions takes them) would commit, and for every cotangent m = 0 ... M - 1 (M = n_cotangents):
+ *   grad[e][k][m][j] = sum_b cot_vm[e][k][m][b] d vm_pu_b / d a_j + cot_va[e][k][m][b] d va_degree_b / d a_j,
+ * every other entry of the candidate and the env's state held fixed (the limits sqrt(s_max_j^2 - p_j^2) are those of the state at the
+ * call).  Exact at the converged power flow: the polar Jacobian is factorised once per (e, k) on the elimination tree, and every
+ * cotangent costs one adjoint solve on those factors.  There is no direct term.  Env-major buffers:
+ *   actions    [B, K, ns] of actions_dtype; K = n_candidates, 1 ... MAPDN_WHATIF_MAX_CANDIDATES
+ *   cot_vm, cot_va   f64 [B, K, M, nb], each may be NULL (zeros); M = 0 ... MAPDN_VJP_MAX_COTANGENTS.  The entries of the ext_grid bus
+ *              are never read (its voltage does not move): a NaN there does not reach the result
+ *   grad       f64 [B, K, M, ns]; NULL if and only if M == 0.  An sgen on the ext_grid bus gets exactly 0.0
+ *   vm_pu, va_degree   f64 [B, K, nb], each may be NULL; vm_pu is bit for bit what mapdn_evaluate_actions writes
+ *   status     u8 [B, K] and iterations i32 [B, K] or NULL: bit for bit what mapdn_evaluate_actions writes
+ * Rows of status 2 (the power flow did not converge) and 3 (not evaluated) are NaN in grad, vm_pu and va_degree; so is a row of
+ * status 0 in which some q_j = sqrt(s_max_j^2 - p_j^2) a_j is not finite (mapdn_action_gradients' rule).
+ * Device pointers on `stream`.  Only enqueues (four launches per candidate, three with M = 0 and va_degree NULL, one more after the last
+ * candidate when vm_pu is given); the workspace is that of mapdn_action_gradients and does not grow with K or M; a row has the same bits
+ * whatever B, K, M, the env's place in the batch, the other candidates and the other cotangents are.  The env's state and its next
+ * mapdn_step are left alone as by mapdn_evaluate_actions.
+ * Refused, by name in mapdn_last_error and with nothing launched, on host-only handles too — first the arguments: MAPDN_E_INVALID for a
+ * NULL actions / status, a bad dtype, n_candidates < 1 or > MAPDN_WHATIF_MAX_CANDIDATES, n_cotangents < 0 or >
+ * MAPDN_VJP_MAX_COTANGENTS, M >= 1 with both cotangents NULL, M == 0 with a grad buffer or M >= 1 without one; then the handle
+ * ("voltage_vjp: ... not supported"): handles of the sparse and of the dense solver (whatever grad_meshed says), meshed nets,
+ * voltage-dependent (ZIP) loads, generators, fused buses.  MAPDN_E_STATE before mapdn_reset and on a host-only handle. */
+#define MAPDN_VJP_MAX_COTANGENTS 1024
+int mapdn_voltage_vjp(mapdn_handle* h, const void* actions, int32_t actions_dtype, int32_t n_candidates, int32_t n_cotangents,
+                      const double* cot_vm, const double* cot_va, double* grad, double* vm_pu, double* va_degree, uint8_t* status,
+                      int32_t* iterations, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,7 +36,7 @@ EXPORTS = (
     "mapdn_critic_head_forward", "mapdn_critic_head_scratch_floats", "mapdn_critic_head_backward", "mapdn_critic_head_backward_dot", "mapdn_critic_head_mse", "mapdn_get_profile_stats",
     "mapdn_explore_actions", "mapdn_rollout_stats", "mapdn_copy_segments",
     "mapdn_policy_forward_train", "mapdn_policy_backward", "mapdn_policy_backward_scratch_floats", "mapdn_get_dc_angles",
-    "mapdn_get_nr_kernel", "mapdn_droop_actions", "mapdn_opf_actions", "mapdn_opf_probe", "mapdn_evaluate_actions", "mapdn_action_gradients", "mapdn_policy_forward_geometry", "mapdn_critic_head_backward_geometry",
+    "mapdn_get_nr_kernel", "mapdn_droop_actions", "mapdn_opf_actions", "mapdn_opf_probe", "mapdn_evaluate_actions", "mapdn_action_gradients", "mapdn_voltage_vjp", "mapdn_policy_forward_geometry", "mapdn_critic_head_backward_geometry",
     "mapdn_critic_twin_forward", "mapdn_critic_twin_scratch_floats", "mapdn_critic_twin_geometry", "mapdn_critic_twin_mse",
     "mapdn_critic_head_counterfactual",
     "mapdn_attention_forward", "mapdn_attention_backward", "mapdn_attention_scratch_floats", "mapdn_attention_max_agents",
@@ -298,6 +298,7 @@ def load():
     lib.mapdn_opf_probe.argtypes = [vp, C.POINTER(COPFConfig), vp, C.c_int32] + [vp] * 13
     lib.mapdn_evaluate_actions.argtypes = [vp, vp, C.c_int32, C.c_int32] + [vp] * 6
     lib.mapdn_action_gradients.argtypes = [vp, vp, C.c_int32, C.c_int32] + [vp] * 7
+    lib.mapdn_voltage_vjp.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 8
     lib.mapdn_set_branch_ratings.argtypes = [vp, _pd, _pd, _pd, _pd, _pd]
     lib.mapdn_get_branch_results.argtypes = [vp, vp, vp, C.POINTER(CBranchOut), C.POINTER(CBranchOut), vp]
     lib.mapdn_get_loading_summary.argtypes = [vp, C.c_double, vp, vp, vp, vp]

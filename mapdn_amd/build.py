@@ -12,7 +12,7 @@ LIB = os.environ.get("MAPDN_BUILD_OUT") or os.path.join(HERE, "libmapdn_hip.so")
 SOURCES = ["plan.cpp", "kernels.hip", "dense.hip", "sparse.hip", "policy.hip", "policy_bwd.hip", "critic.hip", "rollout.hip", "capi.hip"]
 # k_nr_tree's instantiations (nr_inst_list.hpp) are compiled as NR_PARTS objects from ONE source, in parallel
 NR_INST_SOURCE, NR_PARTS = "nr_inst.hip", 4
-HEADERS = ["plan.hpp", "branch.hpp", "branch.hip", "ppo.hip", "colstats.hpp", "rowtile.hpp", "headtile.hpp", "kernels.hpp", "inject.hpp", "philox.hpp", "nrmath.hpp", "ctlloop.hpp", "droop.hpp", "droop.hip", "opf.hpp", "opf.hip", "baselines_host.hpp", "whatif.hpp", "whatif.hip", "grad.hpp", "grad.hip", "grad_sparse.hpp", "grad_sparse.hip", "sparse_prog.hpp", "opf_sparse.hpp", "opf_sparse.hip", "critic_twin.hip", "critic_cf.hip", "critic_attn.hip", "critic_shap.hip", "nr_common.hpp", "gen_mask.hpp", "nr_tree.hpp", "nr_inst_list.hpp", NR_INST_SOURCE,
+HEADERS = ["plan.hpp", "branch.hpp", "branch.hip", "ppo.hip", "colstats.hpp", "rowtile.hpp", "headtile.hpp", "kernels.hpp", "inject.hpp", "philox.hpp", "nrmath.hpp", "ctlloop.hpp", "droop.hpp", "droop.hip", "opf.hpp", "opf.hip", "baselines_host.hpp", "whatif.hpp", "whatif.hip", "grad.hpp", "grad.hip", "vjp.hpp", "vjp.hip", "grad_sparse.hpp", "grad_sparse.hip", "sparse_prog.hpp", "opf_sparse.hpp", "opf_sparse.hip", "critic_twin.hip", "critic_cf.hip", "critic_attn.hip", "critic_shap.hip", "nr_common.hpp", "gen_mask.hpp", "nr_tree.hpp", "nr_inst_list.hpp", NR_INST_SOURCE,
            os.path.join("..", "..", "include", "mapdn.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result"]
 HASH_TAG = b"MAPDN_SRC_HASH="

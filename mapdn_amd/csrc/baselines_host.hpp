@@ -425,3 +425,36 @@ static int grad_run(mapdn_handle* h, const void* actions, int dtype, int K, doub
     else launch_action_grad(d, g, k, st);
   });
 }
+
+// ---- mapdn_voltage_vjp (vjp.hip, vjp.hpp): grad_refusal's list under its own prefix.  The tree solver on a radial net answers; a handle
+// of the sparse or of the dense solver is refused by name whatever grad_meshed says.
+static const char* vjp_refusal(const mapdn_handle* h) {
+  const Plan& P = h->plan;
+  if (h->solver == 1)
+    return "voltage_vjp: handles of the sparse solver (k_nr_sparse: meshed nets and radial ones pinned to it, with grad_meshed = 1 too) are not supported";
+  if (h->solver != 0) return "voltage_vjp: handles of the dense solver (nr_solver = dense, k_nr_dense) are not supported";
+  if (!P.radial) return "voltage_vjp: meshed nets are not supported";
+  if (P.zip) return "voltage_vjp: voltage-dependent (ZIP) loads are not supported";
+  if (P.n_gen) return "voltage_vjp: nets with generators (net.gen, gen buses: k_voltage_vjp takes every non-slack bus as a PQ bus) are not supported";
+  if (P.nbo != P.nb || !P.fused_obus.empty() || !P.alias_pos.empty()) return "voltage_vjp: fused buses are not supported";
+  return nullptr;
+}
+
+// whatif_drive with k_voltage_vjp between the solve and the scoring of every candidate (M = 0 and no angles wanted: nothing between
+// them), on the tables and the workspace of grad_prepare: nothing grows with K or M.  The frame's reward and info are not written.
+// Only enqueues; writes what whatif_run writes, the gradient workspace and the caller's outputs.
+static int vjp_run(mapdn_handle* h, const void* actions, int dtype, int K, int M, const double* cot_vm, const double* cot_va, double* grad,
+                   double* vm_pu, double* va_degree, uint8_t* status, int32_t* iterations, hipStream_t st) {
+  if (const int rc = grad_prepare(h)) return rc;
+  const Dev& d = h->d;
+  const GradState g = h->grad;
+  const VjpState v = {K, M, cot_vm, cot_va, grad, va_degree};
+  const bool between = M > 0 || va_degree;
+  if (const int rc = whatif_drive(h, actions, dtype, K, nullptr, nullptr, status, iterations, vm_pu, st, [&](int k) {
+        if (between) launch_voltage_vjp(d, g, v, k, st);
+      }))
+    return rc;
+  if (vm_pu) launch_vjp_mask(d, K, actions, dtype, status, vm_pu, st);
+  HIPCHK(h, hipGetLastError());
+  return MAPDN_OK;
+}

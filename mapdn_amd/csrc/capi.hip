@@ -1351,6 +1351,31 @@ int mapdn_action_gradients(mapdn_handle* h, const void* actions, int32_t actions
   return grad_run(h, actions, actions_dtype, n_candidates, grad, reward, info, status, iterations, vm_pu, (hipStream_t)stream);
 } MAPDN_CATCH(h)
 
+// The voltages of every candidate that mapdn_evaluate_actions would score, and the products of n_cotangents caller-supplied cotangents
+// over them with their Jacobian by the actions (vjp.hip; vjp_run).  The argument checks come first, then the refusals, both on a
+// host-only handle too; nothing is launched on a refusal.
+int mapdn_voltage_vjp(mapdn_handle* h, const void* actions, int32_t actions_dtype, int32_t n_candidates, int32_t n_cotangents,
+                      const double* cot_vm, const double* cot_va, double* grad, double* vm_pu, double* va_degree, uint8_t* status,
+                      int32_t* iterations, void* stream) try {
+  if (!h) return MAPDN_E_INVALID;
+  if (!actions || !status) return api_fail(h, MAPDN_E_INVALID, "voltage_vjp: null buffer (actions and status are required)");
+  if (actions_dtype != MAPDN_F32 && actions_dtype != MAPDN_F64) return api_fail(h, MAPDN_E_INVALID, "voltage_vjp: bad actions dtype");
+  if (n_candidates < 1 || n_candidates > MAPDN_WHATIF_MAX_CANDIDATES)
+    return api_fail(h, MAPDN_E_INVALID, "voltage_vjp: n_candidates must lie in 1 ... 1024 (MAPDN_WHATIF_MAX_CANDIDATES)");
+  if (n_cotangents < 0 || n_cotangents > MAPDN_VJP_MAX_COTANGENTS)
+    return api_fail(h, MAPDN_E_INVALID, "voltage_vjp: n_cotangents must lie in 0 ... 1024 (MAPDN_VJP_MAX_COTANGENTS)");
+  if (n_cotangents >= 1 && !cot_vm && !cot_va)
+    return api_fail(h, MAPDN_E_INVALID, "voltage_vjp: n_cotangents >= 1 needs cot_vm or cot_va (both are NULL)");
+  if ((n_cotangents == 0) != (grad == nullptr))
+    return api_fail(h, MAPDN_E_INVALID, "voltage_vjp: grad must be NULL with n_cotangents = 0 and a buffer otherwise");
+  if (const char* why = vjp_refusal(h)) return api_fail(h, MAPDN_E_INVALID, why);
+  NEEDDEV(h);
+  if (!h->was_reset) { h->err = "voltage_vjp before reset"; return MAPDN_E_STATE; }
+  HIPCHK(h, hipSetDevice(h->device));
+  return vjp_run(h, actions, actions_dtype, n_candidates, n_cotangents, cot_vm, cot_va, grad, vm_pu, va_degree, status, iterations,
+                 (hipStream_t)stream);
+} MAPDN_CATCH(h)
+
 // ---- the PPO half of MAPPO / IPPO's update (csrc/ppo.hip): argument checks here, nothing is launched on a refusal
 static bool ppo_shape_ok(int64_t rows, int32_t n) { return rows >= 1 && n >= 1 && rows <= ((int64_t)1 << 40) / n; }
 

@@ -585,3 +585,5 @@ void launch_stats(const Dev& d, long long* out, hipStream_t st) { hipLaunchKerne
 #include "grad_sparse.hip"
 // ... and the OPF baseline's linearisation on such a handle, by the same program on the blocks of J itself (opf_sparse.hip)
 #include "opf_sparse.hip"
+// ... and the voltages' vector-Jacobian products of mapdn_voltage_vjp (vjp.hip), on the tree tables and the workspace of grad.hip
+#include "vjp.hip"

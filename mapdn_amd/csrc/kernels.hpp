@@ -220,7 +220,7 @@ void launch_opf_linearise_sparse(const Dev& d, const OpfState& s, const OsM& m, 
 enum { WHATIF_SOLVED = 0, WHATIF_PF_FAILED = 2, WHATIF_STOPPED = CTL_STOPPED };
 struct WhatifState : CtlLoop {       // (vm_out here: [B][K][nbo], or nullptr; a_sol, n_active: not used)
   int32_t K;
-  double *reward, *info;             // [B][K], [B][K][MAPDN_N_INFO]
+  double *reward, *info;             // [B][K], [B][K][MAPDN_N_INFO]; nullptr (both): not written (mapdn_voltage_vjp)
   uint8_t* status_out;               // [B][K]
   int32_t* iters_out;                // [B][K] Newton iterations of the candidate's solve, or nullptr
 };
@@ -239,6 +239,18 @@ struct GradState {
   double* grad;                      // [B][K][ns] env-major
 };
 void launch_action_grad(const Dev& d, const GradState& s, int k, hipStream_t st);
+
+// ---- mapdn_voltage_vjp (vjp.hip, vjp.hpp; baselines_host.hpp vjp_run): M cotangents over the bus voltages of every candidate times the
+// Jacobian of those voltages by the actions, in the what-if frame.  Beside GradState (whose tables, workspace and frame rows it uses; its
+// K and grad are not read): the caller's cotangents and outputs.
+struct VjpState {
+  int32_t K, M;
+  const double *cot_vm, *cot_va;     // [B][K][M][nbo] env-major, or nullptr: zeros
+  double* grad;                      // [B][K][M][ns] env-major (M == 0: not written)
+  double* va_out;                    // [B][K][nbo] res_bus.va_degree of the candidate, or nullptr
+};
+void launch_voltage_vjp(const Dev& d, const GradState& s, const VjpState& v, int k, hipStream_t st);
+void launch_vjp_mask(const Dev& d, int K, const void* actions, int dtype, const uint8_t* status, double* vm_pu, hipStream_t st);
 
 // ---- mapdn_action_gradients on a k_nr_sparse handle (grad_sparse.hip, grad_sparse.hpp; mapdn_env_config.grad_meshed = 1): the same
 // adjoint system solved by the handle's elimination program on transposed blocks.  Its own argument block beside GradState (whose act,

@@ -126,10 +126,11 @@ __global__ void __launch_bounds__(DL * DS) k_whatif_score(Dev d, WhatifState s, 
     for (int r = sl; r < d.nbo; r += DS) vm[r] = conv ? d.nrbuf[(size_t)s.vm_row[r] * S + e] : __builtin_nan("");
   }
   if (sl != 0) return;
-  double* inf = s.info + row * WHATIF_N_INFO;
+  // (reward and info are nullptr in mapdn_voltage_vjp's frame, which reports the voltages, the status and the iterations alone)
+  double* inf = s.info ? s.info + row * WHATIF_N_INFO : nullptr;
   if (!act) {
-    s.reward[row] = __builtin_nan("");
-    for (int c = 0; c < WHATIF_N_INFO; ++c) inf[c] = __builtin_nan("");
+    if (s.reward) s.reward[row] = __builtin_nan("");
+    if (inf) for (int c = 0; c < WHATIF_N_INFO; ++c) inf[c] = __builtin_nan("");
     s.status_out[row] = CTL_STOPPED;
     if (s.iters_out) s.iters_out[row] = 0;
     return;
@@ -138,9 +139,12 @@ __global__ void __launch_bounds__(DL * DS) k_whatif_score(Dev d, WhatifState s, 
 #pragma unroll
   for (int q = 0; q < WT_N; ++q) tot[q] = s_part[q][0][el];
   const WhatifCfg c = {d.nbo, d.n_line, d.ns, d.use_line_weight, d.voltage_weight, d.q_weight, d.line_weight};
-  s.reward[row] = whatif_report(tot, c, conv, out);
+  const double reward = whatif_report(tot, c, conv, out);
+  if (s.reward) s.reward[row] = reward;
+  if (inf) {
 #pragma unroll
-  for (int i = 0; i < WHATIF_N_INFO; ++i) inf[i] = out[i];
+    for (int i = 0; i < WHATIF_N_INFO; ++i) inf[i] = out[i];
+  }
   s.status_out[row] = conv ? WHATIF_SOLVED : WHATIF_PF_FAILED;
   if (s.iters_out) s.iters_out[row] = s.nr_iters[e];
 }

@@ -56,6 +56,32 @@ def _as_dict(kwargs):
     raise TypeError("env args must be a dict or a namedtuple")
 
 
+class _DifferentiableVoltages(torch.autograd.Function):
+    """VoltageControlBatch.differentiable_voltages: forward = solve_actions, backward = one voltage_vjp call with M = 1"""
+
+    @staticmethod
+    def forward(ctx, actions, env):
+        a = env._candidates(actions, "differentiable_voltages")
+        vm, va, st, _ = env.solve_actions(a)
+        ctx.env, ctx.version, ctx.like = env, env._state_version, (actions.shape, actions.device, actions.dtype)
+        ctx.save_for_backward(a, st)
+        ctx.mark_non_differentiable(st)
+        return vm, va, st
+
+    @staticmethod
+    def backward(ctx, g_vm, g_va, _g_st):
+        env = ctx.env
+        if env._state_version != ctx.version:
+            raise RuntimeError("differentiable_voltages: the env's state has moved (step / reset) between forward and backward; "
+                               "the gradient of the forward's voltages can no longer be formed")
+        a, st = ctx.saved_tensors
+        cot = [g.detach().to(torch.float64).unsqueeze(2).contiguous() for g in (g_vm, g_va)]
+        grad = env._voltage_vjp(a, 1, cot[0], cot[1])[0][:, :, 0]
+        grad = torch.where((st == 0).unsqueeze(-1), grad, torch.zeros_like(grad))
+        shape, device, dtype = ctx.like
+        return grad.reshape(shape).to(device=device, dtype=dtype), None
+
+
 class VoltageControlBatch:
     """B env instances sharing one network; state lives on the GPU in env-minor SoA arrays.
 
@@ -127,6 +153,7 @@ class VoltageControlBatch:
         self._obs_hist = None
         self._was_reset = False
         self._stepped = False
+        self._state_version = 0                                     # bumped by whatever moves the env's state (differentiable_voltages)
         self._obs_fresh = None                                      # dtype of the obs buffer that holds the current state's obs
         # step() = mapdn_step_obs (False, or MAPDN_FUSED_STEP=0 for A/B runs: mapdn_step, then mapdn_get_obs)
         self.fused_step = os.environ.get("MAPDN_FUSED_STEP", "1") != "0"
@@ -200,6 +227,7 @@ class VoltageControlBatch:
                                              self.max_reset_tries, self._stream()), self._h)
         self._was_reset = True
         self._stepped = False
+        self._state_version += 1
         self._obs_fresh = None
         if self.history > 1:
             self._obs_hist = None
@@ -233,6 +261,7 @@ class VoltageControlBatch:
                                                 self._reward.data_ptr(), self._term.data_ptr(), self._info.data_ptr(),
                                                 self._stream()), self._h)
             self._stepped = True
+            self._state_version += 1
             self._obs_fresh = None
             return self._out(self._reward), self._out(self._term), self._out(self._info)
         buf = self._obs_buf(self.obs_dtype)
@@ -241,6 +270,7 @@ class VoltageControlBatch:
                                                 self._reward.data_ptr(), self._term.data_ptr(), self._info.data_ptr(),
                                                 buf.data_ptr(), self._code(self.obs_dtype), self._stream()), self._h)
         self._stepped = True
+        self._state_version += 1
         self._obs_fresh = self.obs_dtype
         return self._out(self._reward), self._out(self._term), self._out(self._info)
 
@@ -560,6 +590,117 @@ class VoltageControlBatch:
                 raise
         return (grad, reward, info, st, it, vm) if vm_pu else (grad, reward, info, st, it)
 
+    def _candidates(self, actions, who):
+        """actions as evaluate_actions takes them -> a contiguous CUDA tensor [B, K, n_sgen], float32 or float64"""
+        a = actions
+        if not torch.is_tensor(a):
+            a = torch.as_tensor(np.asarray(a), device=self.device)
+        if a.device != self.device:
+            a = a.to(self.device)
+        if a.dtype not in (torch.float32, torch.float64):
+            a = a.to(torch.float64)
+        B = self.n_envs
+        if a.dim() == 2:
+            a = a.reshape(B, 1, self.n_sgen)
+        if a.dim() != 3 or a.shape[0] != B or a.shape[2] != self.n_sgen or a.shape[1] < 1:
+            raise ValueError(f"{who}: actions must be [{B}, K, {self.n_sgen}] or [{B}, {self.n_sgen}], got {tuple(a.shape)}")
+        return a.detach().contiguous()
+
+    def _cotangent(self, c, K, who):
+        """a cotangent over the buses -> (contiguous float64 CUDA tensor [B, K, M, n_bus] or None, squeezed: it came as [B, K, n_bus])"""
+        if c is None:
+            return None, None
+        if not torch.is_tensor(c):
+            c = torch.as_tensor(np.asarray(c), device=self.device)
+        c = c.detach().to(device=self.device, dtype=torch.float64)
+        squeezed = c.dim() == 3
+        if squeezed:
+            c = c.unsqueeze(2)
+        if c.dim() != 4 or c.shape[0] != self.n_envs or c.shape[1] != K or c.shape[3] != self.n_bus:
+            raise ValueError(f"{who}: a cotangent must be [{self.n_envs}, {K}, M, {self.n_bus}] or [{self.n_envs}, {K}, {self.n_bus}], got {tuple(c.shape)}")
+        return c.contiguous(), squeezed
+
+    def voltage_vjp(self, actions, cot_vm=None, cot_va=None):
+        """The bus voltages that step(actions[:, k]) would commit, differentiated by the actions, for cotangents of the caller's choice
+        (mapdn_voltage_vjp, include/mapdn.h).  actions as evaluate_actions takes them; cot_vm / cot_va float64
+        [B, K, M, n_bus], or [B, K, n_bus] for one cotangent (M = 1, squeezed on return); either may be None (zeros), not both.
+        Returns (grad float64 [B, K, M, n_sgen] with grad[e, k, m, j] = sum_b cot_vm[e, k, m, b] d vm_pu[e, k, b] / d actions[e, k, j]
+        + cot_va[e, k, m, b] d va_degree[e, k, b] / d actions[e, k, j], vm_pu float64 [B, K, n_bus], va_degree float64 [B, K, n_bus],
+        status uint8 [B, K], iterations int32 [B, K]); vm_pu, status and iterations are bit for bit evaluate_actions'.  One
+        factorisation of the power flow's Jacobian per (env, candidate) serves all M cotangents.  The cotangent entries of the ext_grid
+        bus are never read; an sgen on that bus gets exactly 0.  Rows of status 2 and 3 are NaN in grad, vm_pu and va_degree, and so is a
+        solved row in which some lim_j * a_j is not finite.  Radial nets on the tree solver with constant-power loads, no generators
+        and no fused buses; anything else raises NotImplementedError.  The env's state and its next step() are not affected."""
+        a = self._candidates(actions, "voltage_vjp")
+        K = int(a.shape[1])
+        cvm, sq_vm = self._cotangent(cot_vm, K, "voltage_vjp")
+        cva, sq_va = self._cotangent(cot_va, K, "voltage_vjp")
+        if cvm is None and cva is None:
+            raise ValueError("voltage_vjp: give cot_vm or cot_va (solve_actions returns the voltages alone)")
+        if cvm is not None and cva is not None and (cvm.shape != cva.shape or sq_vm != sq_va):
+            raise ValueError(f"voltage_vjp: cot_vm {tuple(cvm.shape)} and cot_va {tuple(cva.shape)} must have one shape")
+        M = int((cvm if cvm is not None else cva).shape[2])
+        if M < 1:
+            raise ValueError("voltage_vjp: a cotangent must hold at least one row (M >= 1)")
+        grad, vm, va, st, it = self._voltage_vjp(a, M, cvm, cva)
+        if sq_vm or sq_va:
+            grad = grad[:, :, 0]
+        return grad, vm, va, st, it
+
+    def _voltage_vjp(self, a, M, cvm, cva):
+        B, K, dv, f64 = self.n_envs, int(a.shape[1]), self.device, torch.float64
+        grad = torch.empty(B, K, M, self.n_sgen, dtype=f64, device=dv) if M else None
+        vm = torch.empty(B, K, self.n_bus, dtype=f64, device=dv)
+        va = torch.empty(B, K, self.n_bus, dtype=f64, device=dv)
+        st = torch.empty(B, K, dtype=torch.uint8, device=dv)
+        it = torch.empty(B, K, dtype=torch.int32, device=dv)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            try:
+                _lib.check(self._lib.mapdn_voltage_vjp(self._h, a.data_ptr(), self._code(a.dtype), K, M, ptr(cvm), ptr(cva), ptr(grad),
+                                                       vm.data_ptr(), va.data_ptr(), st.data_ptr(), it.data_ptr(), self._stream()), self._h)
+            except _lib.MapdnError as err:
+                if "not supported" in str(err):
+                    raise NotImplementedError(str(err)) from None
+                raise
+        return grad, vm, va, st, it
+
+    def solve_actions(self, actions):
+        """The bus voltages that step(actions[:, k]) would commit, without taking the step: voltage_vjp without a cotangent (M = 0).
+        Returns (vm_pu float64 [B, K, n_bus], va_degree float64 [B, K, n_bus], status uint8 [B, K], iterations int32 [B, K]); NaN rows
+        and refusals as voltage_vjp's."""
+        return self._voltage_vjp(self._candidates(actions, "solve_actions"), 0, None, None)[1:]
+
+    def voltage_jacobian(self, actions, buses=None):
+        """d vm_pu[e, k, buses] / d actions[e, k, :] as float64 [B, K, len(buses), n_sgen] (buses: indices into the bus table, default all),
+        by voltage_vjp with unit cotangents on cot_vm, at most 1024 per call."""
+        a = self._candidates(actions, "voltage_jacobian")
+        B, K = self.n_envs, int(a.shape[1])
+        buses = list(range(self.n_bus)) if buses is None else [int(b) for b in buses]
+        if any(b < 0 or b >= self.n_bus for b in buses):
+            raise ValueError(f"voltage_jacobian: buses must lie in 0 ... {self.n_bus - 1}")
+        out = torch.empty(B, K, len(buses), self.n_sgen, dtype=torch.float64, device=self.device)
+        for lo in range(0, len(buses), 1024):
+            chunk = buses[lo:lo + 1024]
+            cot = torch.zeros(B, K, len(chunk), self.n_bus, dtype=torch.float64, device=self.device)
+            cot[:, :, torch.arange(len(chunk), device=self.device), torch.as_tensor(chunk, device=self.device)] = 1.0
+            out[:, :, lo:lo + len(chunk)] = self._voltage_vjp(a, len(chunk), cot, None)[0]
+        return out
+
+    def differentiable_voltages(self, actions):
+        """(vm_pu, va_degree, status) of solve_actions, the first two with a grad_fn: the batched power flow as a differentiable layer of
+        torch.autograd, so that any loss written in torch on the voltages gets its exact gradient by the actions.  Forward is
+        solve_actions.  Backward is ONE voltage_vjp call with the cotangents autograd hands down (M = 1): it solves the same power
+        flow again, since nothing of the forward's factors is kept between the two calls.  Rows of status != 0 (whose voltages are
+        NaN) get a zero gradient here; the raw calls return NaN there.  The gradient is that of the env's state at the forward:
+        backward raises RuntimeError if step(), reset() or manual_reset() has moved the state in between."""
+        a = actions
+        if not torch.is_tensor(a):
+            a = torch.as_tensor(np.asarray(a), device=self.device)
+        self._candidates(a, "differentiable_voltages")                  # (the shape check, before autograd sees the call)
+        vm, va, st = _DifferentiableVoltages.apply(a, self)
+        return vm, va, st
+
     def difference_rewards(self, actions, default=0.0):
         """Ground-truth difference rewards of a joint action [B, n_agents]: r(a) - r(a with agent i's entry replaced by `default`), by one
         evaluate_actions call on n_agents + 1 candidates (the joint action first).  Returns (reward float64 [B], difference float64
@@ -784,6 +925,7 @@ class VoltageControl(MultiAgentEnv):
                     _lib.check(b._lib.mapdn_step_obs(b._h, z["act"], _lib.F64, int(add_noise), z["reward"], z["term"], z["info"],
                                                      z["obs"], _lib.F64, b._stream()), b._h)
                 b._stepped = True
+                b._state_version += 1
                 b._obs_fresh = None                                   # (the batch object's own device-side obs buffer was not filled)
             else:
                 self._act_dev.copy_(self._act_host, non_blocking=True)
@@ -834,6 +976,19 @@ class VoltageControl(MultiAgentEnv):
         g, r, info, st, _ = self._b.action_gradients(torch.as_tensor(c))
         vals = info[0].cpu().numpy()
         return g[0].cpu().numpy(), r[0].cpu().numpy(), [{k: float(v) for k, v in zip(INFO_KEYS, row)} for row in vals], st[0].cpu().numpy()
+
+    def solve_actions(self, candidates):
+        """VoltageControlBatch.solve_actions for this one env, as numpy: candidates [K, n_sgen] -> (vm_pu ndarray [K, n_bus], va_degree
+        ndarray [K, n_bus], status ndarray [K], iterations ndarray [K])"""
+        c = np.asarray(candidates, dtype=np.float64).reshape(1, -1, self._b.n_sgen)
+        return tuple(x[0].cpu().numpy() for x in self._b.solve_actions(torch.as_tensor(c)))
+
+    def voltage_vjp(self, candidates, cot_vm=None, cot_va=None):
+        """VoltageControlBatch.voltage_vjp for this one env, as numpy: candidates [K, n_sgen], cotangents [K, M, n_bus] or [K, n_bus]
+        -> (grad ndarray [K, M, n_sgen] or [K, n_sgen], vm_pu [K, n_bus], va_degree [K, n_bus], status [K], iterations [K])"""
+        c = np.asarray(candidates, dtype=np.float64).reshape(1, -1, self._b.n_sgen)
+        cot = [None if x is None else torch.as_tensor(np.asarray(x, dtype=np.float64)[None]) for x in (cot_vm, cot_va)]
+        return tuple(x[0].cpu().numpy() for x in self._b.voltage_vjp(torch.as_tensor(c), *cot))
 
     def _obs_list(self, obs):
         o = obs[0].double().cpu().numpy()
